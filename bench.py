@@ -103,32 +103,39 @@ def parse():
     ap.add_argument("--refstyle-steps", type=int, default=6, help="FV2P workload: extra steps in the reference's call structure, reported as baseline / vs_restated_structure (vs_baseline itself stays null: BASELINE.md has no published number) (0 = skip)")
     ap.add_argument("--dry-run", action="store_true", help="launcher / rendezvous check without a GPU: ranks join a gloo group, reduce, rank 0 prints n_gpus")
     ap.add_argument("--pyprofile", action="store_true", help="cProfile the timed steps (host-overhead hunting; prints to stderr)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, call the timed step once more from the state the run started from and write what it "
+                         "computed (loss, gradients) as DIR/<name>.npy, float32, at most 64 MB in all (larger arrays: a fixed seeded "
+                         "sample); see dump_step")
     args = ap.parse_args()
+    given = lambda flag: any(a == flag or a.startswith(flag + "=") for a in sys.argv[1:])
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.batch <= 0:
         args.batch = 3 if args.workload == "fv2p" else 2 if args.workload == "fv2p-waymo" else 4
     if args.workload == "fv2p-waymo":
-        if "--points" not in sys.argv:
+        if not given("--points"):
             args.points = 180000
-        if "--steps" not in sys.argv:
-            args.steps, args.warmup = 20, (args.warmup if "--warmup" in sys.argv else 4)
-        if "--prefetch" not in sys.argv:
+        if not given("--steps"):
+            args.steps, args.warmup = 20, (args.warmup if given("--warmup") else 4)
+        if not given("--prefetch"):
             args.prefetch = 0
-    if args.workload == "mgaf" and "--steps" not in sys.argv:
-        args.steps, args.warmup = 30, (args.warmup if "--warmup" in sys.argv else 5)
-    if args.workload == "fv2p" and "--prefetch" not in sys.argv:
+    if args.workload == "mgaf" and not given("--steps"):
+        args.steps, args.warmup = 30, (args.warmup if given("--warmup") else 5)
+    if args.workload == "fv2p" and not given("--prefetch"):
         args.prefetch = 0   # measured: the input-pipeline thread does not pay here (65.3 vs 63.7 ms per step); the step is not launch bound
     # ONE stream arrangement for every N: a 1 -> 8 scan compares like with like and the N = 1 point of a scaling run is the headline
     # run (round 2 switched multi-GPU ranks to another arrangement; RCCL's stream beside the dense-branch stream is unmeasured — the
     # in-line figure `inline_ms_per_step` is the arrangement-free number to fall back on)
     if args.ahead_thread < 0:
         args.ahead_thread = 1 if args.workload == "fv2p-waymo" else 0
-    if args.workload in ("fv2p", "fv2p-waymo") and "--ahead" not in sys.argv and not args.prefetch:
+    if args.workload in ("fv2p", "fv2p-waymo") and not given("--ahead") and not args.prefetch:
         # batch t+1 is voxelised and its rulebooks are built on the sampling stream, in front of that batch's sampler, between forward
         # and backward of step t: the sparse backbone of step t+1 then starts without its five host waits (33.65 -> 32.75 ms).  On a
         # stream of its own the same preparation costs the step 20 - 30 ms (a fifth stream on four hardware queues)
         args.ahead = 2
-    if args.steps == 300 and args.workload == "fv2p" and "--steps" not in sys.argv:
-        args.steps, args.warmup = 40, (args.warmup if "--warmup" in sys.argv else 5)
+    if args.steps == 300 and args.workload == "fv2p" and not given("--steps"):
+        args.steps, args.warmup = 40, (args.warmup if given("--warmup") else 5)
     return args
 
 
@@ -158,11 +165,6 @@ class Later(object):
             raise e
 
 
-# every side-stream input pipeline off: the plain in-line step; and none of the optional N > 1 legs (the other gradient synchronisation
-# has never met RCCL on real xGMI: if IT is what hung the first attempt, the repeat must still deliver the line)
-SAFE_FLAGS = ["--fps-ahead", "0", "--ahead", "0", "--prefetch", "0", "--dense-stream", "0", "--sync-leg-steps", "0"]
-
-
 def beat(phase):
     """Heartbeat of a supervised measurement (see supervise): "<time> <phase>" into the file the supervisor watches."""
     path = os.environ.get("FV2P_BENCH_HEARTBEAT")
@@ -189,82 +191,78 @@ def supervise(args):
     search on cold caches (one fresh box in three, until build_fv2p_step took those steps on one stream).  A hung benchmark
     reports nothing, so: the child writes a heartbeat after every step;
     when a stepping child is silent for --stall seconds (or a child that has not started stepping for --watchdog seconds) its
-    process tree is killed — only what this call created — and the measurement is repeated once with the side-stream arrangements off
-    (SAFE_FLAGS: the plain point-branch stream, sampling in the step; 38.4 instead of 34.3 ms per step)."""
+    process tree is killed — only what this call created — and the call ends with exit status 124.  A hung run is not started again:
+    what hung the device is a finding to be explained, not retried."""
     import signal
     import socket
     import subprocess
     import tempfile
     ranked = "RANK" in os.environ
-    attempts = [[]] + ([SAFE_FLAGS] if args.workload in ("fv2p", "fv2p-waymo") and args.watchdog > 0 else [])
-    rc = 1
-    for attempt, extra in enumerate(attempts):
-        hb = tempfile.NamedTemporaryFile(prefix="fv2p_bench_hb_", delete=False)
-        hb.close()
-        os.unlink(hb.name)
-        env = dict(os.environ, FV2P_BENCH_INNER="1", FV2P_BENCH_HEARTBEAT=hb.name, FV2P_BENCH_ATTEMPT=str(attempt))
-        if args.gpus > 1 and not ranked:
-            with socket.socket() as sk:
-                sk.bind(("127.0.0.1", 0))
-                port = sk.getsockname()[1]
-            cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}", "--master-addr", "127.0.0.1",
-                   "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:] + extra
-        else:
-            cmd = [sys.executable, os.path.abspath(__file__)] + sys.argv[1:] + extra
-        child = subprocess.Popen(cmd, env=env, start_new_session=True)
+    hb = tempfile.NamedTemporaryFile(prefix="fv2p_bench_hb_", delete=False)
+    hb.close()
+    os.unlink(hb.name)
+    env = dict(os.environ, FV2P_BENCH_INNER="1", FV2P_BENCH_HEARTBEAT=hb.name, FV2P_BENCH_ATTEMPT="0")
+    if args.gpus > 1 and not ranked:
+        with socket.socket() as sk:
+            sk.bind(("127.0.0.1", 0))
+            port = sk.getsockname()[1]
+        cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}", "--master-addr", "127.0.0.1",
+               "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
+    else:
+        cmd = [sys.executable, os.path.abspath(__file__)] + sys.argv[1:]
+    child = subprocess.Popen(cmd, env=env, start_new_session=True)
 
-        def stop(*_):   # the launcher above us ends the job: take the child along
-            try:
-                os.killpg(child.pid, signal.SIGKILL)
-            except ProcessLookupError:
-                pass
-            os._exit(143)
-        previous = signal.signal(signal.SIGTERM, stop) if ranked else None
-        started, hung = time.time(), None
-        last = (started, "start")     # the last heartbeat that parsed
-        while child.poll() is None:
-            time.sleep(0.5)
-            if args.watchdog <= 0:
-                continue
-            now = time.time()
-            try:
-                with open(hb.name) as f:
-                    t, phase = f.read().split(None, 1)
-                last = (float(t), phase.strip())
-            except (OSError, ValueError):
-                pass
-            limit = args.stall if last[1] in ("step", "sync") else args.watchdog
-            if now - last[0] > limit:
-                hung = f"no heartbeat for {limit} s in phase '{last[1]}'"
-            if hung:
-                break
-        if previous is not None:
-            signal.signal(signal.SIGTERM, previous)
-        try:
-            os.unlink(hb.name)
-        except OSError:
-            pass
-        if hung is None:
-            return child.returncode
-        print(f"[bench] {hung}: stopping the run" + ("" if extra else " and repeating it with " + " ".join(SAFE_FLAGS)), file=sys.stderr)
-        # the tree this call created, nothing else: the launcher's workers may sit in sessions of their own
-        try:
-            import psutil
-            tree = psutil.Process(child.pid).children(recursive=True)
-        except Exception:
-            tree = []
-        for proc in tree:
-            try:
-                proc.kill()
-            except Exception:
-                pass
+    def stop(*_):   # the launcher above us ends the job: take the child along
         try:
             os.killpg(child.pid, signal.SIGKILL)
         except ProcessLookupError:
             pass
-        child.wait()
-        rc = 124
-    return rc
+        os._exit(143)
+    previous = signal.signal(signal.SIGTERM, stop) if ranked else None
+    started, hung = time.time(), None
+    last = (started, "start")     # the last heartbeat that parsed
+    while child.poll() is None:
+        time.sleep(0.5)
+        if args.watchdog <= 0:
+            continue
+        now = time.time()
+        try:
+            with open(hb.name) as f:
+                t, phase = f.read().split(None, 1)
+            last = (float(t), phase.strip())
+        except (OSError, ValueError):
+            pass
+        limit = args.stall if last[1] in ("step", "sync") else args.watchdog
+        if now - last[0] > limit:
+            hung = f"no heartbeat for {limit} s in phase '{last[1]}'"
+        if hung:
+            break
+    if previous is not None:
+        signal.signal(signal.SIGTERM, previous)
+    try:
+        os.unlink(hb.name)
+    except OSError:
+        pass
+    if hung is None:
+        return child.returncode
+    print(f"[bench] {hung}: stopping the run", file=sys.stderr)
+    # the tree this call created, nothing else: the launcher's workers may sit in sessions of their own
+    try:
+        import psutil
+        tree = psutil.Process(child.pid).children(recursive=True)
+    except Exception:
+        tree = []
+    for proc in tree:
+        try:
+            proc.kill()
+        except Exception:
+            pass
+    try:
+        os.killpg(child.pid, signal.SIGKILL)
+    except ProcessLookupError:
+        pass
+    child.wait()
+    return 124
 
 
 def build_step(args, device, rank, world):
@@ -386,6 +384,7 @@ def build_step(args, device, rank, world):
             flat_sync.broadcast_parameters(0)
     step.set_sync = set_sync
     step.flat_sync = lambda: flat_sync
+    step.opt = opt
 
     def step_phases(i, acc):
         """Same step with a device sync after every phase: (host time until the calls returned, time until the GPU drained)."""
@@ -726,6 +725,7 @@ def build_fv2p_step(args, device, rank, world):
     step.inline = step_inline
     step.set_sync = set_sync
     step.flat_sync = lambda: flat_sync
+    step.opt = opt
     return model, step, voxelize, pool
 
 
@@ -1107,6 +1107,45 @@ def cpu_baseline(model, args):
                       f"dense-grid-equivalent rulebook + per-offset gather/mm/scatter backbone fwd+bwd (torch CPU, {cores} threads), {dt:.1f} s"}
 
 
+DUMP_BUDGET = 64 * 10 ** 6
+
+
+def dump_step(out_dir, run_step, i, model, opt, start_state, device):
+    """--dump-outputs: one more call of the timed step function, with the streams and kernels of the timed steps, on the state the run
+    started from, written as float32 .npy files: the loss the call returns and the gradients it leaves on the parameters (flattened in
+    named_parameters() order; past DUMP_BUDGET a fixed seeded sample of entries, the same on every run and build).
+
+    Why not the state the timed steps reached: that trajectory is not reproducible.  MIOpen's training-mode BatchNorm2d and rocBLAS's
+    split-K GEMMs round differently from run to run, proposals, RoI sampling and ReLU masks turn last-bit differences into
+    different decisions, and after 25 steps two runs differ in the loss by 0.7 of 3.2 (0.015 even under deterministic library
+    settings).  From one fixed state the step is a fixed function of its inputs: two runs give the same loss bit for bit and
+    gradients within 1.3e-7 of a largest entry of 0.11 (the float atomics of a few backward kernels and libraries).  The parameters
+    after the optimiser step are not written:
+    AdamW's first step moves every parameter by lr * sign(gradient), so the rounding noise of a gradient that is zero in exact
+    arithmetic (a conv bias ahead of BatchNorm) would show as a full update."""
+    params, rng = start_state
+    with torch.no_grad():
+        model.load_state_dict(params)
+    opt.state.clear()                        # fresh AdamW moments, as at the first step of the run
+    if hasattr(opt, "_lean"):
+        opt._lean = None
+    torch.cuda.set_rng_state(rng, device)
+    loss = run_step(i)
+    torch.cuda.synchronize()
+    if out_dir is None:
+        return
+    os.makedirs(out_dir, exist_ok=True)
+    ps = [p for _, p in model.named_parameters() if p.requires_grad]
+    arrays = {"loss": loss.detach().float().reshape(1),
+              "gradients": torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().float().reshape(-1) for p in ps])}
+    room = (DUMP_BUDGET - 4096) // 4
+    for name, t in arrays.items():
+        a = t.cpu().numpy()
+        if a.size > room:
+            a = a[np.sort(np.random.default_rng(0).choice(a.size, room, replace=False))]
+        np.save(os.path.join(out_dir, f"{name}.npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
 def workload_name(args):
     if args.workload == "fv2p-waymo":
         return ("FV2P (waymo_fv2p_e30.yaml, Vehicle) end-to-end train step on Waymo-shaped synthetic clouds (~180 k points, 360 degrees, "
@@ -1180,14 +1219,6 @@ def main():
         args.wgrad_stream = 0 if args.workload in ("fv2p", "fv2p-waymo") else 1
     if "FV2P_WGRAD_OVERLAP" not in os.environ:
         os.environ["FV2P_WGRAD_OVERLAP"] = str(int(bool(args.wgrad_stream)))     # read once by the compiled binding at its first backward
-    if (world > 1 or dist_utils.solo_ddp()) and "GPU_MAX_HW_QUEUES" not in os.environ:
-        # The step keeps three to four streams busy (calling stream, dense branch, key-point sampling + next batch, and - when asked for -
-        # weight gradients) on the runtime's four hardware queues; RCCL's stream is one more.  Measured on one GPU with a one-rank DDP and
-        # a stand-in for the all-reduce traffic on a communication stream (tools/ddp_stream_matrix.sh, profiles/r05_ddp_stream_matrix.txt),
-        # ms per step at 4 / 5 / 6 / 8 queues: 42.4 / 41.2 / 35.5 / 63.0 without the weight-gradient stream (46.9 / 46.9 / 36.5 / 61.2 with
-        # it): with four queues the communication stream shares one with the 13 ms sampler.  Without DDP the count does not matter (29.9 /
-        # 29.9 / 30.1 at 4 / 6 / 8).  Read by the HIP runtime when it initialises, i.e. after this line.
-        os.environ["GPU_MAX_HW_QUEUES"] = "6"
     assert torch.cuda.is_available(), "bench.py needs a GPU (the hot path has no CPU fallback)"
     # FV2P_FORCE_DEVICE / FV2P_DIST_BACKEND: test hooks to exercise the multi-rank path on a one-GPU box (all ranks on one
     # device, gloo instead of RCCL); the driver's runs set neither
@@ -1204,6 +1235,8 @@ def main():
     torch.backends.cudnn.benchmark = bool(args.miopen_find)
     build = build_fv2p_step if args.workload in ("fv2p", "fv2p-waymo") else build_step
     model, step, voxelize, pool = build(args, device, rank, world)
+    # --dump-outputs: the state every run starts from (parameters, buffers, the device generator), for the dump step below
+    start_state = ({k: v.detach().clone() for k, v in model.state_dict().items()}, torch.cuda.get_rng_state(device)) if args.dump_outputs else None
     # the detector's first SAFE_FIRST_STEPS GPU steps run on the calling stream only (fv2p_model: MIOpen's first-call search): with fewer
     # warm-up steps than that they would fall into the timed region, so they are taken here, untimed, and reported as guard_steps
     guard_steps = 0
@@ -1292,6 +1325,8 @@ def main():
     dist_utils.barrier()
     torch.cuda.synchronize()
     dt = dist_utils.max_over_ranks(time.perf_counter() - t0, device)
+    if args.dump_outputs:   # after the timing, before the extra legs and probes below
+        dump_step(args.dump_outputs if rank == 0 else None, run_step, args.warmup + args.steps, model, step.opt, start_state, device)
 
     # ---- N > 1: what the collective library actually did (one driver run must explain itself: no 8-GPU box was available to the builder)
     dist_info = None
