@@ -105,6 +105,24 @@ __global__ __launch_bounds__(256) void bev_scatter_k(const float* __restrict__ g
   }
 }
 
+// Entries of the deterministic backward (fv2p_scatter_add): e = 4 * point + corner (a, b, c, d), row b * H * W + corner offset of the
+// [B * H * W][C] gradient, coefficient the corner's weight, source the point's row of gout.
+__global__ void bev_entries_k(const float* __restrict__ xs, const float* __restrict__ ys, int batch, long long n, int h, int w, int c,
+                              int* __restrict__ dst, int64_t* __restrict__ off, float* __restrict__ coef) {
+  const long long p = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (p >= static_cast<long long>(batch) * n) return;
+  const Corners k = bev_corners(xs[p], ys[p], h, w);
+  const long long base = (p / n) * static_cast<long long>(h) * w;
+  const long long rows[4] = {k.a, k.b, k.c, k.d};
+  const float wt[4] = {k.wa, k.wb, k.wc, k.wd};
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    dst[4 * p + u] = static_cast<int>(base + rows[u]);
+    off[4 * p + u] = p * c;
+    coef[4 * p + u] = wt[u];
+  }
+}
+
 // [B][R][S] -> [B][S][R] (R = C, S = H*W: channel-first -> channel-last, and back with the roles swapped) through a 64 x 65 LDS tile:
 // 16-byte global accesses on both sides (a row of the tile is 256 contiguous bytes in the source, a column 256 contiguous bytes in the
 // destination), scalar LDS accesses with the odd pitch (two lanes per bank at most).  torch's .permute().contiguous() moves the same
@@ -207,6 +225,33 @@ extern "C" int fv2p_bev_interp_bwd(const float* grad_out, int batch, int c, int 
     const long long pts = static_cast<long long>(batch) * n;
     hipLaunchKernelGGL(bev_scatter_k, dim3(static_cast<unsigned>(ceil_div(pts, 4 * kBevRun))), dim3(256), 0, stream, grad_out, x, y, batch,
                        static_cast<long long>(n), h, w, c, gim);
+  }
+  if (channels_first)
+    if (int rc = launch_transpose(gim, batch, h * w, c, grad_bev, stream)) return rc;   // [B][HW][C] -> [B][C][HW]
+  FV2P_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" size_t fv2p_bev_interp_bwd_ws_bytes(int batch, int c, int h, int w, int channels_first, int64_t n) {
+  const size_t map = static_cast<size_t>(batch > 0 ? batch : 1) * (c > 0 ? c : 1) * (h > 0 ? h : 1) * (w > 0 ? w : 1);
+  return det_lists_bytes(static_cast<int64_t>(batch > 0 ? batch : 0) * (n > 0 ? n : 0) * 4, c > 0 ? c : 1, true, channels_first ? map : 0);
+}
+extern "C" int fv2p_bev_interp_bwd_gather(const float* grad_out, int batch, int c, int h, int w, int channels_first, const float* x, const float* y,
+                                          int64_t n, float* grad_bev, void* ws, size_t ws_bytes, fv2p_stream_t stream_) {
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  FV2P_REQUIRE(batch >= 1 && c >= 1 && h >= 1 && w >= 1 && n >= 0 && grad_bev, FV2P_EINVAL, "bev_interp_bwd_gather: bad arguments");
+  const int64_t cells = static_cast<int64_t>(batch) * h * w, entries = static_cast<int64_t>(batch) * n * 4;
+  FV2P_REQUIRE(cells < (1ll << 31) - 1 && entries < (1ll << 31), FV2P_ELIMIT, "bev_interp_bwd_gather: map or point count too large");
+  FV2P_REQUIRE(ws && ws_bytes >= fv2p_bev_interp_bwd_ws_bytes(batch, c, h, w, channels_first, n), FV2P_EWORKSPACE, "bev_interp_bwd_gather: workspace too small");
+  const size_t map = static_cast<size_t>(cells) * c;
+  const DetLists d = det_lists(ws, ws_bytes, entries, c, true, channels_first ? map : 0);
+  float* gim = channels_first ? d.stage : grad_bev;
+  FV2P_HIP(hipMemsetAsync(gim, 0, map * sizeof(float), stream));
+  if (n > 0) {
+    FV2P_REQUIRE(grad_out && x && y, FV2P_EINVAL, "bev_interp_bwd_gather: null pointer");
+    hipLaunchKernelGGL(bev_entries_k, dim3(static_cast<unsigned>(ceil_div(entries / 4, 256))), dim3(256), 0, stream, x, y, batch,
+                       static_cast<long long>(n), h, w, c, d.dst, d.off, d.coef);
+    if (int rc = fv2p_scatter_add(entries, c, cells, d.dst, d.off, d.coef, grad_out, 1, gim, d.sws, d.sws_bytes, stream)) return rc;
   }
   if (channels_first)
     if (int rc = launch_transpose(gim, batch, h * w, c, grad_bev, stream)) return rc;   // [B][HW][C] -> [B][C][HW]

@@ -70,6 +70,39 @@ struct Sizer {
   size_t bytes() const { return align_up(off); }
 };
 
+// Workspace of a deterministic backward (*_gather forms on fv2p_scatter_add): the entries' destination rows and source offsets,
+// optionally their coefficients and a row-major staging output of `stage` floats, then the scatter-add's own workspace.
+struct DetLists {
+  int* dst;
+  int64_t* off;
+  float* coef;
+  float* stage;
+  void* sws;
+  size_t sws_bytes;
+};
+static inline size_t det_lists_bytes(int64_t entries, int c, bool coef, size_t stage) {
+  const size_t e = static_cast<size_t>(entries > 0 ? entries : 1);
+  Sizer s;
+  s.take<int>(e);
+  s.take<int64_t>(e);
+  if (coef) s.take<float>(e);
+  if (stage) s.take<float>(stage);
+  s.take<char>(fv2p_scatter_add_ws_bytes(entries, c));
+  return s.bytes();
+}
+static inline DetLists det_lists(void* ws, size_t ws_bytes, int64_t entries, int c, bool coef, size_t stage) {
+  const size_t e = static_cast<size_t>(entries > 0 ? entries : 1);
+  Carver cv(ws, ws_bytes);
+  DetLists d;
+  d.dst = cv.take<int>(e);
+  d.off = cv.take<int64_t>(e);
+  d.coef = coef ? cv.take<float>(e) : nullptr;
+  d.stage = stage ? cv.take<float>(stage) : nullptr;
+  d.sws_bytes = fv2p_scatter_add_ws_bytes(entries, c);
+  d.sws = cv.take<char>(d.sws_bytes);
+  return d;
+}
+
 // One launch that fills up to 8 regions with a 32-bit pattern each (replaces a run of hipMemsetAsync calls: every
 // memset is its own dispatch, ~3 us of queue time each).  Regions are 4-byte aligned, sizes multiples of 4 bytes.
 struct FillJobs {

@@ -1635,6 +1635,31 @@ __global__ __launch_bounds__(256) void interp_fix_k(int c, int64_t entries, int6
   }
 }
 
+// Entries of the deterministic batch-layout gradients (fv2p_scatter_add): grad_out [B][C][P] channel-major, `per` = div * P entries
+// per sample, entry e = (b, j): row b * rows + idx[e] of a [B * rows][C] staging buffer, source column j / div of sample b.
+// group_points (div 1, P = npoints * nsample), gather_points (div 1, P = npoints), three_interpolate (div 3, P = n).
+__global__ void det_batch_entries_k(int64_t entries, int64_t per, int div, int c, int rows, const int* __restrict__ idx,
+                                    int* __restrict__ dst, int64_t* __restrict__ off) {
+  const int64_t e = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (e >= entries) return;
+  const int64_t b = e / per, j = e % per;
+  const int i = idx[e];
+  dst[e] = i >= 0 && i < rows ? static_cast<int>(b * rows + i) : -1;
+  off[e] = b * c * (per / div) + j / div;
+}
+// stack grouping: grad_out [M][C][nsample], entry e = (pt, s) -> feature row start(sample of pt) + idx[e] (dropped outside [0, n))
+__global__ void det_group_stack_entries_k(int B, int M, int C, int nsample, int n, const int* __restrict__ idx, const int* __restrict__ idx_cnt,
+                                          const int* __restrict__ feat_cnt, int* __restrict__ dst, int64_t* __restrict__ off) {
+  const int64_t e = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (e >= static_cast<int64_t>(M) * nsample) return;
+  const int pt = static_cast<int>(e / nsample), sm = static_cast<int>(e % nsample);
+  int bs, tmp;
+  stack_locate(pt, B, idx_cnt, &bs, &tmp);
+  const int64_t r = static_cast<int64_t>(stack_start(bs, feat_cnt)) + idx[e];
+  dst[e] = r >= 0 && r < n ? static_cast<int>(r) : -1;
+  off[e] = static_cast<int64_t>(pt) * C * nsample + sm;
+}
+
 static int fps_ref_block(int n) {  // opt_n_threads (cuda_utils.h:10-14): 2^floor(log2 n) clamped to [1, 1024]
   int p = 1;
   while (p * 2 <= n && p < 1024) p *= 2;
@@ -2011,4 +2036,69 @@ extern "C" int fv2p_three_interpolate_stack_grad_gather(int n, int c, int m, con
 #undef FV2P_IG
   FV2P_LAUNCH_CHECK();
   return 0;
+}
+
+// ---- deterministic forms (fv2p_scatter_add) of the batch / stack scatter gradients ----------------------------------------------------
+// batch layouts: entries into a [B * rows][C] staging buffer, then one transpose into grad_points [B][C][rows]
+static size_t det_batch_ws(int b, int c, int rows, int64_t per) {
+  const int64_t entries = static_cast<int64_t>(b > 0 ? b : 0) * (per > 0 ? per : 0);
+  return det_lists_bytes(entries, c > 0 ? c : 1, false, static_cast<size_t>(b > 0 ? b : 1) * (rows > 0 ? rows : 1) * (c > 0 ? c : 1));
+}
+static int det_batch_grad(const char* who, int b, int c, int rows, int64_t per, int div, const float* grad_out, const int* idx,
+                          const float* weight, float* grad_points, void* ws, size_t ws_bytes, hipStream_t st) {
+  FV2P_REQUIRE(b >= 0 && c >= 0 && rows >= 0 && per >= 0, FV2P_EINVAL, "%s: bad sizes", who);
+  const int64_t out_n = static_cast<int64_t>(b) * c * rows;
+  if (out_n == 0) return 0;
+  FV2P_REQUIRE(grad_points, FV2P_EINVAL, "%s: null pointer", who);
+  const int64_t entries = static_cast<int64_t>(b) * per;
+  if (entries == 0) { FV2P_HIP(hipMemsetAsync(grad_points, 0, static_cast<size_t>(out_n) * sizeof(float), st)); return 0; }
+  FV2P_REQUIRE(grad_out && idx && (div == 1 || weight), FV2P_EINVAL, "%s: null pointer", who);
+  FV2P_REQUIRE(entries < (1ll << 31) && static_cast<int64_t>(b) * rows < (1ll << 30), FV2P_ELIMIT, "%s: too many entries", who);
+  FV2P_REQUIRE(ws && ws_bytes >= det_batch_ws(b, c, rows, per), FV2P_EWORKSPACE, "%s: workspace too small", who);
+  const DetLists d = det_lists(ws, ws_bytes, entries, c, false, static_cast<size_t>(out_n));
+  FV2P_HIP(hipMemsetAsync(d.stage, 0, static_cast<size_t>(out_n) * sizeof(float), st));
+  hipLaunchKernelGGL(det_batch_entries_k, G1D(entries), 0, st, entries, per, div, c, rows, idx, d.dst, d.off);
+  if (int rc = fv2p_scatter_add(entries, c, static_cast<int64_t>(b) * rows, d.dst, d.off, weight, grad_out, per / div, d.stage, d.sws,
+                                d.sws_bytes, st)) return rc;
+  return fv2p_transpose_batched(d.stage, b, rows, c, grad_points, st);   // [B][rows][C] -> [B][C][rows]
+}
+extern "C" size_t fv2p_group_points_batch_grad_ws_bytes(int b, int c, int n, int npoints, int nsample) {
+  return det_batch_ws(b, c, n, static_cast<int64_t>(npoints) * nsample);
+}
+extern "C" int fv2p_group_points_batch_grad_gather(int b, int c, int n, int npoints, int nsample, const float* grad_out, const int* idx,
+                                                   float* grad_points, void* ws, size_t ws_bytes, fv2p_stream_t s) {
+  return det_batch_grad("group_points_batch_grad_gather", b, c, n, static_cast<int64_t>(npoints) * nsample, 1, grad_out, idx, nullptr,
+                        grad_points, ws, ws_bytes, STREAM(s));
+}
+extern "C" size_t fv2p_gather_points_grad_ws_bytes(int b, int c, int n, int npoints) { return det_batch_ws(b, c, n, npoints); }
+extern "C" int fv2p_gather_points_grad_gather(int b, int c, int n, int npoints, const float* grad_out, const int* idx, float* grad_points,
+                                              void* ws, size_t ws_bytes, fv2p_stream_t s) {
+  return det_batch_grad("gather_points_grad_gather", b, c, n, npoints, 1, grad_out, idx, nullptr, grad_points, ws, ws_bytes, STREAM(s));
+}
+// grad_out (B,C,n), idx / weight (B,n,3) -> grad_points (B,C,m): entry e = 3 * (b * n + query) + slot, coefficient weight[e]
+extern "C" size_t fv2p_three_interpolate_batch_grad_ws_bytes(int b, int c, int n, int m) { return det_batch_ws(b, c, m, static_cast<int64_t>(n) * 3); }
+extern "C" int fv2p_three_interpolate_batch_grad_gather(int b, int c, int n, int m, const float* grad_out, const int* idx, const float* weight,
+                                                        float* grad_points, void* ws, size_t ws_bytes, fv2p_stream_t s) {
+  return det_batch_grad("three_interpolate_batch_grad_gather", b, c, m, static_cast<int64_t>(n) * 3, 3, grad_out, idx, weight, grad_points,
+                        ws, ws_bytes, STREAM(s));
+}
+extern "C" size_t fv2p_group_points_stack_grad_ws_bytes(int m, int c, int nsample) {
+  return det_lists_bytes(static_cast<int64_t>(m > 0 ? m : 0) * (nsample > 0 ? nsample : 0), c > 0 ? c : 1, false, 0);
+}
+extern "C" int fv2p_group_points_stack_grad_gather(int b, int m, int c, int n, int nsample, const float* grad_out, const int* idx,
+                                                   const int* idx_batch_cnt, const int* features_batch_cnt, float* grad_features, void* ws,
+                                                   size_t ws_bytes, fv2p_stream_t s) {
+  hipStream_t st = STREAM(s);
+  FV2P_REQUIRE(m >= 0 && c >= 0 && n >= 0 && nsample >= 0, FV2P_EINVAL, "group_points_stack_grad_gather: bad sizes");
+  if (static_cast<int64_t>(n) * c == 0) return 0;
+  FV2P_REQUIRE(grad_features, FV2P_EINVAL, "group_points_stack_grad_gather: null pointer");
+  FV2P_HIP(hipMemsetAsync(grad_features, 0, static_cast<size_t>(n) * c * sizeof(float), st));
+  const int64_t entries = static_cast<int64_t>(m) * nsample;
+  if (entries == 0) return 0;
+  FV2P_REQUIRE(b >= 1 && grad_out && idx && idx_batch_cnt && features_batch_cnt, FV2P_EINVAL, "group_points_stack_grad_gather: bad arguments");
+  FV2P_REQUIRE(entries < (1ll << 31), FV2P_ELIMIT, "group_points_stack_grad_gather: too many entries");
+  FV2P_REQUIRE(ws && ws_bytes >= fv2p_group_points_stack_grad_ws_bytes(m, c, nsample), FV2P_EWORKSPACE, "group_points_stack_grad_gather: workspace too small");
+  const DetLists d = det_lists(ws, ws_bytes, entries, c, false, 0);
+  hipLaunchKernelGGL(det_group_stack_entries_k, G1D(entries), 0, st, b, m, c, nsample, n, idx, idx_batch_cnt, features_batch_cnt, d.dst, d.off);
+  return fv2p_scatter_add(entries, c, n, d.dst, d.off, nullptr, grad_out, nsample, grad_features, d.sws, d.sws_bytes, st);
 }

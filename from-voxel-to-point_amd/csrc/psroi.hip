@@ -155,6 +155,55 @@ __global__ __launch_bounds__(256) void psroi_bwd_k(PsGeom g, long long count, co
   }
 }
 
+// Entries of the deterministic backward (fv2p_scatter_add, one channel): bin `index` owns entries spp^2 * 4 * index + 4 * sample + corner
+// of grad_data (element offset, value = the atomic form's corner product) and entries 2 * index + {0, 1} of grad_trans (the bin's shift
+// gradient summed over its samples in order, as psroi_bwd_k does).  Skipped samples and dead bins leave dropped entries (row -1).
+__global__ __launch_bounds__(256) void psroi_entries_k(PsGeom g, long long count, const float* __restrict__ grad_out, const float* __restrict__ top_count,
+                                                       const float* __restrict__ data, const float* __restrict__ rois, const float* __restrict__ trans,
+                                                       int* __restrict__ ddst, float* __restrict__ dval, int* __restrict__ tdst, float* __restrict__ tval) {
+  const long long index = static_cast<long long>(blockIdx.x) * 256 + threadIdx.x;
+  if (index >= count) return;
+  const int per = g.spp * g.spp * 4;
+  int* dd = ddst + index * per;
+  float* dv = dval + index * per;
+  tdst[2 * index] = -1; tdst[2 * index + 1] = -1;
+  tval[2 * index] = 0.f; tval[2 * index + 1] = 0.f;
+  for (int q = 0; q < per; ++q) { dd[q] = -1; dv[q] = 0.f; }
+  const float cnt = top_count[index];
+  if (cnt <= 0.f) return;
+  const PsBin b = ps_bin(g, rois, trans, index);
+  if (!b.live) return;
+  const float diff = grad_out[index] / cnt;
+  const float* plane = data + b.plane;
+  float gx = 0.f, gy = 0.f;
+  for (int ih = 0; ih < g.spp; ++ih)
+    for (int iw = 0; iw < g.spp; ++iw) {
+      float w, h;
+      if (!ps_sample(g, b, ih, iw, w, h)) continue;
+      const int x0 = static_cast<int>(floorf(w)), x1 = static_cast<int>(ceilf(w));
+      const int y0 = static_cast<int>(floorf(h)), y1 = static_cast<int>(ceilf(h));
+      const float dx = w - static_cast<float>(x0), dy = h - static_cast<float>(y0);
+      const int q = 4 * (ih * g.spp + iw);
+      dd[q + 0] = static_cast<int>(b.plane + y0 * g.width + x0); dv[q + 0] = (1.f - dx) * (1.f - dy) * diff;
+      dd[q + 1] = static_cast<int>(b.plane + y1 * g.width + x0); dv[q + 1] = (1.f - dx) * dy * diff;
+      dd[q + 2] = static_cast<int>(b.plane + y0 * g.width + x1); dv[q + 2] = dx * (1.f - dy) * diff;
+      dd[q + 3] = static_cast<int>(b.plane + y1 * g.width + x1); dv[q + 3] = dx * dy * diff;
+      if (g.no_trans) continue;
+      const float u00 = plane[y0 * g.width + x0], u01 = plane[y1 * g.width + x0];
+      const float u10 = plane[y0 * g.width + x1], u11 = plane[y1 * g.width + x1];
+      float sx = (u11 * dy + u10 * (1.f - dy) - u01 * dy - u00 * (1.f - dy)) * g.trans_std * diff;
+      sx *= b.roi_w;
+      float sy = (u11 * dx + u01 * (1.f - dx) - u10 * dx - u00 * (1.f - dx)) * g.trans_std * diff;
+      sy *= b.roi_h;
+      gx += sx;
+      gy += sy;
+    }
+  if (!g.no_trans) {
+    tdst[2 * index] = static_cast<int>(b.trans_x); tval[2 * index] = gx;
+    tdst[2 * index + 1] = static_cast<int>(b.trans_y); tval[2 * index + 1] = gy;
+  }
+}
+
 static int ps_check(const PsGeom& g, const char* who) {
   FV2P_REQUIRE(g.batch >= 0 && g.channels > 0 && g.height > 0 && g.width > 0 && g.rois >= 0, FV2P_EINVAL, "%s: bad map / RoI sizes", who);
   FV2P_REQUIRE(g.out_dim > 0 && g.group > 0 && g.pooled > 0 && g.part > 0 && g.spp > 0, FV2P_EINVAL, "%s: output_dim, group_size, pooled_size, part_size and sample_per_part must be positive", who);
@@ -202,6 +251,53 @@ extern "C" int fv2p_deform_psroi_pool_backward(const float* grad_out, const floa
                "deform_psroi_pool_backward: null pointer");
   hipLaunchKernelGGL(psroi_bwd_k, dim3(static_cast<unsigned>(ceil_div(count, 256))), dim3(256), 0, stream, g, count, grad_out, top_count, data, rois,
                      trans, grad_data, grad_trans);
+  FV2P_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" size_t fv2p_deform_psroi_pool_backward_ws_bytes(int num_rois, int output_dim, int pooled_size, int sample_per_part) {
+  const size_t bins = static_cast<size_t>(num_rois > 0 ? num_rois : 1) * (output_dim > 0 ? output_dim : 1) * (pooled_size > 0 ? pooled_size : 1) *
+                      (pooled_size > 0 ? pooled_size : 1);
+  const size_t e1 = bins * (sample_per_part > 0 ? sample_per_part : 1) * (sample_per_part > 0 ? sample_per_part : 1) * 4, e2 = bins * 2;
+  Sizer sz;
+  sz.take<int>(e1); sz.take<float>(e1); sz.take<int>(e2); sz.take<float>(e2);
+  sz.take<char>(fv2p_scatter_add_ws_bytes(static_cast<int64_t>(e1), 1));
+  return sz.bytes();
+}
+extern "C" int fv2p_deform_psroi_pool_backward_gather(const float* grad_out, const float* data, const float* rois, const float* trans,
+                                                      const float* top_count, PS_GEOM_ARGS, float* grad_data, float* grad_trans,
+                                                      void* ws, size_t ws_bytes, fv2p_stream_t stream_) {
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  PS_GEOM_INIT;
+  if (int rc = ps_check(g, "deform_psroi_pool_backward_gather")) return rc;
+  const long long count = static_cast<long long>(g.rois) * g.out_dim * g.pooled * g.pooled;
+  const int64_t map = static_cast<int64_t>(g.batch) * g.channels * g.height * g.width;
+  const int64_t tn = static_cast<int64_t>(g.rois) * g.classes * 2 * g.part * g.part;
+  FV2P_REQUIRE(map == 0 || grad_data, FV2P_EINVAL, "deform_psroi_pool_backward_gather: null pointer");
+  FV2P_REQUIRE(map < (1ll << 31) - 1, FV2P_ELIMIT, "deform_psroi_pool_backward_gather: map too large");
+  if (map) FV2P_HIP(hipMemsetAsync(grad_data, 0, static_cast<size_t>(map) * sizeof(float), stream));
+  if (!g.no_trans && tn) {
+    FV2P_REQUIRE(grad_trans, FV2P_EINVAL, "deform_psroi_pool_backward_gather: null pointer");
+    FV2P_HIP(hipMemsetAsync(grad_trans, 0, static_cast<size_t>(tn) * sizeof(float), stream));
+  }
+  if (count == 0 || map == 0) return 0;
+  FV2P_REQUIRE(grad_out && data && rois && top_count && (g.no_trans || trans), FV2P_EINVAL, "deform_psroi_pool_backward_gather: null pointer");
+  const int64_t e1 = count * g.spp * g.spp * 4, e2 = count * 2;
+  FV2P_REQUIRE(e1 < (1ll << 31) && tn < (1ll << 31) - 1, FV2P_ELIMIT, "deform_psroi_pool_backward_gather: too many samples");
+  FV2P_REQUIRE(ws && ws_bytes >= fv2p_deform_psroi_pool_backward_ws_bytes(num_rois, output_dim, pooled_size, sample_per_part), FV2P_EWORKSPACE,
+               "deform_psroi_pool_backward_gather: workspace too small");
+  Carver cv(ws, ws_bytes);
+  int* ddst = cv.take<int>(static_cast<size_t>(e1));
+  float* dval = cv.take<float>(static_cast<size_t>(e1));
+  int* tdst = cv.take<int>(static_cast<size_t>(e2));
+  float* tval = cv.take<float>(static_cast<size_t>(e2));
+  const size_t sb = fv2p_scatter_add_ws_bytes(e1, 1);
+  void* sws = cv.take<char>(sb);
+  hipLaunchKernelGGL(psroi_entries_k, dim3(static_cast<unsigned>(ceil_div(count, 256))), dim3(256), 0, stream, g, count, grad_out, top_count, data,
+                     rois, trans, ddst, dval, tdst, tval);
+  if (int rc = fv2p_scatter_add(e1, 1, map, ddst, nullptr, nullptr, dval, 1, grad_data, sws, sb, stream)) return rc;
+  if (!g.no_trans)   // the second list is shorter: the same scatter workspace is large enough, and the stream orders the two uses
+    if (int rc = fv2p_scatter_add(e2, 1, tn, tdst, nullptr, nullptr, tval, 1, grad_trans, sws, sb, stream)) return rc;
   FV2P_LAUNCH_CHECK();
   return 0;
 }

@@ -224,6 +224,31 @@ __global__ void roiaware_pool_bwd_k(int64_t total, int channels, int max_pts, co
   }
 }
 
+// Entries of the deterministic backward (fv2p_scatter_add).  max: one scalar entry per (voxel, channel) t, element argmax * C + c of
+// grad_in (dropped where argmax is -1), source grad_out[t].  avg: one row entry per (voxel, member slot k < max_pts - 1), row
+// list[k + 1] (dropped past the voxel's count), coefficient 1 / max(count, 1), source the voxel's row of grad_out.
+__global__ void roiaware_max_entries_k(int64_t total, int channels, int64_t n_dst, const int* __restrict__ argmax, int* __restrict__ dst,
+                                       int64_t* __restrict__ off) {
+  const int64_t t = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (t >= total) return;
+  const int am = argmax[t];
+  const int64_t el = static_cast<int64_t>(am) * channels + t % channels;
+  dst[t] = am >= 0 && el < n_dst ? static_cast<int>(el) : -1;
+  off[t] = t;
+}
+__global__ void roiaware_avg_entries_k(int64_t entries, int channels, int max_pts, const int* __restrict__ pts_idx_of_voxels, int* __restrict__ dst,
+                                       int64_t* __restrict__ off, float* __restrict__ coef) {
+  const int64_t e = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (e >= entries) return;
+  const int64_t voxel = e / (max_pts - 1);
+  const int k = static_cast<int>(e % (max_pts - 1));
+  const int* list = pts_idx_of_voxels + voxel * max_pts;
+  const int n = list[0];
+  dst[e] = k < n ? list[k + 1] : -1;
+  off[e] = voxel * channels;
+  coef[e] = 1.0f / fmaxf(static_cast<float>(n), 1.0f);
+}
+
 }  // namespace fv2p
 using namespace fv2p;
 
@@ -313,4 +338,40 @@ extern "C" int fv2p_roiaware_pool3d_bwd(const int* pts_idx_of_voxels, const int*
     hipLaunchKernelGGL(roiaware_pool_bwd_k<1>, grid, block, 0, stream, total, channels, max_pts_each_voxel, pts_idx_of_voxels, argmax, grad_out, grad_in);
   FV2P_LAUNCH_CHECK();
   return 0;
+}
+
+static int64_t roiaware_entries(int boxes_num, int out_x, int out_y, int out_z, int channels, int max_pts, int pool_method) {
+  const int64_t voxels = static_cast<int64_t>(boxes_num > 0 ? boxes_num : 0) * out_x * out_y * out_z;
+  return pool_method == 0 ? voxels * channels : voxels * (max_pts > 1 ? max_pts - 1 : 0);
+}
+extern "C" size_t fv2p_roiaware_pool3d_bwd_ws_bytes(int boxes_num, int out_x, int out_y, int out_z, int channels, int max_pts_each_voxel,
+                                                    int pool_method) {
+  return det_lists_bytes(roiaware_entries(boxes_num, out_x, out_y, out_z, channels, max_pts_each_voxel, pool_method),
+                         pool_method == 0 ? 1 : (channels > 0 ? channels : 1), pool_method != 0, 0);
+}
+extern "C" int fv2p_roiaware_pool3d_bwd_gather(const int* pts_idx_of_voxels, const int* argmax, const float* grad_out, int boxes_num, int out_x,
+                                               int out_y, int out_z, int channels, int max_pts_each_voxel, int pool_method, int pts_num,
+                                               float* grad_in, void* ws, size_t ws_bytes, fv2p_stream_t stream_) {
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  FV2P_REQUIRE(boxes_num >= 0 && channels >= 1 && pts_num >= 0 && out_x >= 0 && out_y >= 0 && out_z >= 0 && max_pts_each_voxel >= 1 &&
+               (pool_method == 0 || pool_method == 1), FV2P_EINVAL, "roiaware_pool3d_bwd_gather: bad arguments");
+  const int64_t n_dst = static_cast<int64_t>(pts_num) * channels;
+  if (n_dst == 0) return 0;
+  FV2P_REQUIRE(grad_in, FV2P_EINVAL, "roiaware_pool3d_bwd_gather: null pointer");
+  FV2P_HIP(hipMemsetAsync(grad_in, 0, static_cast<size_t>(n_dst) * sizeof(float), stream));
+  const int64_t entries = roiaware_entries(boxes_num, out_x, out_y, out_z, channels, max_pts_each_voxel, pool_method);
+  if (entries == 0) return 0;
+  FV2P_REQUIRE(pts_idx_of_voxels && argmax && grad_out, FV2P_EINVAL, "roiaware_pool3d_bwd_gather: null pointer");
+  FV2P_REQUIRE(entries < (1ll << 31) && n_dst < (1ll << 31) - 1, FV2P_ELIMIT, "roiaware_pool3d_bwd_gather: too many entries");
+  FV2P_REQUIRE(ws && ws_bytes >= fv2p_roiaware_pool3d_bwd_ws_bytes(boxes_num, out_x, out_y, out_z, channels, max_pts_each_voxel, pool_method),
+               FV2P_EWORKSPACE, "roiaware_pool3d_bwd_gather: workspace too small");
+  const dim3 grid(static_cast<unsigned>(ceil_div(entries, 256))), block(256);
+  if (pool_method == 0) {
+    const DetLists d = det_lists(ws, ws_bytes, entries, 1, false, 0);
+    hipLaunchKernelGGL(roiaware_max_entries_k, grid, block, 0, stream, entries, channels, n_dst, argmax, d.dst, d.off);
+    return fv2p_scatter_add(entries, 1, n_dst, d.dst, d.off, nullptr, grad_out, 1, grad_in, d.sws, d.sws_bytes, stream);
+  }
+  const DetLists d = det_lists(ws, ws_bytes, entries, channels, true, 0);
+  hipLaunchKernelGGL(roiaware_avg_entries_k, grid, block, 0, stream, entries, channels, max_pts_each_voxel, pts_idx_of_voxels, d.dst, d.off, d.coef);
+  return fv2p_scatter_add(entries, channels, pts_num, d.dst, d.off, d.coef, grad_out, 1, grad_in, d.sws, d.sws_bytes, stream);
 }

@@ -333,11 +333,13 @@ constexpr int kSaDp = 33;   // row stride of the dP tile (floats): odd, so the s
                             // with 32 every row starts on bank 0 or 32 and a wave's 64 adds fall on 8 banks
 // kSaBwdWaves = 8 where the dP tile leaves room for eight waves' transpose tiles (n <= 589), two per SIMD: one wave's gathers, LDS
 // atomics and transposes run beside the other's MFMAs (one workgroup per CU either way: the dP tile); 4 above that.
-template <int TILES, int kSaBwdWaves>   // TILES = samples per centre / 16: register arrays below are indexed by compile-time tile numbers only
+// DET (fv2p_sa_grid_bwd_gather): instead of the LDS atomics into the dP tile, every (centre, sample) row of dh1 is stored to
+// dh1_rows[(r * m + i) * s + sample][64] (zeros included) and summed per point afterwards in the fixed order of fv2p_scatter_add.
+template <int TILES, int kSaBwdWaves, bool DET>   // TILES = samples per centre / 16: register arrays below are indexed by compile-time tile numbers only
 __global__ __launch_bounds__(kSaBwdWaves * 64) void sa_grid_bwd_k(int n, int m, const float* __restrict__ P, const float* __restrict__ Q,
                                                      const int* __restrict__ idx, const float* __restrict__ W2, const unsigned char* __restrict__ arg,
                                                      const float* __restrict__ dout, float* __restrict__ dP, float* __restrict__ dQ,
-                                                     float* __restrict__ dW2_partial) {
+                                                     float* __restrict__ dW2_partial, float* __restrict__ dh1_rows) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   float* wtfrag = lds;                         // W2^T    as A operand (dh1^T = W2^T dh2^T), this half's two row blocks only: 8 KB
   float* tile = wtfrag + 8 * 64 * 4;           // per wave: two 16 x 72 transpose tiles (dh2, h1)
@@ -350,7 +352,8 @@ __global__ __launch_bounds__(kSaBwdWaves * 64) void sa_grid_bwd_k(int n, int m, 
     const int rw = 32 * static_cast<int>(blockIdx.x) + 16 * bb + (l & 15), col = 16 * j + 4 * (l >> 4);
     *reinterpret_cast<float4*>(wtfrag + e * 4) = make_float4(W2[(col + 0) * kSaC + rw], W2[(col + 1) * kSaC + rw], W2[(col + 2) * kSaC + rw], W2[(col + 3) * kSaC + rw]);
   }
-  for (int e = threadIdx.x; e < n * kSaDp; e += kSaBwdWaves * 64) dpt[e] = 0.f;
+  if constexpr (!DET)
+    for (int e = threadIdx.x; e < n * kSaDp; e += kSaBwdWaves * 64) dpt[e] = 0.f;
   __syncthreads();
   float* t_dh2 = tile + wave * 2 * 16 * kSaTs;
   float* t_h1 = t_dh2 + 16 * kSaTs;
@@ -455,7 +458,8 @@ __global__ __launch_bounds__(kSaBwdWaves * 64) void sa_grid_bwd_k(int n, int m, 
         for (int e = 0; e < 4; ++e) {
           const float v = hv[e] > 0.f ? d1[bb][e] : 0.f;
           dq[bb][e] += v;
-          if (v != 0.f) atomicAdd(&dpt[src[t] * kSaDp + 16 * bb + 4 * g + e], v);
+          if constexpr (DET) dh1_rows[((static_cast<long long>(r) * m + i) * s + 16 * t + row) * kSaC + 32 * half + 16 * bb + 4 * g + e] = v;
+          else if (v != 0.f) atomicAdd(&dpt[src[t] * kSaDp + 16 * bb + 4 * g + e], v);
         }
       }
       // dW2[c'][c] += sum_rows dh2[row][c'] h1[row][c]: rows become the K dimension -> transpose both tiles through LDS
@@ -497,7 +501,7 @@ __global__ __launch_bounds__(kSaBwdWaves * 64) void sa_grid_bwd_k(int n, int m, 
   __syncthreads();
   // flush dP (each (RoI, half) tile is owned by this workgroup: plain stores)
   float* dpo = dP + static_cast<long long>(r) * n * kSaC + 32 * half;
-  for (int e = threadIdx.x; e < n * 8; e += kSaBwdWaves * 64) {
+  for (int e = threadIdx.x; e < (DET ? 0 : n * 8); e += kSaBwdWaves * 64) {
     const int pt = e >> 3, c4 = (e & 7) * 4;
     const float* t4 = dpt + pt * kSaDp + c4;
     *reinterpret_cast<float4*>(dpo + static_cast<long long>(pt) * kSaC + c4) = make_float4(t4[0], t4[1], t4[2], t4[3]);
@@ -568,33 +572,83 @@ extern "C" size_t fv2p_sa_grid_bwd_ws_bytes(int rois) {
   return sz.bytes();
 }
 
-extern "C" int fv2p_sa_grid_bwd(const float* per_point, const float* per_centre, const int* idx, const float* w2, const unsigned char* arg,
-                                const float* grad_out, int rois, int n, int m, int s, int c, float* grad_point, float* grad_centre,
-                                float* grad_w2, void* ws, size_t ws_bytes, fv2p_stream_t stream_) {
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
-  FV2P_REQUIRE(sa_shapes_ok(rois, n, m, s, c) && fv2p_sa_grid_supported(n, m, s, c), FV2P_EINVAL, "sa_grid_bwd: unsupported shape");
-  FV2P_REQUIRE(per_point && per_centre && idx && w2 && arg && grad_out && grad_point && grad_centre && grad_w2, FV2P_EINVAL, "sa_grid_bwd: null pointer");
-  FV2P_REQUIRE(ws && ws_bytes >= fv2p_sa_grid_bwd_ws_bytes(rois), FV2P_EWORKSPACE, "sa_grid_bwd: workspace too small");
-  Carver cv(ws, ws_bytes);
-  float* partial = cv.take<float>(static_cast<size_t>(rois) * kSaC * kSaC);
+// dh1_rows == nullptr: the LDS-atomic kernel (fv2p_sa_grid_bwd); otherwise the DET one, which leaves grad_point to the caller
+template <bool DET>
+static int sa_grid_bwd_launch(const float* per_point, const float* per_centre, const int* idx, const float* w2, const unsigned char* arg,
+                              const float* grad_out, int rois, int n, int m, int s, float* grad_point, float* grad_centre, float* grad_w2,
+                              float* partial, float* dh1_rows, hipStream_t stream) {
   auto lds_of = [&](int waves) { return (8 * 64 * 4 + static_cast<size_t>(waves) * 2 * 16 * kSaTs + static_cast<size_t>(n) * kSaDp) * sizeof(float); };
   const int waves = lds_of(8) <= 160 * 1024 ? 8 : 4;
   const size_t lds = lds_of(waves);
   static bool roomy[4] = {false, false, false, false};   // per kernel instance: the dynamic-LDS limit is raised once
-  bool& raised = roomy[(s == 32 ? 2 : 0) + (waves == 8 ? 1 : 0)];
+  bool& raised = roomy[(s == 32 ? 2 : 0) + (waves == 8 ? 1 : 0)];   // (one table per DET instance of this function)
   auto launch = [&](auto kernel) -> int {
     if (lds > 48 * 1024 && !raised) {
       FV2P_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
       raised = true;
     }
-    hipLaunchKernelGGL(kernel, dim3(2, rois), dim3(waves * 64), lds, stream, n, m, per_point, per_centre, idx, w2, arg, grad_out, grad_point, grad_centre, partial);
+    hipLaunchKernelGGL(kernel, dim3(2, rois), dim3(waves * 64), lds, stream, n, m, per_point, per_centre, idx, w2, arg, grad_out, grad_point, grad_centre, partial,
+                       dh1_rows);
     return 0;
   };
   int rc;
-  if (s == 16) rc = waves == 8 ? launch(&sa_grid_bwd_k<1, 8>) : launch(&sa_grid_bwd_k<1, 4>);
-  else rc = waves == 8 ? launch(&sa_grid_bwd_k<2, 8>) : launch(&sa_grid_bwd_k<2, 4>);
+  if (s == 16) rc = waves == 8 ? launch(&sa_grid_bwd_k<1, 8, DET>) : launch(&sa_grid_bwd_k<1, 4, DET>);
+  else rc = waves == 8 ? launch(&sa_grid_bwd_k<2, 8, DET>) : launch(&sa_grid_bwd_k<2, 4, DET>);
   if (rc) return rc;
   hipLaunchKernelGGL(sa_grid_dw_reduce_k, dim3(kSaC * kSaC / 16), dim3(256), 0, stream, rois, partial, grad_w2);
   FV2P_LAUNCH_CHECK();
   return 0;
+}
+
+extern "C" int fv2p_sa_grid_bwd(const float* per_point, const float* per_centre, const int* idx, const float* w2, const unsigned char* arg,
+                                const float* grad_out, int rois, int n, int m, int s, int c, float* grad_point, float* grad_centre,
+                                float* grad_w2, void* ws, size_t ws_bytes, fv2p_stream_t stream_) {
+  FV2P_REQUIRE(sa_shapes_ok(rois, n, m, s, c) && fv2p_sa_grid_supported(n, m, s, c), FV2P_EINVAL, "sa_grid_bwd: unsupported shape");
+  FV2P_REQUIRE(per_point && per_centre && idx && w2 && arg && grad_out && grad_point && grad_centre && grad_w2, FV2P_EINVAL, "sa_grid_bwd: null pointer");
+  FV2P_REQUIRE(ws && ws_bytes >= fv2p_sa_grid_bwd_ws_bytes(rois), FV2P_EWORKSPACE, "sa_grid_bwd: workspace too small");
+  Carver cv(ws, ws_bytes);
+  float* partial = cv.take<float>(static_cast<size_t>(rois) * kSaC * kSaC);
+  return sa_grid_bwd_launch<false>(per_point, per_centre, idx, w2, arg, grad_out, rois, n, m, s, grad_point, grad_centre, grad_w2, partial, nullptr,
+                                   static_cast<hipStream_t>(stream_));
+}
+
+// entry e = (r * m + i) * s + sample of the dh1 rows -> row r * n + idx[e] of grad_point (dropped outside [0, n))
+__global__ void sa_grid_entries_k(int64_t entries, int n, int64_t per_roi, const int* __restrict__ idx, int* __restrict__ dst) {
+  const int64_t e = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (e >= entries) return;
+  const int i = idx[e];
+  dst[e] = i >= 0 && i < n ? static_cast<int>((e / per_roi) * n + i) : -1;
+}
+
+extern "C" size_t fv2p_sa_grid_bwd_gather_ws_bytes(int rois, int m, int s) {
+  const int64_t entries = static_cast<int64_t>(rois > 0 ? rois : 1) * (m > 0 ? m : 1) * (s > 0 ? s : 1);
+  Sizer sz;
+  sz.take<char>(fv2p_sa_grid_bwd_ws_bytes(rois));
+  sz.take<int>(static_cast<size_t>(entries));
+  sz.take<float>(static_cast<size_t>(entries) * kSaC);
+  sz.take<char>(fv2p_scatter_add_ws_bytes(entries, kSaC));
+  return sz.bytes();
+}
+
+extern "C" int fv2p_sa_grid_bwd_gather(const float* per_point, const float* per_centre, const int* idx, const float* w2, const unsigned char* arg,
+                                       const float* grad_out, int rois, int n, int m, int s, int c, float* grad_point, float* grad_centre,
+                                       float* grad_w2, void* ws, size_t ws_bytes, fv2p_stream_t stream_) {
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  FV2P_REQUIRE(sa_shapes_ok(rois, n, m, s, c) && fv2p_sa_grid_supported(n, m, s, c), FV2P_EINVAL, "sa_grid_bwd_gather: unsupported shape");
+  FV2P_REQUIRE(per_point && per_centre && idx && w2 && arg && grad_out && grad_point && grad_centre && grad_w2, FV2P_EINVAL, "sa_grid_bwd_gather: null pointer");
+  const int64_t entries = static_cast<int64_t>(rois) * m * s;
+  FV2P_REQUIRE(entries < (1ll << 31) && static_cast<int64_t>(rois) * n < (1ll << 31) - 1, FV2P_ELIMIT, "sa_grid_bwd_gather: too many samples");
+  FV2P_REQUIRE(ws && ws_bytes >= fv2p_sa_grid_bwd_gather_ws_bytes(rois, m, s), FV2P_EWORKSPACE, "sa_grid_bwd_gather: workspace too small");
+  Carver cv(ws, ws_bytes);
+  float* partial = reinterpret_cast<float*>(cv.take<char>(fv2p_sa_grid_bwd_ws_bytes(rois)));
+  int* dst = cv.take<int>(static_cast<size_t>(entries));
+  float* rows = cv.take<float>(static_cast<size_t>(entries) * kSaC);
+  const size_t sb = fv2p_scatter_add_ws_bytes(entries, kSaC);
+  void* sws = cv.take<char>(sb);
+  if (int rc = sa_grid_bwd_launch<true>(per_point, per_centre, idx, w2, arg, grad_out, rois, n, m, s, grad_point, grad_centre, grad_w2, partial, rows,
+                                        stream)) return rc;
+  hipLaunchKernelGGL(sa_grid_entries_k, dim3(static_cast<unsigned>(ceil_div(entries, 256))), dim3(256), 0, stream, entries, n,
+                     static_cast<int64_t>(m) * s, idx, dst);
+  FV2P_HIP(hipMemsetAsync(grad_point, 0, static_cast<size_t>(rois) * n * kSaC * sizeof(float), stream));
+  return fv2p_scatter_add(entries, kSaC, static_cast<int64_t>(rois) * n, dst, nullptr, nullptr, rows, 1, grad_point, sws, sb, stream);
 }

@@ -1,0 +1,208 @@
+// Deterministic scatter-add — the library primitive behind the deterministic backward passes.
+//
+// out[dst_row[e], :] += coef[e] * src[src_off[e] + ch * src_cs]  over the entries e, with the ASSOCIATION of every row's sum fixed by the
+// entry list alone.  It is the machinery of the stack interpolation gradient (pointnet2.hip: interp_keys_k / interp_seg_k / interp_fix_k,
+// DESIGN §3.6a) with the source rows, coefficients and destination rows given by the caller:
+//   1. keys (dst_row << 32 | e), radix-sorted on the row bits (stable): each row's entries become one run in ascending e; entries whose
+//      row is outside [0, n_dst) sort behind every row and are dropped;
+//   2. the sorted sequence is cut into segments of kScatterSeg entries; a segment's piece of a run is summed from zero in sorted order,
+//      acc = acc + coef * value (two roundings, no contraction: the file is built with -ffp-contract=off);
+//   3. a run inside one segment: out = out + acc.  A run over several segments: the piece of the segment it starts in, then the pieces
+//      of the following segments added one by one in segment order, and out = out + that total.
+// Nothing depends on the launch, the stream, timing or other work on the device.  tests/test_scatter_add_gpu.py restates the order on
+// the host and compares bit for bit.
+#include "common.hpp"
+
+namespace fv2p {
+
+constexpr int kScatterSeg = 32;
+
+__global__ void scatter_keys_k(int64_t entries, int64_t n_dst, const int* __restrict__ dst_row, uint64_t* __restrict__ keys) {
+  const int64_t e = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (e >= entries) return;
+  const int r = dst_row[e];
+  keys[e] = (static_cast<uint64_t>(r >= 0 && r < n_dst ? r : n_dst) << 32) | static_cast<uint64_t>(e);
+}
+
+struct SVec4 { float v[4]; };
+// vec: 16-byte access allowed for this address (the caller checked the base pointers, the channel count and the offset)
+__device__ __forceinline__ SVec4 sc_load4(const float* p, int64_t cs, bool vec, int c0, int c) {
+  SVec4 r;
+  if (vec) { const float4 q = *reinterpret_cast<const float4*>(p); r.v[0] = q.x; r.v[1] = q.y; r.v[2] = q.z; r.v[3] = q.w; }
+  else {
+#pragma unroll
+    for (int u = 0; u < 4; ++u) r.v[u] = c0 + u < c ? p[u * cs] : 0.f;
+  }
+  return r;
+}
+__device__ __forceinline__ void sc_add_store4(float* p, const SVec4& a, bool vec, int c0, int c) {   // p[u] = p[u] + a[u]
+  if (vec) {
+    float4 q = *reinterpret_cast<float4*>(p);
+    q.x = q.x + a.v[0]; q.y = q.y + a.v[1]; q.z = q.z + a.v[2]; q.w = q.w + a.v[3];
+    *reinterpret_cast<float4*>(p) = q;
+  } else {
+#pragma unroll
+    for (int u = 0; u < 4; ++u) if (c0 + u < c) p[u] = p[u] + a.v[u];
+  }
+}
+__device__ __forceinline__ void sc_store4(float* p, const SVec4& a, bool vec, int c0, int c) {
+  if (vec) *reinterpret_cast<float4*>(p) = make_float4(a.v[0], a.v[1], a.v[2], a.v[3]);
+  else {
+#pragma unroll
+    for (int u = 0; u < 4; ++u) if (c0 + u < c) p[u] = a.v[u];
+  }
+}
+
+// Segment flags as in interp_seg_k: bit 0 the segment's first run continues from the segment before (piece in part[s][0]); bit 1 that
+// run goes on into the next segment; bit 2 the segment's last run starts here and goes on (piece in part[s][1]).
+// TPR lanes per segment (power of two, <= 64), each lane four channels per pass.  vec: src_cs == 1, c % 4 == 0 and src / out / part
+// 16-byte aligned; an entry whose source offset is not a multiple of four then still takes scalar loads.
+template <int TPR>
+__global__ __launch_bounds__(256) void scatter_seg_k(int64_t n_dst, int c, int64_t entries, const uint64_t* __restrict__ keys,
+                                                     const int64_t* __restrict__ src_off, const float* __restrict__ coef,
+                                                     const float* __restrict__ src, int64_t src_cs, float* __restrict__ out,
+                                                     float* __restrict__ part, int* __restrict__ flags, int vec_ok) {
+  const int64_t t = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
+  const int64_t s = t / TPR;
+  const int sub = static_cast<int>(t % TPR);
+  const int64_t i0 = s * kScatterSeg;
+  if (i0 >= entries) return;
+  const int64_t i1 = i0 + kScatterSeg < entries ? i0 + kScatterSeg : entries;
+  const uint32_t prev = i0 > 0 ? static_cast<uint32_t>(keys[i0 - 1] >> 32) : 0xffffffffu;   // rows are < 2^31: never equal to these two
+  const uint32_t next = i1 < entries ? static_cast<uint32_t>(keys[i1] >> 32) : 0xfffffffeu;
+  const uint64_t um = static_cast<uint64_t>(n_dst);
+  int fl = 0;
+  for (int c0 = 4 * sub; c0 < c; c0 += 4 * TPR) {
+    const bool vec = vec_ok && c0 + 3 < c;
+    SVec4 acc = {{0.f, 0.f, 0.f, 0.f}};
+    uint32_t cur = static_cast<uint32_t>(keys[i0] >> 32);
+    bool at_start = true;
+    auto flush = [&](bool at_end) {
+      if (cur >= um) return;   // dropped entries
+      const bool from_prev = at_start && cur == prev, to_next = at_end && cur == next;
+      if (!from_prev && !to_next) sc_add_store4(out + static_cast<int64_t>(cur) * c + c0, acc, vec, c0, c);
+      else if (from_prev) { sc_store4(part + (s * 2 + 0) * c + c0, acc, vec, c0, c); fl |= to_next ? 3 : 1; }
+      else { sc_store4(part + (s * 2 + 1) * c + c0, acc, vec, c0, c); fl |= 4; }
+    };
+    for (int64_t i = i0; i < i1; i += 4) {
+      uint64_t k[4];
+      bool in[4], ok[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        in[u] = i + u < i1;
+        k[u] = in[u] ? keys[i + u] : ~0ull;
+        ok[u] = in[u] && (k[u] >> 32) < um;
+      }
+      SVec4 v[4];
+      float w[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const uint32_t e = static_cast<uint32_t>(k[u]);
+        w[u] = ok[u] ? (coef ? coef[e] : 1.f) : 0.f;
+        const int64_t off = ok[u] ? (src_off ? src_off[e] : static_cast<int64_t>(e) * c) : 0;
+        v[u] = ok[u] ? sc_load4(src + off + c0 * src_cs, src_cs, vec && (off & 3) == 0, c0, c) : SVec4{{0.f, 0.f, 0.f, 0.f}};
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+        if (in[u]) {   // ascending e inside a run: the order is part of the result
+          const uint32_t row = static_cast<uint32_t>(k[u] >> 32);
+          if (row != cur) {
+            flush(false);
+            cur = row; at_start = false;
+            acc = SVec4{{0.f, 0.f, 0.f, 0.f}};
+          }
+          if (ok[u]) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) acc.v[q] = acc.v[q] + w[u] * v[u].v[q];
+          }
+        }
+    }
+    flush(true);
+  }
+  if (sub == 0) flags[s] = fl;
+}
+
+// the runs that cross segment borders: the group of the segment a run starts in adds the following segments' pieces in segment order
+template <int TPR>
+__global__ __launch_bounds__(256) void scatter_fix_k(int c, int64_t entries, int64_t segments, const uint64_t* __restrict__ keys,
+                                                     const float* __restrict__ part, const int* __restrict__ flags, float* __restrict__ out,
+                                                     int vec_ok) {
+  const int64_t t = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
+  const int64_t s = t / TPR;
+  const int sub = static_cast<int>(t % TPR);
+  if (s >= segments || !(flags[s] & 4)) return;
+  const int64_t i1 = (s + 1) * kScatterSeg < entries ? (s + 1) * kScatterSeg : entries;
+  const int64_t row = static_cast<int64_t>(keys[i1 - 1] >> 32);
+  int64_t len = 0;   // the run goes on through segments s + 1 .. s + len
+  for (bool open = true; open;) {
+    int f[16];
+#pragma unroll
+    for (int u = 0; u < 16; ++u) { const int64_t q = s + 1 + len + u; f[u] = q < segments ? flags[q] : 0; }
+#pragma unroll
+    for (int u = 0; u < 16; ++u)
+      if (open) { ++len; open = (f[u] & 2) != 0; }
+  }
+  if (s + len >= segments) len = segments - 1 - s;   // (cannot happen on a consistent flag array)
+  for (int c0 = 4 * sub; c0 < c; c0 += 4 * TPR) {
+    const bool vec = vec_ok && c0 + 3 < c;
+    SVec4 acc = sc_load4(part + (s * 2 + 1) * c + c0, 1, vec, c0, c);
+    for (int64_t j = 1; j <= len; ++j) {
+      const SVec4 p = sc_load4(part + ((s + j) * 2 + 0) * c + c0, 1, vec, c0, c);
+#pragma unroll
+      for (int q = 0; q < 4; ++q) acc.v[q] = acc.v[q] + p.v[q];
+    }
+    sc_add_store4(out + row * c + c0, acc, vec, c0, c);
+  }
+}
+
+}  // namespace fv2p
+using namespace fv2p;
+
+extern "C" size_t fv2p_scatter_add_ws_bytes(int64_t entries, int c) {
+  const size_t e = static_cast<size_t>(entries > 0 ? entries : 1);
+  const size_t segments = (e + kScatterSeg - 1) / kScatterSeg;
+  Sizer sz;
+  sz.take<uint64_t>(e);
+  sz.take<uint64_t>(e);
+  sz.take<char>(radix_sort_ws_bytes(static_cast<int64_t>(e)));
+  sz.take<float>(segments * 2 * static_cast<size_t>(c > 0 ? c : 1));
+  sz.take<int>(segments);
+  return sz.bytes();
+}
+
+extern "C" int fv2p_scatter_add(int64_t entries, int c, int64_t n_dst, const int* dst_row, const int64_t* src_off, const float* coef,
+                                const float* src, int64_t src_cs, float* out, void* ws, size_t ws_bytes, fv2p_stream_t stream) {
+  FV2P_REQUIRE(entries >= 0 && c >= 0 && n_dst >= 0 && src_cs >= 1, FV2P_EINVAL, "scatter_add: bad sizes");
+  if (entries == 0 || c == 0 || n_dst == 0) return 0;
+  FV2P_REQUIRE(dst_row && src && out, FV2P_EINVAL, "scatter_add: null pointer");
+  FV2P_REQUIRE(entries < (1ll << 31) && n_dst < (1ll << 31) - 1, FV2P_ELIMIT, "scatter_add: more than 2^31 entries or rows");
+  FV2P_REQUIRE(ws && ws_bytes >= fv2p_scatter_add_ws_bytes(entries, c), FV2P_EWORKSPACE, "scatter_add: workspace too small");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const int64_t segments = ceil_div(entries, kScatterSeg);
+  Carver cv(ws, ws_bytes);
+  uint64_t* keys = cv.take<uint64_t>(static_cast<size_t>(entries));
+  uint64_t* tmp = cv.take<uint64_t>(static_cast<size_t>(entries));
+  const size_t rb = radix_sort_ws_bytes(entries);
+  void* rws = cv.take<char>(rb);
+  float* part = cv.take<float>(static_cast<size_t>(segments) * 2 * c);
+  int* flags = cv.take<int>(static_cast<size_t>(segments));
+  hipLaunchKernelGGL(scatter_keys_k, dim3(static_cast<unsigned>(ceil_div(entries, 256))), dim3(256), 0, st, entries, n_dst, dst_row, keys);
+  if (int rc = radix_sort_u64(keys, tmp, entries, 32, 32 + bits_for(static_cast<uint64_t>(n_dst)), rws, rb, st)) return rc;
+  int tpr = 1;
+  while (tpr < 64 && tpr * 4 < c) tpr *= 2;
+  const int64_t blocks = ceil_div(segments * tpr, 256);
+  const int vec_ok = src_cs == 1 && (c & 3) == 0 &&
+                     ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(part)) & 15) == 0;
+#define FV2P_SC(T)                                                                                                                      \
+  {                                                                                                                                     \
+    hipLaunchKernelGGL((scatter_seg_k<T>), dim3(static_cast<unsigned>(blocks)), dim3(256), 0, st, n_dst, c, entries, keys, src_off, coef, \
+                       src, src_cs, out, part, flags, vec_ok);                                                                          \
+    hipLaunchKernelGGL((scatter_fix_k<T>), dim3(static_cast<unsigned>(blocks)), dim3(256), 0, st, c, entries, segments, keys, part, flags, \
+                       out, vec_ok);                                                                                                    \
+  }
+  switch (tpr) { case 1: FV2P_SC(1) break; case 2: FV2P_SC(2) break; case 4: FV2P_SC(4) break; case 8: FV2P_SC(8) break;
+                 case 16: FV2P_SC(16) break; case 32: FV2P_SC(32) break; default: FV2P_SC(64) }
+#undef FV2P_SC
+  FV2P_LAUNCH_CHECK();
+  return 0;
+}

@@ -106,11 +106,15 @@ StatRing& stat_ring(const at::Tensor& like, void* stream, int which = 0) {
   return it->second;
 }
 static int g_bn_epilogue = -1;   // FV2P_BN_EPILOGUE=0 or set_bn_epilogue(false): BatchNorm takes its own sums (tests compare the two)
+// deterministic mode (pcdet.ops.set_deterministic): the epilogue sums are float64 atomics, so BatchNorm takes its own fixed-order reduce
+static bool g_deterministic = false;
 static bool fuse_bn_stats() {
   if (g_bn_epilogue < 0) { const char* e = std::getenv("FV2P_BN_EPILOGUE"); g_bn_epilogue = !(e && e[0] == '0'); }
-  return g_bn_epilogue != 0;
+  return g_bn_epilogue != 0 && !g_deterministic;
 }
 void set_bn_epilogue(bool on) { g_bn_epilogue = on ? 1 : 0; }
+void set_deterministic(bool on) { g_deterministic = on; }
+bool deterministic() { return g_deterministic; }
 
 
 // two zeroed device words per (device, stream) for the one-launch BatchNorm passes (fv2p_batchnorm_forward_one / _backward_one);
@@ -1042,6 +1046,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("prenorm_supported", &prenorm_supported, "the conv kernel of this shape can normalise its source rows on the gather");
   m.def("set_bn_fold", &set_bn_fold, "round-6 arrangement of conv / BatchNorm / residual blocks on (default) or off (the round-5 one)");
   m.def("bn_fold", &bn_fold);
+  m.def("set_deterministic", &set_deterministic, "deterministic mode: no float-atomic conv-epilogue statistics (BatchNorm's own fixed-order reduce)");
+  m.def("deterministic", &deterministic);
   m.def("set_bn_one", &set_bn_one, "BatchNorm passes without conv-epilogue sums as one launch each (default) or as reduce + apply");
   m.def("bn_one", &bn_one);
   m.def("set_bn_wide", &set_bn_wide, "large BatchNorm passes with the wide reduce finalised by its own launch (default) or the <= 64-workgroup reduce + folding apply");

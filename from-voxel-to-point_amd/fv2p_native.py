@@ -100,6 +100,24 @@ def lib():
     return _LIB
 
 
+_DETERMINISTIC = False
+
+
+def set_deterministic(on):
+    """Process-wide deterministic mode (off by default): the Python wrappers call the fixed-order `*_gather` forms of the backward
+    passes that otherwise add with float atomics, and the compiled binding keeps BatchNorm statistics off the float64-atomic conv
+    epilogue.  See INTEGRATION.md, "Deterministic mode"."""
+    global _DETERMINISTIC
+    _DETERMINISTIC = bool(on)
+    ext = torch_ext()
+    if ext is not None:
+        ext.set_deterministic(_DETERMINISTIC)
+
+
+def deterministic():
+    return _DETERMINISTIC
+
+
 _EXT = False
 
 

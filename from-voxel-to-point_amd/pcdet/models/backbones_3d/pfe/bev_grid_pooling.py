@@ -42,6 +42,11 @@ class _BevInterp(Function):
         g = grad_out.contiguous()
         grad_bev = torch.empty((b, c, h, w) if channels_first else (b, h, w, c), dtype=g.dtype, device=g.device)
         with _nat.device_guard(g.device):
+            if _nat.deterministic():   # fixed-order form (fv2p_scatter_add) instead of float atomics
+                ws = _nat.workspace(int(_nat.lib().fv2p_bev_interp_bwd_ws_bytes(b, c, h, w, int(channels_first), x.shape[1])), g.device)
+                _nat.call("fv2p_bev_interp_bwd_gather", g, b, c, h, w, int(channels_first), x, y, x.shape[1], grad_bev, ws, ws.numel(),
+                          _nat.stream())
+                return grad_bev, None, None, None
             ws = _nat.workspace(max(b * c * h * w * 4 if channels_first else 16, 16), g.device)
             _nat.call("fv2p_bev_interp_bwd", g, b, c, h, w, int(channels_first), x, y, x.shape[1], grad_bev, ws, ws.numel(), _nat.stream())
         return grad_bev, None, None, None

@@ -164,6 +164,13 @@ def deform_psroi_pooling_backward(out_grad, input, bbox, trans, top_count, no_tr
     x = input.float().contiguous()
     dx = torch.zeros_like(x)
     dtrans = torch.zeros_like(trans, dtype=torch.float32).contiguous()
+    if _nat.deterministic():   # fixed-order form (fv2p_scatter_add): writes dx and dtrans's first len(bbox) rows
+        with _nat.device_guard(input.device):
+            ws = _nat.workspace(_nat.lib().fv2p_deform_psroi_pool_backward_ws_bytes(g[4], g[7], g[9], g[11]), input.device)
+            _nat.call("fv2p_deform_psroi_pool_backward_gather", out_grad.float().contiguous(), x, bbox.float().contiguous(),
+                      None if no_trans else trans.float().contiguous(), top_count.float().contiguous(), *g, dx,
+                      None if no_trans else dtrans, ws, ws.numel(), _nat.stream())
+        return dx.to(input.dtype), dtrans.to(trans.dtype)
     with _nat.device_guard(input.device):
         _nat.call("fv2p_deform_psroi_pool_backward", out_grad.float().contiguous(), x, bbox.float().contiguous(),
                   None if no_trans else trans.float().contiguous(), top_count.float().contiguous(), *g, dx,

@@ -37,6 +37,11 @@ def _bwd(saved, grad):
         raise RuntimeError("sa_grid_max: backward of a forward pass that ran without gradients enabled")
     r, n, m, s, c = saved["dims"]
     g_point, g_centre, g_w = torch.empty_like(per_point), torch.empty_like(per_centre), torch.empty_like(w2)
+    if _nat.deterministic():   # per-point gradient in the fixed order of fv2p_scatter_add instead of LDS atomics
+        ws = G.scratch("fv2p_sa_grid_bwd_gather_ws_bytes", grad.device, r, m, s)
+        G.run("fv2p_sa_grid_bwd_gather", per_point, per_centre, idx, w2, arg, grad.contiguous(), r, n, m, s, c, g_point, g_centre, g_w, ws,
+              ws.numel())
+        return g_point, g_centre, None, g_w
     ws = G.scratch("fv2p_sa_grid_bwd_ws_bytes", grad.device, r)
     G.run("fv2p_sa_grid_bwd", per_point, per_centre, idx, w2, arg, grad.contiguous(), r, n, m, s, c, g_point, g_centre, g_w, ws, ws.numel())
     return g_point, g_centre, None, g_w

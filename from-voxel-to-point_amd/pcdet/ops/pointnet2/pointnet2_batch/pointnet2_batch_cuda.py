@@ -15,6 +15,17 @@ def _go(name, dev_tensor, *args):
     return 1
 
 
+def _det(name, grad_points_tensor, ws_args, *args):
+    """Deterministic mode: `name`_gather writes the gradient into a fresh tensor, which is added to the caller's buffer once (the
+    reference's contract: the buffer is accumulated into)."""
+    g = torch.empty_like(grad_points_tensor)
+    with _nat.device_guard(grad_points_tensor.device):
+        ws = _nat.workspace(getattr(_nat.lib(), name + "_ws_bytes")(*ws_args), grad_points_tensor.device)
+    _go(name + "_gather", grad_points_tensor, *args, g, ws, ws.numel())
+    grad_points_tensor.add_(g)
+    return 1
+
+
 def ball_query_wrapper(b, n, m, radius, nsample, new_xyz_tensor, xyz_tensor, idx_tensor):
     return _go("fv2p_ball_query_batch", idx_tensor, b, n, m, float(radius), nsample, new_xyz_tensor, xyz_tensor, idx_tensor)
 
@@ -24,6 +35,9 @@ def group_points_wrapper(b, c, n, npoints, nsample, points_tensor, idx_tensor, o
 
 
 def group_points_grad_wrapper(b, c, n, npoints, nsample, grad_out_tensor, idx_tensor, grad_points_tensor):
+    if _nat.deterministic():
+        return _det("fv2p_group_points_batch_grad", grad_points_tensor, (b, c, n, npoints, nsample), b, c, n, npoints, nsample,
+                    grad_out_tensor, idx_tensor)
     return _go("fv2p_group_points_batch_grad", grad_out_tensor, b, c, n, npoints, nsample, grad_out_tensor, idx_tensor, grad_points_tensor)
 
 
@@ -32,6 +46,8 @@ def gather_points_wrapper(b, c, n, npoints, points_tensor, idx_tensor, out_tenso
 
 
 def gather_points_grad_wrapper(b, c, n, npoints, grad_out_tensor, idx_tensor, grad_points_tensor):
+    if _nat.deterministic():
+        return _det("fv2p_gather_points_grad", grad_points_tensor, (b, c, n, npoints), b, c, n, npoints, grad_out_tensor, idx_tensor)
     return _go("fv2p_gather_points_grad", grad_out_tensor, b, c, n, npoints, grad_out_tensor, idx_tensor, grad_points_tensor)
 
 
@@ -50,4 +66,7 @@ def three_interpolate_wrapper(b, c, m, n, points_tensor, idx_tensor, weight_tens
 
 
 def three_interpolate_grad_wrapper(b, c, n, m, grad_out_tensor, idx_tensor, weight_tensor, grad_points_tensor):
+    if _nat.deterministic():
+        return _det("fv2p_three_interpolate_batch_grad", grad_points_tensor, (b, c, n, m), b, c, n, m, grad_out_tensor, idx_tensor,
+                    weight_tensor)
     return _go("fv2p_three_interpolate_batch_grad", grad_out_tensor, b, c, n, m, grad_out_tensor, idx_tensor, weight_tensor, grad_points_tensor)

@@ -7,6 +7,8 @@ Each operator is a forward / backward function pair calling the C ABI directly (
 import torch
 import torch.nn as nn
 
+import fv2p_native as _nat
+
 from ... import _glue as G
 
 
@@ -33,6 +35,11 @@ def _gather(saved, features, idx):
 
 def _gather_grad(saved, grad):
     b, c, n, m = saved["shape"]
+    if _nat.deterministic():
+        g = torch.empty((b, c, n), dtype=torch.float32, device=grad.device)
+        ws = G.scratch("fv2p_gather_points_grad_ws_bytes", grad.device, b, c, n, m)
+        G.run("fv2p_gather_points_grad_gather", b, c, n, m, grad.contiguous(), saved["idx"], g, ws, ws.numel())
+        return g
     g = torch.zeros((b, c, n), dtype=torch.float32, device=grad.device)
     G.run("fv2p_gather_points_grad", b, c, n, m, grad.contiguous(), saved["idx"], g)
     return g
@@ -60,6 +67,11 @@ def _interp(saved, features, idx, weight):
 
 def _interp_grad(saved, grad):
     b, c, m, n = saved["shape"]
+    if _nat.deterministic():
+        g = torch.empty((b, c, m), dtype=torch.float32, device=grad.device)
+        ws = G.scratch("fv2p_three_interpolate_batch_grad_ws_bytes", grad.device, b, c, n, m)
+        G.run("fv2p_three_interpolate_batch_grad_gather", b, c, n, m, grad.contiguous(), saved["idx"], saved["weight"], g, ws, ws.numel())
+        return g
     g = torch.zeros((b, c, m), dtype=torch.float32, device=grad.device)
     G.run("fv2p_three_interpolate_batch_grad", b, c, n, m, grad.contiguous(), saved["idx"], saved["weight"], g)
     return g
@@ -87,6 +99,11 @@ def _group(saved, features, idx):
 
 def _group_grad(saved, grad):
     b, c, n, m, s = saved["shape"]
+    if _nat.deterministic():
+        g = torch.empty((b, c, n), dtype=torch.float32, device=grad.device)
+        ws = G.scratch("fv2p_group_points_batch_grad_ws_bytes", grad.device, b, c, n, m, s)
+        G.run("fv2p_group_points_batch_grad_gather", b, c, n, m, s, grad.contiguous(), saved["idx"], g, ws, ws.numel())
+        return g
     g = torch.zeros((b, c, n), dtype=torch.float32, device=grad.device)
     G.run("fv2p_group_points_batch_grad", b, c, n, m, s, grad.contiguous(), saved["idx"], g)
     return g

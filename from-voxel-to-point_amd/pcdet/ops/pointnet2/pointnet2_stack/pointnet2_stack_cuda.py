@@ -16,6 +16,16 @@ def _go(name, dev_tensor, *args):
     return 1
 
 
+def _det(name, grad_features, ws_bytes, *args):
+    """Deterministic mode: the fixed-order form writes a fresh tensor, added to the caller's (accumulated) buffer once."""
+    g = torch.empty_like(grad_features)
+    with _nat.device_guard(grad_features.device):
+        ws = _nat.workspace(ws_bytes, grad_features.device)
+    _go(name, grad_features, *args, g, ws, ws.numel())
+    grad_features.add_(g)
+    return 1
+
+
 def _i32(t):
     return t if t.dtype == torch.int32 else t.int()
 
@@ -40,6 +50,9 @@ def group_points_wrapper(B, M, C, nsample, features, features_batch_cnt, idx, id
 
 
 def group_points_grad_wrapper(B, M, C, N, nsample, grad_out, idx, idx_batch_cnt, features_batch_cnt, grad_features):
+    if _nat.deterministic():
+        return _det("fv2p_group_points_stack_grad_gather", grad_features, _nat.lib().fv2p_group_points_stack_grad_ws_bytes(M, C, nsample),
+                    B, M, C, N, nsample, grad_out, idx, _i32(idx_batch_cnt), _i32(features_batch_cnt))
     return _go("fv2p_group_points_stack_grad", grad_out, B, M, C, N, nsample, grad_out, idx, _i32(idx_batch_cnt),
                _i32(features_batch_cnt), grad_features)
 
@@ -54,4 +67,8 @@ def three_interpolate_wrapper(features, idx, weight, out):
 
 
 def three_interpolate_grad_wrapper(grad_out, idx, weight, grad_features):
+    if _nat.deterministic():
+        n, c, m = idx.shape[0], grad_out.shape[1], grad_features.shape[0]
+        return _det("fv2p_three_interpolate_stack_grad_gather", grad_features, _nat.lib().fv2p_three_interpolate_stack_grad_ws_bytes(n, c, m),
+                    n, c, m, grad_out, idx, weight)
     return _go("fv2p_three_interpolate_stack_grad", grad_out, idx.shape[0], grad_out.shape[1], grad_out, idx, weight, grad_features)

@@ -6,6 +6,8 @@ import os
 import torch
 import torch.nn as nn
 
+import fv2p_native as _nat
+
 from ... import _glue as G
 
 
@@ -39,6 +41,11 @@ def _group(saved, features, features_batch_cnt, idx, idx_batch_cnt):
 
 def _group_grad(saved, grad):
     b, m, c, n, s = saved["dims"]
+    if _nat.deterministic():
+        g = torch.empty((n, c), dtype=torch.float32, device=grad.device)
+        ws = G.scratch("fv2p_group_points_stack_grad_ws_bytes", grad.device, m, c, s)
+        G.run("fv2p_group_points_stack_grad_gather", b, m, c, n, s, grad.contiguous(), saved["idx"], saved["ic"], saved["fc"], g, ws, ws.numel())
+        return g
     g = torch.zeros((n, c), dtype=torch.float32, device=grad.device)
     G.run("fv2p_group_points_stack_grad", b, m, c, n, s, grad.contiguous(), saved["idx"], saved["ic"], saved["fc"], g)
     return g
@@ -103,7 +110,7 @@ GATHER_GRAD_MIN_QUERIES = 8192
 
 def _interp_grad(saved, grad):
     n, c, m = grad.shape[0], grad.shape[1], saved["rows"]
-    if n >= GATHER_GRAD_MIN_QUERIES and os.environ.get("FV2P_INTERP_GATHER", "1") != "0":
+    if _nat.deterministic() or (n >= GATHER_GRAD_MIN_QUERIES and os.environ.get("FV2P_INTERP_GATHER", "1") != "0"):
         g = torch.empty((m, c), dtype=grad.dtype, device=grad.device)
         ws = G.scratch("fv2p_three_interpolate_stack_grad_ws_bytes", grad.device, n, c, m)
         G.run("fv2p_three_interpolate_stack_grad_gather", n, c, m, grad.contiguous(), saved["idx"], saved["weight"], g, ws, ws.numel())

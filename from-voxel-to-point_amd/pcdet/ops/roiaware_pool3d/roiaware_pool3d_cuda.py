@@ -19,6 +19,15 @@ def backward(pts_idx_of_voxels, argmax, grad_out, grad_in, pool_method):
     _nat.require_cuda(pts_idx_of_voxels, argmax, grad_out, grad_in)
     boxes_num, out_x, out_y, out_z, max_pts = pts_idx_of_voxels.shape
     channels = grad_out.shape[4]
+    if _nat.deterministic():   # fixed-order form into a fresh tensor, added to the caller's (accumulated) buffer once
+        g = torch.empty_like(grad_in)
+        with _nat.device_guard(grad_out.device):
+            ws = _nat.workspace(_nat.lib().fv2p_roiaware_pool3d_bwd_ws_bytes(boxes_num, out_x, out_y, out_z, channels, max_pts, int(pool_method)),
+                                grad_out.device)
+            _nat.call("fv2p_roiaware_pool3d_bwd_gather", pts_idx_of_voxels, argmax, grad_out.contiguous(), boxes_num, out_x, out_y, out_z,
+                      channels, max_pts, int(pool_method), grad_in.shape[0], g, ws, ws.numel(), _nat.stream())
+        grad_in.add_(g)
+        return 1
     with _nat.device_guard(grad_out.device):
         _nat.call("fv2p_roiaware_pool3d_bwd", pts_idx_of_voxels, argmax, grad_out.contiguous(), boxes_num, out_x, out_y, out_z, channels,
                   max_pts, int(pool_method), grad_in, _nat.stream())

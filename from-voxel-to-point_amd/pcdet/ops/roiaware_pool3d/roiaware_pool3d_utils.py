@@ -54,6 +54,12 @@ def _pool(saved, rois, pts, pts_feature, out_size, max_pts_each_voxel, pool_meth
 
 def _pool_grad(saved, grad):
     n, ox, oy, oz, c, p, cap = saved["dims"]
+    if _nat.deterministic():
+        g = torch.empty((p, c), dtype=grad.dtype, device=grad.device)
+        ws = G.scratch("fv2p_roiaware_pool3d_bwd_ws_bytes", grad.device, n, ox, oy, oz, c, cap, saved["code"])
+        G.run("fv2p_roiaware_pool3d_bwd_gather", saved["members"], saved["argmax"], grad.contiguous(), n, ox, oy, oz, c, cap, saved["code"], p, g,
+              ws, ws.numel())
+        return None, None, g
     g = torch.zeros((p, c), dtype=grad.dtype, device=grad.device)
     G.run("fv2p_roiaware_pool3d_bwd", saved["members"], saved["argmax"], grad.contiguous(), n, ox, oy, oz, c, cap, saved["code"], g)
     return None, None, g

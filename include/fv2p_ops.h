@@ -299,6 +299,10 @@ int fv2p_bev_interp_fwd(const float* bev, int batch, int c, int h, int w, int ch
                         const float* y, int64_t n, float* out, void* ws, size_t ws_bytes, fv2p_stream_t stream);
 int fv2p_bev_interp_bwd(const float* grad_out, int batch, int c, int h, int w, int channels_first, const float* x,
                         const float* y, int64_t n, float* grad_bev, void* ws, size_t ws_bytes, fv2p_stream_t stream);
+/* bwd in the fixed order of fv2p_scatter_add (4 entries per point, the bilinear weights as coefficients), with its own workspace */
+size_t fv2p_bev_interp_bwd_ws_bytes(int batch, int c, int h, int w, int channels_first, int64_t n);
+int fv2p_bev_interp_bwd_gather(const float* grad_out, int batch, int c, int h, int w, int channels_first, const float* x,
+                               const float* y, int64_t n, float* grad_bev, void* ws, size_t ws_bytes, fv2p_stream_t stream);
 
 /* ---- (f).2: SparseConvTensor.dense() and its gradient ---------------------------------------------------------
  * Replaces scatter_nd + permute + contiguous (pcdet/ops/spconv/structure.py:5-18, 57-66; consumer HeightCompression,
@@ -411,6 +415,12 @@ int fv2p_roiaware_pool3d_fwd(const float* rois, const float* pts, const float* p
 int fv2p_roiaware_pool3d_bwd(const int* pts_idx_of_voxels, const int* argmax, const float* grad_out, int boxes_num,
                              int out_x, int out_y, int out_z, int channels, int max_pts_each_voxel, int pool_method,
                              float* grad_in, fv2p_stream_t stream);
+/* roiaware_pool3d_bwd in the fixed order of fv2p_scatter_add; pts_num = rows of grad_in (P), which is written, not accumulated */
+size_t fv2p_roiaware_pool3d_bwd_ws_bytes(int boxes_num, int out_x, int out_y, int out_z, int channels, int max_pts_each_voxel,
+                                         int pool_method);
+int fv2p_roiaware_pool3d_bwd_gather(const int* pts_idx_of_voxels, const int* argmax, const float* grad_out, int boxes_num,
+                                    int out_x, int out_y, int out_z, int channels, int max_pts_each_voxel, int pool_method,
+                                    int pts_num, float* grad_in, void* ws, size_t ws_bytes, fv2p_stream_t stream);
 
 /* ---- A8-A12: pointnet2 (batch and stacked layouts) ------------------------------------------------
  * Replace pointnet2_batch_cuda.* (pcdet/ops/pointnet2/pointnet2_batch/src/pointnet2_api.cpp:10-24) and
@@ -492,6 +502,35 @@ size_t fv2p_three_interpolate_stack_grad_ws_bytes(int n, int c, int m);
 int fv2p_three_interpolate_stack_grad_gather(int n, int c, int m, const float* grad_out, const int* idx, const float* weight,
                                              float* grad_features, void* ws, size_t ws_bytes, fv2p_stream_t stream);
 
+/* ---- Deterministic mode: scatter-add in a fixed order, and the backward passes built on it --------------------------------
+ * fv2p_scatter_add: for every entry e whose dst_row[e] lies in [0, n_dst),
+ *     out[dst_row[e] * c + ch] += coef[e] * src[src_off[e] + ch * src_cs]      (ch < c)
+ * coef NULL = 1; src_off NULL = e * c (then src_cs must be 1: src is [entries, c]).  Other entries are dropped.  The association of
+ * every sum is a function of the entry list only: the entries of a row are taken in ascending e, at their positions in the (row, e)
+ * order of all kept entries; that sequence is cut into segments of 32 positions; the piece of a row inside one segment is summed from
+ * zero in order (acc = acc + coef * value, two roundings), the pieces of a row that spans segments are added in segment order (first
+ * piece, then the next ones), and the row's total is added to out once.  No float atomics; bit-identical from run to run, whatever the
+ * stream or the other work on the device.  entries < 2^31, n_dst < 2^31 - 1.
+ * The *_gather backward passes below compute the gradient of the atomic entry point they are named after, in that fixed order, and
+ * WRITE their outputs (no zero fill by the caller); index entries outside their range are dropped.  Each needs the workspace of its
+ * *_ws_bytes query. */
+size_t fv2p_scatter_add_ws_bytes(int64_t entries, int c);
+int fv2p_scatter_add(int64_t entries, int c, int64_t n_dst, const int* dst_row, const int64_t* src_off, const float* coef,
+                     const float* src, int64_t src_cs, float* out, void* ws, size_t ws_bytes, fv2p_stream_t stream);
+size_t fv2p_group_points_batch_grad_ws_bytes(int b, int c, int n, int npoints, int nsample);
+int fv2p_group_points_batch_grad_gather(int b, int c, int n, int npoints, int nsample, const float* grad_out, const int* idx,
+                                        float* grad_points, void* ws, size_t ws_bytes, fv2p_stream_t stream);
+size_t fv2p_gather_points_grad_ws_bytes(int b, int c, int n, int npoints);
+int fv2p_gather_points_grad_gather(int b, int c, int n, int npoints, const float* grad_out, const int* idx, float* grad_points,
+                                   void* ws, size_t ws_bytes, fv2p_stream_t stream);
+size_t fv2p_group_points_stack_grad_ws_bytes(int m, int c, int nsample);
+int fv2p_group_points_stack_grad_gather(int b, int m, int c, int n, int nsample, const float* grad_out, const int* idx,
+                                        const int* idx_batch_cnt, const int* features_batch_cnt, float* grad_features, void* ws,
+                                        size_t ws_bytes, fv2p_stream_t stream);
+size_t fv2p_three_interpolate_batch_grad_ws_bytes(int b, int c, int n, int m);
+int fv2p_three_interpolate_batch_grad_gather(int b, int c, int n, int m, const float* grad_out, const int* idx, const float* weight,
+                                             float* grad_points, void* ws, size_t ws_bytes, fv2p_stream_t stream);
+
 /* ---- A11 consumer: fused grid set-abstraction (gather -> shared-MLP layer -> max over the samples) ---------------------
  * The part of PointnetSAModuleMSG.forward (pointnet2_batch/pointnet2_modules.py:30-62) that follows the ball query, for the
  * bn=False module of IoUGuidedRoIHead (iouguided_roi_head.py:52-76) after its first, linear layer has been applied per point
@@ -509,6 +548,12 @@ size_t fv2p_sa_grid_bwd_ws_bytes(int rois);
 int fv2p_sa_grid_bwd(const float* per_point, const float* per_centre, const int* idx, const float* w2, const unsigned char* arg,
                      const float* grad_out, int rois, int n, int m, int s, int c, float* grad_point, float* grad_centre,
                      float* grad_w2, void* ws, size_t ws_bytes, fv2p_stream_t stream);
+/* The same backward with the per-point gradient in the fixed order of fv2p_scatter_add: every (RoI, centre, sample) row of dh1 is
+ * written out and summed into its point's row (no LDS atomics); dW2, grad_centre and the arg-max routing are fv2p_sa_grid_bwd's. */
+size_t fv2p_sa_grid_bwd_gather_ws_bytes(int rois, int m, int s);
+int fv2p_sa_grid_bwd_gather(const float* per_point, const float* per_centre, const int* idx, const float* w2, const unsigned char* arg,
+                            const float* grad_out, int rois, int n, int m, int s, int c, float* grad_point, float* grad_centre,
+                            float* grad_w2, void* ws, size_t ws_bytes, fv2p_stream_t stream);
 
 /* ---- A13: modulated deformable convolution (DCNv2; DCNv1 = mask of ones) -------------------------
  * Replace DCN.modulated_deform_conv_forward / _backward and DCN.deform_conv_forward / _backward
@@ -575,6 +620,15 @@ int fv2p_deform_psroi_pool_backward(const float* grad_out, const float* data, co
                                     int group_size, int pooled_size, int part_size, int sample_per_part,
                                     float trans_std, int num_classes, float* grad_data, float* grad_trans,
                                     fv2p_stream_t stream);
+/* backward in the fixed order of fv2p_scatter_add: grad_data from 4 entries per sample, grad_trans from the bins' sums (each over
+ * its samples in order) as 2 entries per bin.  Writes grad_data and the first num_rois rows of grad_trans (no zero fill needed). */
+size_t fv2p_deform_psroi_pool_backward_ws_bytes(int num_rois, int output_dim, int pooled_size, int sample_per_part);
+int fv2p_deform_psroi_pool_backward_gather(const float* grad_out, const float* data, const float* rois, const float* trans,
+                                           const float* top_count, int batch, int channels, int height, int width,
+                                           int num_rois, int no_trans, float spatial_scale, int output_dim,
+                                           int group_size, int pooled_size, int part_size, int sample_per_part,
+                                           float trans_std, int num_classes, float* grad_data, float* grad_trans,
+                                           void* ws, size_t ws_bytes, fv2p_stream_t stream);
 
 /* ---- (f).3: BatchNorm1d (+ReLU) over sparse-tensor features [N, C] --------------------------------
  * The pair every conv of the reference backbones is followed by: nn.BatchNorm1d(eps=1e-3, momentum=0.01) + nn.ReLU
