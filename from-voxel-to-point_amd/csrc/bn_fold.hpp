@@ -171,6 +171,9 @@ __device__ __forceinline__ void fin_rows_done(double* rows, double* gslots, unsi
       fo.bf.coef[fo.coef_ld + tid] = fo.bf.batch_stats ? static_cast<float>(sb / nn) : 0.f;
     }
   }
+  // momentum=None: every column above read *num_batches_tracked; the bump below must not overtake a column of another wave (c > 64).
+  // The threads arriving here are the ones that passed the barrier above (tid < 256 of the finalising workgroup).
+  __syncthreads();
   if (tid == 0) {
     if (!fo.bwd && fo.bump && fo.ff.running_mean && fo.ff.num_batches_tracked) *fo.ff.num_batches_tracked += 1;
     __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

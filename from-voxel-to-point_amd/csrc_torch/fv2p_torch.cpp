@@ -13,6 +13,7 @@
 #include <c10/core/DeviceGuard.h>
 #include <hip/hip_runtime_api.h>
 
+#include <atomic>
 #include <cstdlib>
 
 #include <map>
@@ -30,7 +31,17 @@ using torch::autograd::variable_list;
 
 void* cur_stream(const at::Tensor& t) { return static_cast<void*>(c10::hip::getCurrentHIPStream(t.device().index()).stream()); }
 
+// record_entry_points(true): every library call the binding makes is logged by name until entry_points() collects the log, so tests can
+// assert which route a call took (tests/test_bn_routes_gpu.py).  Off by default; backward passes run on the autograd engine's thread.
+std::atomic<bool> g_record{false};
+std::mutex g_record_mu;
+std::vector<std::string> g_entries;
+
 void check(int rc, const char* what) {
+  if (g_record.load(std::memory_order_relaxed)) {
+    std::lock_guard<std::mutex> lock(g_record_mu);
+    g_entries.emplace_back(what);
+  }
   TORCH_CHECK(rc >= 0, what, " failed (", rc, "): ", fv2p_last_error());
 }
 
@@ -829,7 +840,10 @@ struct ConvFinFn : public torch::autograd::Function<ConvFinFn> {
     out[0] = din;
     out[1] = dw;
     if (ctx->saved_data["has_bias"].toBool()) out[12] = at::zeros({cout}, features.options());   // see the section comment
-    if (pre) { out[21] = dgamma_src; out[22] = dbeta_src; }
+    if (pre) {   // (an affine=False BatchNorm passes no gamma / beta: no gradient may be returned for them)
+      if (pre_gamma.defined()) out[21] = dgamma_src;
+      if (pre_beta.defined()) out[22] = dbeta_src;
+    }
     return out;
   }
 };
@@ -1052,5 +1066,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("bn_one", &bn_one);
   m.def("set_bn_wide", &set_bn_wide, "large BatchNorm passes with the wide reduce finalised by its own launch (default) or the <= 64-workgroup reduce + folding apply");
   m.def("bn_wide", &bn_wide);
+  m.def("record_entry_points", [](bool on) {
+    std::lock_guard<std::mutex> lock(g_record_mu);
+    g_entries.clear();
+    g_record.store(on);
+  }, "log the name of every library entry point the binding calls (tests), and clear the log");
+  m.def("entry_points", []() {
+    std::lock_guard<std::mutex> lock(g_record_mu);
+    std::vector<std::string> out;
+    out.swap(g_entries);
+    return out;
+  }, "the entry points called since the last collection");
   m.def("sparse_conv_bn_relu", &sparse_conv_bn_relu, "sparse conv -> BatchNorm1d (-> ReLU) with autograd, one call per backbone block");
 }

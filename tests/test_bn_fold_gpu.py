@@ -65,32 +65,36 @@ def subm_tables(x, conv, planned=False):
     return rb, tab_f, flip_f, tab_b, flip_b
 
 
-@pytest.mark.parametrize("c,n,planned", [(16, 1500, False), (32, 1500, False), (64, 1500, False), (128, 1500, False), (64, 5000, False), (128, 70, False),
-                                         (64, 1100, True), (128, 1500, True), (128, 2600, True), (64, 9000, True)])
-def test_statistics_finalised_by_the_conv_launch(gpu, c, n, planned):
+@pytest.mark.parametrize("c,n,planned,momentum", [pytest.param(c, n, p, 0.01, id=f"{c}-{n}-{p}") for c, n, p in (
+    (16, 1500, False), (32, 1500, False), (64, 1500, False), (128, 1500, False), (64, 5000, False), (128, 70, False), (64, 1100, True), (128, 1500, True),
+    (128, 2600, True), (64, 9000, True))] + [pytest.param(128, 1500, False, None, id="128-1500-False-momentumNone")])
+def test_statistics_finalised_by_the_conv_launch(gpu, c, n, planned, momentum):
     """(planned: a small table with a tiling plan - 256 tiles for ~1 500 rows - once overran the row buffer of the finalisation.)
     conv_fin leaves mean / invstd of ITS output and the running statistics as BatchNorm1d would compute them: against float64 sums of the
     conv's own output at 1e-6, running statistics like torch's (momentum 0.01, unbiased variance), num_batches_tracked + 1; a second call
     (the slots were cleared by the last workgroup, the counter reset) gives the same statistics again, and so does a third on another layer
-    size in between (one slot buffer per stream serves every layer)."""
+    size in between (one slot buffer per stream serves every layer).  momentum=None: the cumulative average, 1 / (num_batches_tracked + 1)
+    for every column - the first call from a fresh layer replaces the running statistics, the second, on the same rows, keeps them."""
     e = ext()
     batch, shape = 2, [9, 20, 18]
     ind, feats, x = make_input(c * 3 + n, batch, shape, n, c, gpu)
     conv = spconv.SubMConv3d(c, c, 3, padding=1, bias=True, indice_key="k").to(gpu)
-    bn = nn.BatchNorm1d(c, eps=1e-3, momentum=0.01).to(gpu)
+    bn = nn.BatchNorm1d(c, eps=1e-3, momentum=momentum).to(gpu)
+    f = 1.0 if momentum is None else momentum
     rb, tab_f, flip_f, tab_b, flip_b = subm_tables(x, conv, planned)
     rm0, rv0 = bn.running_mean.clone(), bn.running_var.clone()
 
     def run():
         return e.conv_fin(x.features, conv.weight, tab_f, flip_f, tab_b, flip_b, x.features.shape[0], rb.kvol // 2, None, None, 0, None, conv.bias, True,
-                          bn.running_mean, bn.running_var, bn.num_batches_tracked, True, 0.01, 1e-3, None, None, None, False, False)
+                          bn.running_mean, bn.running_var, bn.num_batches_tracked, True, -1.0 if momentum is None else momentum, 1e-3, None, None,
+                          None, False, False)
     y, saved = run()
     y64 = y.double()
     mean, var = y64.mean(0), y64.var(0, unbiased=False)
     assert rel(saved[0], mean) < 1e-6 and rel(saved[1], 1.0 / torch.sqrt(var + 1e-3)) < 1e-6
     nrows = y.shape[0]
-    assert rel(bn.running_mean, 0.99 * rm0.double() + 0.01 * mean) < 1e-6
-    assert rel(bn.running_var, 0.99 * rv0.double() + 0.01 * var * nrows / (nrows - 1)) < 1e-6
+    assert rel(bn.running_mean, (1 - f) * rm0.double() + f * mean) < 1e-6
+    assert rel(bn.running_var, (1 - f) * rv0.double() + f * var * nrows / (nrows - 1)) < 1e-6
     assert int(bn.num_batches_tracked) == 1
     # conv output itself: oracle
     _, pairs, num = oracle.indice_pairs(ind, batch, shape, [3, 3, 3], [1, 1, 1], [1, 1, 1], [1, 1, 1], subm=True)
@@ -108,6 +112,8 @@ def test_statistics_finalised_by_the_conv_launch(gpu, c, n, planned):
     assert torch.equal(y, y_again)
     assert rel(saved_again, saved) < 1e-7
     assert int(bn.num_batches_tracked) == 2
+    if momentum is None:   # f = 1/2 on the same rows: the running statistics stay the batch's
+        assert rel(bn.running_mean, mean) < 1e-6 and rel(bn.running_var, var * nrows / (nrows - 1)) < 1e-6
 
 
 @pytest.mark.parametrize("cin,cout,n", [(16, 16, 1500), (32, 32, 1500), (32, 16, 900), (64, 64, 1500), (128, 128, 1500), (64, 128, 1200), (128, 64, 70), (64, 64, 20000)])
