@@ -27,8 +27,9 @@ namespace fv2p {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
+// G: convolution groups - input channels [g*Cin/G, (g+1)*Cin/G) feed output channels [g*Cout/G, (g+1)*Cout/G) only
 struct DcnGeom {
-  int B, H, W, Cin, Cout, Ho, Wo, kh, kw, sh, sw, ph, pw, dh, dw, dg;
+  int B, H, W, Cin, Cout, Ho, Wo, kh, kw, sh, sw, ph, pw, dh, dw, dg, G;
 };
 
 // out = (accumulate ? out : 0) + partial[0] + partial[1] + ...: a fixed order, also across the batch chunks of one call
@@ -90,8 +91,10 @@ __device__ __forceinline__ void make_corners(const DcnGeom& g, bool live, int b,
 
 __device__ __forceinline__ f32x4 ldx4(const char* base, unsigned off) { return *reinterpret_cast<const f32x4*>(base + off); }
 
-// x NHWC [B,H,W,Cin]; wt_oc [K][Cout][Cin]; y NHWC [npix][Cout].
-// Block = 4 waves, wave = MB*16 pixels x NB*16 output channels (grid.y = column blocks of NB*16).  Product formed transposed:
+// x NHWC [B,H,W,Cin]; wt_oc [K][Cout][Cin/G]; y NHWC [npix][Cout].
+// Block = 4 waves, wave = MB*16 pixels x NB*16 output channels.  n_sub = G x (column blocks of NB*16 per conv group): a workgroup's
+// columns never cross a group, and its steps walk that group's Cin/G input channels only, 16 at a time (chunk J of the map's channels,
+// deformable group J / cps: a chunk never crosses a deformable group either, the caller guarantees Cin/G and Cin/dg multiples of 16).  Product formed transposed:
 // A = weights (rows = output channels, LDS), B = modulated bilinear samples (columns = pixels, registers of the lane that gathered them).
 // TAPIN (round 6): step order (group, 16-channel chunk, tap) instead of (tap, group, chunk).  The nine taps of one chunk gather from the same
 // 4 x 4-pixel neighbourhoods of 64-byte segments back to back (L1 / L2 hits), where the tap-outer order walks a pixel's whole channel
@@ -109,11 +112,14 @@ __global__ __launch_bounds__(256, 2) void dcn_fwd_k(DcnGeom g, const float* __re
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), n = lane & 15, gq = lane >> 4;
   const long long npix = static_cast<long long>(g.B) * g.Ho * g.Wo;
   const int plane = g.Ho * g.Wo;
-  const int K = g.kh * g.kw, cpg = g.Cin / g.dg, cps = cpg / 16, segs = K * g.dg, steps = segs * cps;
+  const int K = g.kh * g.kw, cpg = g.Cin / g.dg, cps = cpg / 16, cing = g.Cin / g.G, coutg = g.Cout / g.G;
   long long tile;
-  int cb;
-  xcd_tile(n_sub, tile, cb);
-  const int col0 = cb * (NB * 16);
+  int sub;
+  xcd_tile(n_sub, tile, sub);
+  const int col_blocks = n_sub / g.G, grp = sub / col_blocks, cb = sub - grp * col_blocks;
+  // this group's 16-channel chunks [J0, J1) and deformable groups [dgA, dgB]; columns [col0, co_end)
+  const int J0 = grp * (cing / 16), J1 = J0 + cing / 16, dgA = J0 / cps, dgB = (J1 - 1) / cps, steps = K * (J1 - J0);
+  const int col0 = grp * coutg + cb * (NB * 16), co_end = grp * coutg + coutg;
   const long long tile0 = pix_base + tile * (64 * MB) + wave * (16 * MB);
   // this lane's pixels
   bool live[MB];
@@ -129,19 +135,20 @@ __global__ __launch_bounds__(256, 2) void dcn_fwd_k(DcnGeom g, const float* __re
     pwo[mb] = ppos[mb] % g.Wo;
   }
   // weight rows this lane feeds to the LDS-DMA: piece nb (1 KB = 64 lanes x 16 B), lane (n, gq) <- wt_oc[k][col0 + nb*16 + n][c0 + 4 gq ..]
+  // (c0: channel within the group)
   constexpr int NDMA = (NB + 3) / 4;
   const float* wrow[NDMA];
 #pragma unroll
   for (int i = 0; i < NDMA; ++i) {
     const int nb = wave + 4 * i;
-    const int co = min(col0 + nb * 16 + n, g.Cout - 1);
-    wrow[i] = wt_oc + static_cast<long long>(co) * g.Cin + 4 * gq;
+    const int co = min(col0 + nb * 16 + n, co_end - 1);
+    wrow[i] = wt_oc + static_cast<long long>(co) * cing + 4 * gq;
   }
   auto dma = [&](int k, int c0, float* buf) {
 #pragma unroll
     for (int i = 0; i < NDMA; ++i) {
       const int nb = wave + 4 * i;
-      if (nb < NB) glds16(wrow[i] + (static_cast<long long>(k) * g.Cout * g.Cin + c0), buf + nb * 256);
+      if (nb < NB) glds16(wrow[i] + (static_cast<long long>(k) * g.Cout * cing + c0), buf + nb * 256);
     }
   };
   Corner4 t[MB];
@@ -193,10 +200,10 @@ __global__ __launch_bounds__(256, 2) void dcn_fwd_k(DcnGeom g, const float* __re
 #pragma unroll
     for (int mb = 0; mb < MB; ++mb) acc[nb][mb] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  // position of a step: tap k, group dgi, chunk c of the group
-  auto advance = [&](int& k_, int& dg_, int& c_) {
-    if constexpr (TAPIN) { if (++k_ == K) { k_ = 0; if (++c_ == cps) { c_ = 0; ++dg_; } } }
-    else { if (++c_ == cps) { c_ = 0; if (++dg_ == g.dg) { dg_ = 0; ++k_; } } }
+  // position of a step: tap k, chunk J (of the map's channels), its deformable group dgi
+  auto advance = [&](int& k_, int& dg_, int& j_) {
+    if constexpr (TAPIN) { if (++k_ == K) { k_ = 0; if (++j_ == (dg_ + 1) * cps) ++dg_; } }
+    else { if (++j_ == J1) { j_ = J0; dg_ = dgA; ++k_; } else if (j_ == (dg_ + 1) * cps) ++dg_; }
   };
   // TAPIN: this wave's tap states of the current group, [K][16 pixels][8]: {offset of corner 0, + column, + row, mask} {four bilinear weights}
   float* taps = lds + 2 * FRAG + wave * (K * 16 * 8);
@@ -230,39 +237,41 @@ __global__ __launch_bounds__(256, 2) void dcn_fwd_k(DcnGeom g, const float* __re
   };
   // prologue: step 0 taps and operands; the offsets of the next tap state that will be needed
   if constexpr (TAPIN) {
-    build_group(0);
+    build_group(dgA);
     fetch_taps(0);
     expand_taps();
   } else {
-    load_offsets(0, 0);
+    load_offsets(0, dgA);
     set_taps(0);
-    if (segs > 1) load_offsets(g.dg > 1 ? 0 : 1, g.dg > 1 ? 1 : 0);   // segment 1 = (tap, group) after (0, 0)
+    if (dgB > dgA) load_offsets(0, dgA + 1);   // segment 1 = (tap, group) after (0, dgA)
+    else if (K > 1) load_offsets(1, dgA);
   }
   dma(0, 0, lds);
-  gather(0);
+  gather(J0 * 16);
   f32x4 bs[MB];
   combine(bs);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
-  int k = 0, dgi = 0, c = 0;   // position of step s
+  int k = 0, dgi = dgA, c = J0;   // position of step s
   for (int s = 0; s < steps; ++s) {
     float* cur = lds + (s & 1) * FRAG;
     // position of step s + 1
     int c1 = c, dg1 = dgi, k1 = k;
     advance(k1, dg1, c1);
     const bool more = s + 1 < steps;
+    const bool new_seg = dg1 != dgi || k1 != k;   // (tap, group) segment of step s + 1 starts there
     if (more) {
       if constexpr (TAPIN) {
         if (dg1 != dgi) build_group(dg1);           // (the state of step s is in registers already)
         fetch_taps(k1);                             // (read two steps ahead into a second register set: 2 014 against 1 856 us at the head)
         expand_taps();
-      } else if (c1 == 0) set_taps(k1);             // its offsets were fetched a segment ago
-      dma(k1, (dg1 * cps + c1) * 16, lds + ((s + 1) & 1) * FRAG);
-      gather((dg1 * cps + c1) * 16);
+      } else if (new_seg) set_taps(k1);             // its offsets were fetched a segment ago
+      dma(k1, (c1 - J0) * 16, lds + ((s + 1) & 1) * FRAG);
+      gather(c1 * 16);
       if constexpr (TAPIN) {
-      } else if (c1 == 0) {                         // fetch the offsets of the segment after that
+      } else if (new_seg) {                         // fetch the offsets of the segment after that
         int dg2 = dg1 + 1, k2 = k1;
-        if (dg2 == g.dg) { dg2 = 0; ++k2; }
+        if (dg2 > dgB) { dg2 = dgA; ++k2; }
         if (k2 < K) load_offsets(k2, dg2);
       }
     }
@@ -288,16 +297,16 @@ __global__ __launch_bounds__(256, 2) void dcn_fwd_k(DcnGeom g, const float* __re
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) {
       const int col = col0 + nb * 16 + 4 * gq;
-      if (col >= g.Cout) continue;
+      if (col >= co_end) continue;
       f32x4 v = acc[nb][mb];
       float* dst = y + pix * g.Cout + col;
-      if (col + 3 < g.Cout && (g.Cout & 3) == 0) {
+      if (col + 3 < co_end && (coutg & 3) == 0) {
         if (bias) { const f32x4 bb = *reinterpret_cast<const f32x4*>(bias + col); v += bb; }
         *reinterpret_cast<f32x4*>(dst) = v;
       } else {
 #pragma unroll
         for (int e = 0; e < 4; ++e)
-          if (col + e < g.Cout) dst[e] = v[e] + (bias ? bias[col + e] : 0.f);
+          if (col + e < co_end) dst[e] = v[e] + (bias ? bias[col + e] : 0.f);
       }
     }
   }
@@ -342,25 +351,36 @@ __device__ __forceinline__ void make_corners_b(const DcnGeom& g, bool live, int 
   t.o[3] = (row1 + w1) * pitch + lane_bytes;
 }
 
-// JO = ceil(Cout / 16); NBP = 16-pixel blocks per wave; block = 4 waves = 64 * NBP pixels; step = (tap, group, 16 * MC input channels)
+// JO = ceil(columns of the slice / 16); NBP = 16-pixel blocks per wave; block = 4 waves = 64 * NBP pixels; step = (tap, group,
+// 16 * MC input channels).  wt = [K][Cin][Cout/G].  A workgroup covers the input channels of ONE conv group (grp0 + sub / n_share) and
+// the group's output columns [256 slice, 256 slice + 256): its dy registers hold those columns only.  slice > 0 adds to colg and to
+// grad_offset / grad_mask (the caller launches the slices in ascending order), and so does a deformable group that began in an earlier
+// conv group (launched before this one): fixed-order sums, no float atomics.
 template <int JO, int NBP, int MC>
 __global__ __launch_bounds__(256, 2) void dcn_bwd_col_k(DcnGeom g, const float* __restrict__ x, const float* __restrict__ wt,
                                                         const float* __restrict__ offset, const float* __restrict__ mask,
                                                         const float* __restrict__ dy, float* __restrict__ colg, float* __restrict__ doff,
-                                                        float* __restrict__ dmask, long long pix_base, int n_sub) {
+                                                        float* __restrict__ dmask, long long pix_base, int n_sub, int n_share, int grp0,
+                                                        int slice) {
   extern __shared__ __attribute__((aligned(16))) float lds[];   // 2 x (MC x JO) pieces of 256 floats
   constexpr int FRAG = MC * JO * 256, CS = 16 * MC;
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), n = lane & 15, gq = lane >> 4;
   const long long npix = static_cast<long long>(g.B) * g.Ho * g.Wo;
   const int plane = g.Ho * g.Wo;
-  const int K = g.kh * g.kw, cpg = g.Cin / g.dg, cps = cpg / CS, segs = K * g.dg;   // cpg % CS == 0
-  // n_sub shares of the (tap, group) segments per pixel tile: small maps do not fill the chip with pixel tiles alone
+  const int K = g.kh * g.kw, cpg = g.Cin / g.dg, cps = cpg / CS, cing = g.Cin / g.G, coutg = g.Cout / g.G;   // cpg % CS == cing % CS == 0
+  // n_share shares of the group's (tap, group) segments per pixel tile: small maps do not fill the chip with pixel tiles alone
   long long tile;
-  int share;
-  xcd_tile(n_sub, tile, share);
-  const int seg_begin = static_cast<int>(static_cast<long long>(segs) * share / n_sub);
-  const int seg_end = static_cast<int>(static_cast<long long>(segs) * (share + 1) / n_sub);
-  const int steps = (seg_end - seg_begin) * cps;
+  int sub;
+  xcd_tile(n_sub, tile, sub);
+  const int grp = grp0 + sub / n_share, share = sub % n_share;
+  // the group's chunks [J0, J1) of CS channels, deformable groups [dgA, dgB]; segment sg = (tap sg / nsd, deformable group dgA + sg % nsd)
+  const int J0 = grp * (cing / CS), J1 = J0 + cing / CS, dgA = J0 / cps, dgB = (J1 - 1) / cps, nsd = dgB - dgA + 1, segs = K * nsd;
+  const int cs0 = grp * coutg + 256 * slice, ncols = min(256, coutg - 256 * slice);   // the slice's dy columns [cs0, cs0 + ncols)
+  const bool add = slice > 0;
+  const int seg_begin = static_cast<int>(static_cast<long long>(segs) * share / n_share);
+  const int seg_end = static_cast<int>(static_cast<long long>(segs) * (share + 1) / n_share);
+  auto seg_step = [&](int sg) { return (sg / nsd) * (J1 - J0) + max(J0, (dgA + sg % nsd) * cps) - J0; };   // first step of segment sg
+  const int steps = seg_step(seg_end) - seg_step(seg_begin);
   const long long tile0 = pix_base + tile * (64 * NBP) + wave * (16 * NBP);
   bool live[NBP];
   int pb[NBP], pho[NBP], pwo[NBP], ppos[NBP];
@@ -381,17 +401,17 @@ __global__ __launch_bounds__(256, 2) void dcn_bwd_col_k(DcnGeom g, const float* 
       const int c = 16 * jb + 4 * gq;
       f32x4 v = f32x4{0.f, 0.f, 0.f, 0.f};
       if (live[np]) {
-        const float* p = dy + pp * g.Cout + c;
-        if (c + 3 < g.Cout && (g.Cout & 3) == 0) v = *reinterpret_cast<const f32x4*>(p);
+        const float* p = dy + pp * g.Cout + cs0 + c;
+        if (c + 3 < ncols && (coutg & 3) == 0) v = *reinterpret_cast<const f32x4*>(p);
         else {
 #pragma unroll
-          for (int e = 0; e < 4; ++e) if (c + e < g.Cout) v[e] = p[e];
+          for (int e = 0; e < 4; ++e) if (c + e < ncols) v[e] = p[e];
         }
       }
       dyr[np][jb] = v;
     }
   }
-  // LDS-DMA pieces: piece (mc, jb), lane (n, gq) <- wt[k][ci0 + mc*16 + n][16 jb + 4 gq ..]; pieces dealt to the waves round robin
+  // LDS-DMA pieces: piece (mc, jb), lane (n, gq) <- wt[k][ci0 + mc*16 + n][256 slice + 16 jb + 4 gq ..]; pieces dealt to the waves round robin
   constexpr int NP = MC * JO, NDMA = (NP + 3) / 4;
   auto dma = [&](int k, int ci0, float* buf) {
 #pragma unroll
@@ -399,8 +419,8 @@ __global__ __launch_bounds__(256, 2) void dcn_bwd_col_k(DcnGeom g, const float* 
       const int pc = wave + 4 * i;
       if (pc < NP) {
         const int mc = pc / JO, jb = pc % JO;
-        const int co = min(16 * jb + 4 * gq, g.Cout - 4);
-        glds16(wt + (static_cast<long long>(k) * g.Cin + ci0 + mc * 16 + n) * g.Cout + co, buf + pc * 256);
+        const int co = 256 * slice + min(16 * jb + 4 * gq, ncols - 4);
+        glds16(wt + (static_cast<long long>(k) * g.Cin + ci0 + mc * 16 + n) * coutg + co, buf + pc * 256);
       }
     }
   };
@@ -428,20 +448,20 @@ __global__ __launch_bounds__(256, 2) void dcn_bwd_col_k(DcnGeom g, const float* 
 #pragma unroll
   for (int np = 0; np < NBP; ++np) Dq[np][0] = Dq[np][1] = Dq[np][2] = Dq[np][3] = 0.f;
   if (steps <= 0) return;
-  int k = seg_begin / g.dg, dgi = seg_begin % g.dg, c = 0;
+  int k = seg_begin / nsd, dgi = dgA + seg_begin % nsd, c = max(J0, dgi * cps);   // c: chunk of the map's channels
   load_offsets(k, dgi);
   set_taps(k);
-  if (seg_begin + 1 < seg_end) load_offsets((seg_begin + 1) / g.dg, (seg_begin + 1) % g.dg);
-  dma(k, dgi * cps * CS, lds);
+  if (seg_begin + 1 < seg_end) load_offsets((seg_begin + 1) / nsd, dgA + (seg_begin + 1) % nsd);
+  dma(k, c * CS, lds);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
   for (int s = 0; s < steps; ++s) {
     float* cur = lds + (s & 1) * FRAG;
     int c1 = c + 1, dg1 = dgi, k1 = k;
-    if (c1 == cps) { c1 = 0; ++dg1; if (dg1 == g.dg) { dg1 = 0; ++k1; } }
+    if (c1 == J1) { c1 = J0; dg1 = dgA; ++k1; } else if (c1 == (dgi + 1) * cps) ++dg1;
     const bool more = s + 1 < steps;
-    const int ci0 = (dgi * cps + c) * CS;
-    if (more) dma(k1, (dg1 * cps + c1) * CS, lds + ((s + 1) & 1) * FRAG);
+    const int ci0 = c * CS;
+    if (more) dma(k1, c1 * CS, lds + ((s + 1) & 1) * FRAG);
     // x at the four corners of this step's channels (consumed by the epilogue, after the MFMAs)
     f32x4 raw[NBP][MC][4];
     {
@@ -485,10 +505,13 @@ __global__ __launch_bounds__(256, 2) void dcn_bwd_col_k(DcnGeom g, const float* 
             for (int e = 0; e < 4; ++e) a = __builtin_fmaf(d[e], raw[np][mc][q][e], a);
             Dq[np][q] = a;
           }
-          if (live[np]) *reinterpret_cast<f32x4*>(cg + mc * 64 + cbase[np]) = d * t[np].m;
+          if (live[np]) {
+            f32x4* dst = reinterpret_cast<f32x4*>(cg + mc * 64 + cbase[np]);
+            *dst = add ? *dst + d * t[np].m : d * t[np].m;
+          }
         }
     }
-    if (c1 == 0 || !more) {
+    if (dg1 != dgi || k1 != k || !more) {
       // end of the (tap, group) segment: reduce D_q over the four channel quarters (lanes n, n+16, n+32, n+48), write grad_mask / grad_offset
 #pragma unroll
       for (int np = 0; np < NBP; ++np) {
@@ -506,17 +529,21 @@ __global__ __launch_bounds__(256, 2) void dcn_bwd_col_k(DcnGeom g, const float* 
           const float gm = t[np].w[0] * D[0] + t[np].w[1] * D[1] + t[np].w[2] * D[2] + t[np].w[3] * D[3];
           const float gh = m * (-hw * D[0] - lw * D[1] + hw * D[2] + lw * D[3]);
           const float gw = m * (-hh * D[0] + hh * D[1] - lh * D[2] + lh * D[3]);
-          dmask[((static_cast<long long>(pb[np]) * g.dg + dgi) * K + k) * plane + ppos[np]] = gm;
+          const bool add_d = add || dgi * cpg < grp * cing;   // (uniform) a later slice, or the deformable group's later conv group
+          float* dm = dmask + ((static_cast<long long>(pb[np]) * g.dg + dgi) * K + k) * plane + ppos[np];
           float* ob = doff + (static_cast<long long>(pb[np]) * g.dg + dgi) * 2 * K * plane + ppos[np];
-          ob[static_cast<long long>(2 * k) * plane] = gh;
-          ob[static_cast<long long>(2 * k + 1) * plane] = gw;
+          float* oh = ob + static_cast<long long>(2 * k) * plane;
+          float* ow = ob + static_cast<long long>(2 * k + 1) * plane;
+          *dm = add_d ? *dm + gm : gm;
+          *oh = add_d ? *oh + gh : gh;
+          *ow = add_d ? *ow + gw : gw;
         }
       }
       if (more) {
         set_taps(k1);
         int dg2 = dg1 + 1, k2 = k1;
-        if (dg2 == g.dg) { dg2 = 0; ++k2; }
-        if (k2 * g.dg + dg2 < seg_end) load_offsets(k2, dg2);
+        if (dg2 > dgB) { dg2 = dgA; ++k2; }
+        if (k2 * nsd + dg2 - dgA < seg_end) load_offsets(k2, dg2);
       }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -758,6 +785,8 @@ __global__ __launch_bounds__(256) void dcn_col2im_k(DcnGeom g, const float* __re
 // (a thread = one pixel, four adjacent channels: four 16-byte corner loads, as in the forward) and copy the dy tile [16 px][128 co] into
 // LDS, pixel-major; a wave then multiplies its 64 x 64 corner of the tile (A[ci][px] and B[px][co] read one float per lane and MFMA).
 // Loads of step s + 1 are in flight during the MFMAs of step s.  Partial tiles of the pixel ranges are summed in a fixed order (dcn_reduce_k).
+// Conv groups: dW = [K][Cin][Cout/G]; only the (ci tile, co tile) pairs inside one group are launched, tile edges min(128, Cin/G) x
+// min(128, Cout/G) (z tile = (group, co tile, ci tile)).
 constexpr int kDwPitch = 132;   // floats per pixel row of an LDS tile: rows 4 pixels apart land 16 banks apart
 __global__ __launch_bounds__(256, 2) void dcn_bwd_weight_k(DcnGeom g, const float* __restrict__ x, const float* __restrict__ offset,
                                                             const float* __restrict__ mask, const float* __restrict__ dy, int pix_per_block,
@@ -765,15 +794,17 @@ __global__ __launch_bounds__(256, 2) void dcn_bwd_weight_k(DcnGeom g, const floa
   extern __shared__ __attribute__((aligned(16))) float lds[];   // 2 buffers x (col tile 16 x 132 + dy tile 16 x 132)
   constexpr int TILE = 16 * kDwPitch, BUF = 2 * TILE;
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), r = lane & 15, gq = lane >> 4;
-  const int K = g.kh * g.kw, cpg = g.Cin / g.dg, plane = g.Ho * g.Wo;
-  const int ci_tiles = static_cast<int>((g.Cin + 127) / 128);
+  const int K = g.kh * g.kw, cpg = g.Cin / g.dg, plane = g.Ho * g.Wo, cing = g.Cin / g.G, coutg = g.Cout / g.G;
+  const int ci_tiles = static_cast<int>((cing + 127) / 128), co_tiles = static_cast<int>((coutg + 127) / 128);
   // one grid dimension, decoded XCD-major: the kh*kw taps (and channel tiles) of one pixel range run on ONE XCD and share its x and dy
   // lines in that L2 (in launch order they went to all eight: 1 131 MB of L2 fills for 144 MB of x + dy at [4,128,200,176])
   long long lp;
   int zt;
   xcd_tile(n_ztiles, lp, zt);
   const int k = static_cast<int>(lp % K), split = static_cast<int>(lp / K);
-  const int ci0 = (zt % ci_tiles) * 128, co0 = (zt / ci_tiles) * 128;
+  const int grp = zt / (ci_tiles * co_tiles), zg = zt - grp * (ci_tiles * co_tiles);
+  const int ci0 = grp * cing + (zg % ci_tiles) * 128, co0 = (zg / ci_tiles) * 128, ci_end = grp * cing + cing;   // co0: column of the group
+  const float* dyg = dy + grp * coutg;
   const long long npix = static_cast<long long>(g.B) * plane;
   const long long p_begin = static_cast<long long>(split) * pix_per_block, p_end = min(p_begin + pix_per_block, npix);
   // staging role: pixel tid >> 4 of the step, channel quads (tid & 15) and (tid & 15) + 16
@@ -783,7 +814,7 @@ __global__ __launch_bounds__(256, 2) void dcn_bwd_weight_k(DcnGeom g, const floa
   float wq[2][4], mk[2];
   float roh[2], row_[2], rom[2];
   unsigned off0[4] = {0u, 0u, 0u, 0u};
-  const bool one_group = cpg % 128 == 0;   // the 128 input channels of the tile belong to one deformable group: one sampling position per pixel
+  const bool one_group = cpg % 128 == 0 && cing % 128 == 0;   // the tile's 128 input channels belong to one deformable group: one sampling position per pixel
   auto load_offsets = [&](long long p) {   // raw offsets / mask of pixel p for this thread's two channel quads
     const bool ok = p < p_end;
     const long long pp = ok ? p : p_begin;
@@ -806,7 +837,7 @@ __global__ __launch_bounds__(256, 2) void dcn_bwd_weight_k(DcnGeom g, const floa
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       const int ci = ci0 + 64 * h + 4 * cq;
-      const bool cok = ok && ci < g.Cin;
+      const bool cok = ok && ci < ci_end;
       if (h == 1 && one_group) {   // (uniform) both channel quads sample at the same position: the second one is 64 channels further
 #pragma unroll
         for (int q = 0; q < 4; ++q) { raw[1][q] = ldx4(reinterpret_cast<const char*>(x) + 256, off0[q]); wq[1][q] = wq[0][q]; }
@@ -822,7 +853,7 @@ __global__ __launch_bounds__(256, 2) void dcn_bwd_weight_k(DcnGeom g, const floa
       }
       const int co = co0 + 64 * h + 4 * cq;
       f32x4 v = f32x4{0.f, 0.f, 0.f, 0.f};
-      if (ok && co < g.Cout) v = *reinterpret_cast<const f32x4*>(dy + pp * g.Cout + co);   // Cout % 4 == 0
+      if (ok && co < coutg) v = *reinterpret_cast<const f32x4*>(dyg + pp * g.Cout + co);   // Cout / G % 4 == 0
       dyv[h] = v;
     }
   };
@@ -879,17 +910,17 @@ __global__ __launch_bounds__(256, 2) void dcn_bwd_weight_k(DcnGeom g, const floa
     __syncthreads();
   }
   // acc[a][c][e] = dW[k][ci0 + (wi*4 + a)*16 + 4 gq + e][co0 + (wj*4 + c)*16 + r]
-  float* out = partial + (static_cast<long long>(split) * K + k) * g.Cin * g.Cout;
+  float* out = partial + (static_cast<long long>(split) * K + k) * g.Cin * coutg;
 #pragma unroll
   for (int a = 0; a < 4; ++a)
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       const int ci = ci0 + (wi * 4 + a) * 16 + 4 * gq + e;
-      if (ci >= g.Cin) continue;
+      if (ci >= ci_end) continue;
 #pragma unroll
       for (int c = 0; c < 4; ++c) {
         const int co = co0 + (wj * 4 + c) * 16 + r;
-        if (co < g.Cout) out[static_cast<long long>(ci) * g.Cout + co] = acc[a][c][e];
+        if (co < coutg) out[static_cast<long long>(ci) * coutg + co] = acc[a][c][e];
       }
     }
 }
@@ -900,7 +931,20 @@ static int dcn_check(const DcnGeom& g) {
                FV2P_EINVAL, "dcn: bad geometry");
   FV2P_REQUIRE(g.Cin % g.dg == 0 && (g.Cin / g.dg) % 16 == 0, FV2P_ELIMIT,
                "dcn: channels per deformable group (%d/%d) must be a multiple of 16", g.Cin, g.dg);
-  FV2P_REQUIRE(g.Cout <= 256, FV2P_ELIMIT, "dcn: more than 256 output channels per launch (split on the host)");
+  FV2P_REQUIRE(g.Cout <= 256, FV2P_ELIMIT, "dcn: more than 256 output channels (fv2p_dcn_*_grouped take any)");
+  return 0;
+}
+
+// the *_grouped entry points: any Cout, conv groups; the channels of a conv group and of a deformable group in multiples of 16
+static int dcn_check_grouped(const DcnGeom& g) {
+  FV2P_REQUIRE(g.B >= 0 && g.H >= 1 && g.W >= 1 && g.Cin >= 1 && g.Cout >= 1 && g.kh >= 1 && g.kw >= 1 && g.sh >= 1 && g.sw >= 1 &&
+                   g.dh >= 1 && g.dw >= 1 && g.dg >= 1 && g.G >= 1 && g.Ho >= 1 && g.Wo >= 1,
+               FV2P_EINVAL, "dcn: bad geometry");
+  FV2P_REQUIRE(g.Cin % g.G == 0 && g.Cout % g.G == 0 && g.Cin % g.dg == 0, FV2P_EINVAL,
+               "dcn: groups (%d) must divide Cin (%d) and Cout (%d), deformable groups (%d) must divide Cin", g.G, g.Cin, g.Cout, g.dg);
+  FV2P_REQUIRE((g.Cin / g.G) % 16 == 0 && (g.Cin / g.dg) % 16 == 0, FV2P_ELIMIT,
+               "dcn: channels per conv group (%d) and per deformable group (%d) must be multiples of 16 (zero-pad on the host)",
+               g.Cin / g.G, g.Cin / g.dg);
   return 0;
 }
 
@@ -909,7 +953,7 @@ using namespace fv2p;
 
 #define DCN_GEOM_ARGS int batch, int height, int width, int c_in, int c_out, int h_out, int w_out, int kh, int kw, int sh, int sw, \
                       int ph, int pw, int dh, int dw, int deformable_group
-#define DCN_GEOM_INIT DcnGeom g = {batch, height, width, c_in, c_out, h_out, w_out, kh, kw, sh, sw, ph, pw, dh, dw, deformable_group}
+#define DCN_GEOM_INIT DcnGeom g = {batch, height, width, c_in, c_out, h_out, w_out, kh, kw, sh, sw, ph, pw, dh, dw, deformable_group, 1}
 
 
 static int dcn_cu_count() {
@@ -935,13 +979,14 @@ static bool dcn_forward_tap_inner(const DcnGeom& g) {
 template <int NB>
 static void dcn_fwd_launch(const DcnGeom& g, const float* x, const float* wt_oc, const float* bias, const float* offset, const float* mask,
                            float* y, long long npix, int col_blocks, hipStream_t stream) {
-  const dim3 grid(static_cast<unsigned>(ceil_div(npix, 64) * col_blocks));   // one dimension: (tile, column block) decoded XCD-major in the kernel
+  const int n_sub = g.G * col_blocks;   // (conv group, column block) per pixel tile
+  const dim3 grid(static_cast<unsigned>(ceil_div(npix, 64) * n_sub));   // one dimension: (tile, sub) decoded XCD-major in the kernel
   const size_t lds_tapin = (2 * NB * 256 + 4 * static_cast<size_t>(g.kh) * g.kw * 16 * 8) * sizeof(float);
   static const bool big_ok = hipFuncSetAttribute(reinterpret_cast<const void*>(&dcn_fwd_k<NB, 1, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024) == hipSuccess;
   if (dcn_forward_tap_inner(g) && big_ok && lds_tapin <= 96 * 1024)
-    hipLaunchKernelGGL((dcn_fwd_k<NB, 1, true>), grid, dim3(256), lds_tapin, stream, g, x, wt_oc, bias, offset, mask, y, 0ll, col_blocks);
+    hipLaunchKernelGGL((dcn_fwd_k<NB, 1, true>), grid, dim3(256), lds_tapin, stream, g, x, wt_oc, bias, offset, mask, y, 0ll, n_sub);
   else
-    hipLaunchKernelGGL((dcn_fwd_k<NB, 1>), grid, dim3(256), 2 * NB * 256 * sizeof(float), stream, g, x, wt_oc, bias, offset, mask, y, 0ll, col_blocks);
+    hipLaunchKernelGGL((dcn_fwd_k<NB, 1>), grid, dim3(256), 2 * NB * 256 * sizeof(float), stream, g, x, wt_oc, bias, offset, mask, y, 0ll, n_sub);
 }
 
 // Samples per launch sequence: the kernels address x, the column gradients and the sample lists with 32-bit offsets, so a call is
@@ -977,18 +1022,15 @@ extern "C" int fv2p_dcn_set_colg_cap(int64_t bytes) {
   return 0;
 }
 
-// wt_oc: weight permuted to [kh*kw][Cout][Cin] (input channels contiguous: what the LDS-DMA of the forward kernel fetches 16 bytes at a time)
-extern "C" int fv2p_dcn_forward(const float* x_nhwc, const float* wt_oc, const float* bias, const float* offset, const float* mask,
-                                DCN_GEOM_ARGS, float* y_nhwc, fv2p_stream_t stream_) {
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
-  DCN_GEOM_INIT;
-  if (int rc = dcn_check(g)) return rc;
+// wt_oc: weight permuted to [kh*kw][Cout][Cin/G] (input channels contiguous: what the LDS-DMA of the forward kernel fetches 16 bytes at a time)
+static int dcn_forward_run(const DcnGeom& g, const float* x_nhwc, const float* wt_oc, const float* bias, const float* offset, const float* mask,
+                           float* y_nhwc, hipStream_t stream) {
   if (static_cast<long long>(g.B) * g.Ho * g.Wo == 0) return 0;
   FV2P_REQUIRE(x_nhwc && wt_oc && offset && mask && y_nhwc, FV2P_EINVAL, "dcn_forward: null pointer");
   const int bs = dcn_chunk_samples(g, false);
   FV2P_REQUIRE(bs >= 1, FV2P_ELIMIT, "dcn_forward: one sample's input is above 4 GiB");
   const long long K = static_cast<long long>(g.kh) * g.kw, pix = static_cast<long long>(g.Ho) * g.Wo;
-  const int nb_all = static_cast<int>(ceil_div(g.Cout, 16));
+  const int nb_all = static_cast<int>(ceil_div(g.Cout / g.G, 16));   // 16-column blocks of one conv group
   for (int s0 = 0; s0 < g.B; s0 += bs) {
     DcnGeom gc = g;
     gc.B = std::min(bs, g.B - s0);
@@ -999,9 +1041,9 @@ extern "C" int fv2p_dcn_forward(const float* x_nhwc, const float* wt_oc, const f
     float* yc = y_nhwc + static_cast<long long>(s0) * pix * g.Cout;
     // A workgroup computes 64 pixels x 16*NB columns (32-pixel wave tiles measured 3 - 8 % slower: half the waves per SIMD).  Per-pixel
     // arithmetic does not depend on the plan, so results are identical for every batch size.  256 columns go to one workgroup unless the
-    // map is too small to fill the chip: then two column halves, each gathering for itself.
+    // map is too small to fill the chip: then two column halves, each gathering for itself.  Wider groups: column blocks of 256.
     int nb = nb_all <= 4 ? 4 : (nb_all <= 8 ? 8 : 16);
-    if (nb == 16 && ceil_div(npix, 64) < 2 * dcn_cu_count()) nb = 8;
+    if (nb == 16 && ceil_div(npix, 64) * g.G < 2 * dcn_cu_count()) nb = 8;
     if (const char* force = FV2P_DEV_ENV("FV2P_DCN_FWD_NB")) {   // development: only the instantiated tiles, anything else is ignored
       const int f = atoi(force);
       if (f == 4 || f == 8 || f == 16) nb = std::max(f, nb_all <= 4 ? 4 : (nb_all <= 8 ? 8 : f));
@@ -1013,6 +1055,21 @@ extern "C" int fv2p_dcn_forward(const float* x_nhwc, const float* wt_oc, const f
   }
   FV2P_LAUNCH_CHECK();
   return 0;
+}
+
+extern "C" int fv2p_dcn_forward(const float* x_nhwc, const float* wt_oc, const float* bias, const float* offset, const float* mask,
+                                DCN_GEOM_ARGS, float* y_nhwc, fv2p_stream_t stream_) {
+  DCN_GEOM_INIT;
+  if (int rc = dcn_check(g)) return rc;
+  return dcn_forward_run(g, x_nhwc, wt_oc, bias, offset, mask, y_nhwc, static_cast<hipStream_t>(stream_));
+}
+
+extern "C" int fv2p_dcn_forward_grouped(const float* x_nhwc, const float* wt_oc, const float* bias, const float* offset, const float* mask,
+                                        DCN_GEOM_ARGS, int group, float* y_nhwc, fv2p_stream_t stream_) {
+  DCN_GEOM_INIT;
+  g.G = group;
+  if (int rc = dcn_check_grouped(g)) return rc;
+  return dcn_forward_run(g, x_nhwc, wt_oc, bias, offset, mask, y_nhwc, static_cast<hipStream_t>(stream_));
 }
 
 // ---- backward: workspace carving shared by the size query and the call
@@ -1029,9 +1086,9 @@ static DcnBwdPlan dcn_bwd_plan(const DcnGeom& g) {
   p.npix = static_cast<long long>(g.B) * g.Ho * g.Wo;
   p.nkeys = static_cast<long long>(g.B) * g.dg * (g.H + 1) * (g.W + 1);
   p.max_entries = p.npix * g.dg * K;
-  p.ci_tiles = static_cast<int>(ceil_div(g.Cin, 128));
-  p.co_tiles = static_cast<int>(ceil_div(g.Cout, 128));
-  const long long cols = static_cast<long long>(K) * p.ci_tiles * p.co_tiles;
+  p.ci_tiles = static_cast<int>(ceil_div(g.Cin / g.G, 128));    // per conv group
+  p.co_tiles = static_cast<int>(ceil_div(g.Cout / g.G, 128));
+  const long long cols = static_cast<long long>(K) * g.G * p.ci_tiles * p.co_tiles;
   long long s = (kDwBlocksPerCu * dcn_cu_count()) / cols;   // one resident round of workgroups
   const long long smax = ceil_div(p.npix > 0 ? p.npix : 1, 64);
   if (s > smax) s = smax;
@@ -1054,15 +1111,13 @@ static void dcn_bwd_carve(C& c, const DcnGeom& g, const DcnBwdPlan& p, float** c
   entries->lh = c.template take<float>(static_cast<size_t>(p.max_entries));
   entries->lw = c.template take<float>(static_cast<size_t>(p.max_entries));
   *scan_ws = c.template take<char>(scan_ws_bytes(p.nkeys));
-  *partial = c.template take<float>(static_cast<size_t>(p.splits_cap) * K * g.Cin * g.Cout);
+  *partial = c.template take<float>(static_cast<size_t>(p.splits_cap) * K * g.Cin * (g.Cout / g.G));
 }
 struct SizerC : Sizer {
   template <typename T> T* take(size_t n) { Sizer::take<T>(n); return nullptr; }
 };
 
-extern "C" size_t fv2p_dcn_backward_ws_bytes(int batch, int height, int width, int h_out, int w_out, int c_in, int c_out, int kh, int kw,
-                                             int deformable_group) {
-  DcnGeom g = {batch, height, width, c_in, c_out, h_out, w_out, kh, kw, 1, 1, 0, 0, 1, 1, deformable_group > 0 ? deformable_group : 1};
+static size_t dcn_backward_ws(DcnGeom g) {
   g.B = std::max(1, std::min(g.B, dcn_chunk_samples(g, true)));   // the workspace of one chunk serves every chunk
   const DcnBwdPlan p = dcn_bwd_plan(g);
   SizerC s;
@@ -1071,35 +1126,42 @@ extern "C" size_t fv2p_dcn_backward_ws_bytes(int batch, int height, int width, i
   return s.bytes();
 }
 
-template <int JO, int MC>
-static void dcn_col_launch(const DcnGeom& g, const float* x, const float* wt, const float* offset, const float* mask, const float* dy, float* colg,
-                           float* doff, float* dmask, long long npix, int seg_split, hipStream_t stream) {
-  hipLaunchKernelGGL((dcn_bwd_col_k<JO, 1, MC>), dim3(static_cast<unsigned>(ceil_div(npix, 64) * seg_split)), dim3(256),
-                     2 * MC * JO * 256 * sizeof(float), stream, g, x, wt, offset, mask, dy, colg, doff, dmask, 0ll, seg_split);
+extern "C" size_t fv2p_dcn_backward_ws_bytes(int batch, int height, int width, int h_out, int w_out, int c_in, int c_out, int kh, int kw,
+                                             int deformable_group) {
+  return dcn_backward_ws({batch, height, width, c_in, c_out, h_out, w_out, kh, kw, 1, 1, 0, 0, 1, 1, deformable_group > 0 ? deformable_group : 1, 1});
 }
 
-// dx_nhwc, doffset, dmask, dwt are fully written (nothing to zero).  wt = [kh*kw][Cin][Cout].
-extern "C" int fv2p_dcn_backward(const float* x_nhwc, const float* wt, const float* offset, const float* mask, const float* dy_nhwc,
-                                 DCN_GEOM_ARGS, float* dx_nhwc, float* doffset, float* dmask, float* dwt, void* ws, size_t ws_bytes,
-                                 fv2p_stream_t stream_) {
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
-  DCN_GEOM_INIT;
-  if (int rc = dcn_check(g)) return rc;
-  FV2P_REQUIRE((g.Cout & 3) == 0, FV2P_ELIMIT, "dcn_backward: output channels must be a multiple of 4 (pad the weight)");
+extern "C" size_t fv2p_dcn_backward_grouped_ws_bytes(int batch, int height, int width, int h_out, int w_out, int c_in, int c_out, int kh,
+                                                     int kw, int deformable_group, int group) {
+  const int G = group > 0 && c_in % group == 0 && c_out % group == 0 ? group : 1;
+  return dcn_backward_ws({batch, height, width, c_in, c_out, h_out, w_out, kh, kw, 1, 1, 0, 0, 1, 1, deformable_group > 0 ? deformable_group : 1, G});
+}
+
+// grid: pixel tiles x ng conv groups (grp0 ..) x n_share shares of a group's segments; output columns [256 slice, 256 slice + 256) of each group
+template <int JO, int MC>
+static void dcn_col_launch(const DcnGeom& g, const float* x, const float* wt, const float* offset, const float* mask, const float* dy, float* colg,
+                           float* doff, float* dmask, long long npix, int seg_split, int grp0, int ng, int slice, hipStream_t stream) {
+  hipLaunchKernelGGL((dcn_bwd_col_k<JO, 1, MC>), dim3(static_cast<unsigned>(ceil_div(npix, 64) * ng * seg_split)), dim3(256),
+                     2 * MC * JO * 256 * sizeof(float), stream, g, x, wt, offset, mask, dy, colg, doff, dmask, 0ll, ng * seg_split, seg_split,
+                     grp0, slice);
+}
+
+// dx_nhwc, doffset, dmask, dwt are fully written (nothing to zero).  wt = [kh*kw][Cin][Cout/G], dwt likewise.
+static int dcn_backward_run(const DcnGeom& g, const float* x_nhwc, const float* wt, const float* offset, const float* mask, const float* dy_nhwc,
+                            float* dx_nhwc, float* doffset, float* dmask, float* dwt, void* ws, size_t ws_bytes, hipStream_t stream) {
   const long long npix = static_cast<long long>(g.B) * g.Ho * g.Wo;
-  const int K = g.kh * g.kw;
+  const int K = g.kh * g.kw, cing = g.Cin / g.G, coutg = g.Cout / g.G;
   FV2P_REQUIRE(dwt, FV2P_EINVAL, "dcn_backward: null dwt");
   const long long nin = static_cast<long long>(g.B) * g.H * g.W;
   if (npix == 0) {
-    FV2P_HIP(hipMemsetAsync(dwt, 0, sizeof(float) * (size_t)K * g.Cin * g.Cout, stream));
+    FV2P_HIP(hipMemsetAsync(dwt, 0, sizeof(float) * (size_t)K * g.Cin * coutg, stream));
     if (nin > 0 && dx_nhwc) FV2P_HIP(hipMemsetAsync(dx_nhwc, 0, sizeof(float) * (size_t)nin * g.Cin, stream));
     return 0;
   }
   FV2P_REQUIRE(x_nhwc && wt && offset && mask && dy_nhwc && dx_nhwc && doffset && dmask, FV2P_EINVAL, "dcn_backward: null pointer");
   const int bs = dcn_chunk_samples(g, true);
   FV2P_REQUIRE(bs >= 1, FV2P_ELIMIT, "dcn_backward: one sample's input, column gradients or sample list is above the 32-bit limits");
-  FV2P_REQUIRE(ws && ws_bytes >= fv2p_dcn_backward_ws_bytes(g.B, g.H, g.W, g.Ho, g.Wo, g.Cin, g.Cout, g.kh, g.kw, g.dg), FV2P_EWORKSPACE,
-               "dcn_backward: workspace too small");
+  FV2P_REQUIRE(ws && ws_bytes >= dcn_backward_ws(g), FV2P_EWORKSPACE, "dcn_backward: workspace too small");
   DcnGeom gmax = g;
   gmax.B = std::min(bs, g.B);
   const DcnBwdPlan pmax = dcn_bwd_plan(gmax);
@@ -1130,22 +1192,31 @@ extern "C" int fv2p_dcn_backward(const float* x_nhwc, const float* wt, const flo
     hipLaunchKernelGGL((dcn_index_k<1>), dim3(iblocks), dim3(256), 0, stream, gc, oc, cursor, entries);
     hipLaunchKernelGGL(dcn_index_sort_long_k, dim3(static_cast<unsigned>(std::min<long long>(1024, ceil_div(p.nkeys, 256)))), dim3(256), 0, stream,
                        cursor, p.nkeys, entries);
-    // 2. column gradients, grad_mask, grad_offset
-    const int jo = static_cast<int>(ceil_div(g.Cout, 16));
-    const bool mc2 = (g.Cin / g.dg) % 32 == 0;
+    // 2. column gradients, grad_mask, grad_offset.  Conv groups whose channels hold whole deformable groups share a launch; otherwise
+    // (a deformable group spans conv groups) the groups run one launch each in ascending order, the later ones adding their share of
+    // grad_offset / grad_mask.  Groups wider than 256 output columns run in slices of 256, in ascending order, each adding to colg
+    // and to grad_offset / grad_mask: fixed-order sums, no float atomics.
+    const int nslices = static_cast<int>(ceil_div(coutg, 256));
+    const int jo = static_cast<int>(ceil_div(std::min(coutg, 256), 16));
+    const bool mc2 = (g.Cin / g.dg) % 32 == 0 && cing % 32 == 0;   // a 32-channel block must not cross a conv group
+    const int ng = cing % (g.Cin / g.dg) == 0 ? g.G : 1;            // conv groups per launch
+    const int segs_g = K * std::max(1, g.dg / g.G);                 // segments of a group (the fewest, when groups launch one at a time)
     // small maps: the (tap, group) segments of a pixel tile go to several workgroups, in equal shares (550 tiles on 256 CUs are two
     // rounds with the second almost empty: [4,256,100,88] 1 327 -> 1 182 us with three shares; at 2 200 tiles shares only cost)
     int seg_split = 1;
-    for (int sp = 1; sp <= K * g.dg; ++sp)
-      if ((K * g.dg) % sp == 0) { seg_split = sp; if (ceil_div(cpix, 64) * sp >= 6 * dcn_cu_count()) break; }
+    for (int sp = 1; sp <= segs_g; ++sp)
+      if (segs_g % sp == 0) { seg_split = sp; if (ceil_div(cpix, 64) * ng * sp >= 6 * dcn_cu_count()) break; }
     if (const char* force = FV2P_DEV_ENV("FV2P_DCN_BWD_SPLIT")) {   // development: a divisor of the segment count or nothing
       const int f = atoi(force);
-      if (f >= 1 && f <= K * g.dg && (K * g.dg) % f == 0) seg_split = f;
+      if (f >= 1 && f <= segs_g && segs_g % f == 0) seg_split = f;
     }
-#define DCN_CJ(JO) do { if (mc2) dcn_col_launch<JO, 2>(gc, xc, wt, oc, mc, dyc, colg, doc, dmc, cpix, seg_split, stream); \
-                        else dcn_col_launch<JO, 1>(gc, xc, wt, oc, mc, dyc, colg, doc, dmc, cpix, seg_split, stream); } while (0)
-    if (jo <= 1) DCN_CJ(1); else if (jo <= 2) DCN_CJ(2); else if (jo <= 4) DCN_CJ(4); else if (jo <= 8) DCN_CJ(8); else DCN_CJ(16);
+    for (int grp0 = 0; grp0 < g.G; grp0 += ng)
+      for (int sl = 0; sl < nslices; ++sl) {
+#define DCN_CJ(JO) do { if (mc2) dcn_col_launch<JO, 2>(gc, xc, wt, oc, mc, dyc, colg, doc, dmc, cpix, seg_split, grp0, ng, sl, stream); \
+                        else dcn_col_launch<JO, 1>(gc, xc, wt, oc, mc, dyc, colg, doc, dmc, cpix, seg_split, grp0, ng, sl, stream); } while (0)
+        if (jo <= 1) DCN_CJ(1); else if (jo <= 2) DCN_CJ(2); else if (jo <= 4) DCN_CJ(4); else if (jo <= 8) DCN_CJ(8); else DCN_CJ(16);
 #undef DCN_CJ
+      }
     // 3. grad_input
     const int cpg = g.Cin / g.dg;
     const long long ntiles = static_cast<long long>(gc.B) * g.dg * ((g.H + 1) / 2) * ((g.W + 3) / 4);
@@ -1154,13 +1225,32 @@ extern "C" int fv2p_dcn_backward(const float* x_nhwc, const float* wt, const flo
     else if (cpg > 64) hipLaunchKernelGGL((dcn_col2im_k<2>), dim3(gblocks), dim3(256), 0, stream, gc, colg, cursor, entries, dxc);
     else hipLaunchKernelGGL((dcn_col2im_k<1>), dim3(gblocks), dim3(256), 0, stream, gc, colg, cursor, entries, dxc);
     // 4. weight gradient: the chunk's pixel splits, added to dwt in ascending chunk order
-    const dim3 wgrid(static_cast<unsigned>(static_cast<long long>(p.splits) * K * p.ci_tiles * p.co_tiles));
+    const dim3 wgrid(static_cast<unsigned>(static_cast<long long>(p.splits) * K * g.G * p.ci_tiles * p.co_tiles));
     hipLaunchKernelGGL(dcn_bwd_weight_k, wgrid, dim3(256), 2 * 2 * 16 * kDwPitch * sizeof(float), stream, gc, xc, oc, mc, dyc,
-                       p.pix_per_block, p.ci_tiles * p.co_tiles, partial);
-    const long long per_chunk = static_cast<long long>(K) * g.Cin * g.Cout;
+                       p.pix_per_block, g.G * p.ci_tiles * p.co_tiles, partial);
+    const long long per_chunk = static_cast<long long>(K) * g.Cin * coutg;
     hipLaunchKernelGGL(dcn_reduce_k, dim3(static_cast<unsigned>(ceil_div(per_chunk, 256))), dim3(256), 0, stream, partial, p.splits, per_chunk, dwt,
                        s0 > 0 ? 1 : 0);
   }
   FV2P_LAUNCH_CHECK();
   return 0;
+}
+
+extern "C" int fv2p_dcn_backward(const float* x_nhwc, const float* wt, const float* offset, const float* mask, const float* dy_nhwc,
+                                 DCN_GEOM_ARGS, float* dx_nhwc, float* doffset, float* dmask, float* dwt, void* ws, size_t ws_bytes,
+                                 fv2p_stream_t stream_) {
+  DCN_GEOM_INIT;
+  if (int rc = dcn_check(g)) return rc;
+  FV2P_REQUIRE((g.Cout & 3) == 0, FV2P_ELIMIT, "dcn_backward: output channels must be a multiple of 4 (pad the weight)");
+  return dcn_backward_run(g, x_nhwc, wt, offset, mask, dy_nhwc, dx_nhwc, doffset, dmask, dwt, ws, ws_bytes, static_cast<hipStream_t>(stream_));
+}
+
+extern "C" int fv2p_dcn_backward_grouped(const float* x_nhwc, const float* wt, const float* offset, const float* mask, const float* dy_nhwc,
+                                         DCN_GEOM_ARGS, int group, float* dx_nhwc, float* doffset, float* dmask, float* dwt, void* ws,
+                                         size_t ws_bytes, fv2p_stream_t stream_) {
+  DCN_GEOM_INIT;
+  g.G = group;
+  if (int rc = dcn_check_grouped(g)) return rc;
+  FV2P_REQUIRE(((g.Cout / g.G) & 3) == 0, FV2P_ELIMIT, "dcn_backward_grouped: output channels per group must be a multiple of 4 (pad the weight)");
+  return dcn_backward_run(g, x_nhwc, wt, offset, mask, dy_nhwc, dx_nhwc, doffset, dmask, dwt, ws, ws_bytes, static_cast<hipStream_t>(stream_));
 }

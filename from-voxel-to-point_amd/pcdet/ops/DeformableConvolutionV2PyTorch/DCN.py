@@ -1,5 +1,11 @@
 """`DCN` — the extension module of the reference's DeformableConvolutionV2PyTorch (src/vision.cpp:6-12) as a Python
-shim over libfv2p_ops: same six function names and positional arguments."""
+shim over libfv2p_ops: same six function names and positional arguments.
+
+Two routes.  groups == 1, Cout <= 256 and Cin / deformable_group a multiple of 16 (every reference config, the MGAF head) reach
+fv2p_dcn_forward / fv2p_dcn_backward as they always did.  Every other geometry the reference accepts (groups > 1, channel tails,
+Cout > 256) reaches fv2p_dcn_*_grouped, with the input channels zero-padded on the host (_tail_pad)."""
+import math
+
 import torch
 
 import fv2p_native as _nat
@@ -15,6 +21,53 @@ def _geom(input, weight, kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w, d
     Ho = (H + 2 * pad_h - (dilation_h * (kernel_h - 1) + 1)) // stride_h + 1
     Wo = (W + 2 * pad_w - (dilation_w * (kernel_w - 1) + 1)) // stride_w + 1
     return (B, H, W, C, Cout, Ho, Wo, kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w, deformable_group)
+
+
+def _plain(input, weight, group, deformable_group):
+    """The geometries fv2p_dcn_forward / fv2p_dcn_backward take: today's route, unchanged."""
+    C, Cout = input.shape[1], weight.shape[0]
+    return group == 1 and Cout <= 256 and deformable_group >= 1 and C % deformable_group == 0 and (C // deformable_group) % 16 == 0
+
+
+def _geom_grouped(input, weight, kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w, group, deformable_group):
+    """-> (geometry of the padded problem, (s, sp)): the reference's checks (modulated_deform_conv_cuda.cu:40-58), then the channel
+    padding.  The input channels split at every conv-group and every deformable-group boundary into pieces s = gcd(Cin/G, Cin/dg)
+    wide; each piece is zero-padded to sp = s rounded up to 16, so that both kinds of group hold a multiple of 16 channels."""
+    _nat.require_cuda(input)
+    B, C, H, W = input.shape
+    Cout = weight.shape[0]
+    if group < 1 or C % group or Cout % group:
+        raise ValueError(f"DCN: groups {group} must divide input channels {C} and output channels {Cout}")
+    if deformable_group < 1 or C % deformable_group:
+        raise ValueError(f"DCN: deformable groups {deformable_group} must divide input channels {C}")
+    if tuple(weight.shape[1:]) != (C // group, kernel_h, kernel_w):
+        raise ValueError(f"DCN: input / kernel shape mismatch: weight {tuple(weight.shape)} for {C} input channels in {group} groups")
+    Ho = (H + 2 * pad_h - (dilation_h * (kernel_h - 1) + 1)) // stride_h + 1
+    Wo = (W + 2 * pad_w - (dilation_w * (kernel_w - 1) + 1)) // stride_w + 1
+    s = math.gcd(C // group, C // deformable_group)
+    sp = -(-s // 16) * 16
+    g = (B, H, W, C // s * sp, Cout, Ho, Wo, kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w, deformable_group)
+    return g, (s, sp)
+
+
+def _tail_pad(t, tail):
+    """Last axis in pieces of s channels, each zero-padded to sp.  The cost is the padding: a piece of 1 channel is moved and
+    multiplied 16 times over (sp / s), in x, the weight and the column gradients alike."""
+    s, sp = tail
+    if s == sp:
+        return t
+    lead = t.shape[:-1]
+    return torch.nn.functional.pad(t.reshape(*lead, t.shape[-1] // s, s), (0, sp - s)).reshape(*lead, t.shape[-1] // s * sp)
+
+
+def _tail_unpad(t, tail):
+    """Inverse of _tail_pad: the real channels of every piece, as a contiguous copy (with s = 1 the reshape alone would be a view with
+    a channel stride of sp, which the library's transposes must not see)."""
+    s, sp = tail
+    if s == sp:
+        return t
+    lead = t.shape[:-1]
+    return t.reshape(*lead, t.shape[-1] // sp, sp)[..., :s].reshape(*lead, t.shape[-1] // sp * s).contiguous()
 
 
 def _channels_last(t):
@@ -70,11 +123,70 @@ def _forward_nhwc(x, weight, bias, offset, mask, g):
     return y
 
 
+def _grouped_forward(input, weight, bias, offset, mask, kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w,
+                     group, deformable_group):
+    """fv2p_dcn_forward_grouped on the padded channels: x [B,H,W,Cin'] and wt_oc [K][Cout][Cin'/G] with zero channels in every piece."""
+    g, tail = _geom_grouped(input, weight, kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w, group,
+                            deformable_group)
+    B, H, W, Cp, Cout, Ho, Wo = g[:7]
+    x = _tail_pad(_to_nhwc(input), tail)
+    wt_oc = _tail_pad(weight.float().permute(2, 3, 0, 1), tail).reshape(kernel_h * kernel_w, Cout, Cp // group).contiguous()
+    y = torch.empty((B * Ho * Wo, Cout), dtype=torch.float32, device=x.device)
+    with _nat.device_guard(x.device):
+        _nat.call("fv2p_dcn_forward_grouped", x, wt_oc, bias.float().contiguous() if bias is not None else None,
+                  offset.float().contiguous(), mask.float().contiguous(), *g, group, y, _nat.stream())
+    y = y.view(B, Ho, Wo, Cout)
+    if _channels_last(input):
+        return y.permute(0, 3, 1, 2).to(input.dtype)
+    return _to_nchw(y).to(input.dtype)
+
+
+def _grouped_backward(input, weight, offset, mask, grad_output, kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w, dilation_h,
+                      dilation_w, group, deformable_group):
+    """fv2p_dcn_backward_grouped on the padded channels; each group's output columns padded to a multiple of 4 with zeros (in dy and
+    the weight), grad_input and grad_weight sliced back to the real channels."""
+    g, tail = _geom_grouped(input, weight, kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w, group,
+                            deformable_group)
+    B, H, W, Cp, Cout, Ho, Wo = g[:7]
+    K, C, dev = kernel_h * kernel_w, input.shape[1], input.device
+    cing, coutg = Cp // group, Cout // group
+    cop = coutg + (-coutg) % 4      # the kernels read output channels four at a time
+    x = _tail_pad(_to_nhwc(input), tail)
+    dy0 = _to_nhwc(grad_output).view(B * Ho * Wo, Cout)
+    dy = dy0
+    if cop != coutg:
+        dy = torch.nn.functional.pad(dy0.view(-1, group, coutg), (0, cop - coutg)).reshape(-1, group * cop)
+    # [Cout, Cin/G, kh, kw] -> [K][Cin'][Cout'/G]: wt[k][g*cing + c][o] = W[g*coutg + o, c, k]
+    w = _tail_pad(weight.float().permute(0, 2, 3, 1), tail)                        # [Cout, kh, kw, cing]
+    wz = w.new_zeros((group, cop, kernel_h, kernel_w, cing))
+    wz[:, :coutg] = w.reshape(group, coutg, kernel_h, kernel_w, cing)
+    wt = wz.permute(2, 3, 0, 4, 1).reshape(K, Cp, cop).contiguous()
+    g = g[:4] + (group * cop,) + g[5:]
+    dx = torch.empty_like(x)
+    doff = torch.empty_like(offset, dtype=torch.float32).contiguous()
+    dmask = torch.empty_like(mask, dtype=torch.float32).contiguous()
+    dwt = torch.empty((K, Cp, cop), dtype=torch.float32, device=dev)
+    with _nat.device_guard(dev):
+        nb = _nat.lib().fv2p_dcn_backward_grouped_ws_bytes(B, H, W, Ho, Wo, Cp, group * cop, kernel_h, kernel_w, deformable_group, group)
+        ws = _nat.workspace(nb, dev)
+        _nat.call("fv2p_dcn_backward_grouped", x, wt, offset.float().contiguous(), mask.float().contiguous(), dy, *g, group, dx, doff,
+                  dmask, dwt, ws, ws.numel(), _nat.stream())
+    dx = _tail_unpad(dx, tail)
+    grad_input = dx.permute(0, 3, 1, 2) if _channels_last(input) else _to_nchw(dx)
+    dw = _tail_unpad(dwt.view(K, group, cing, cop)[..., :coutg].transpose(2, 3), tail)     # [K, G, coutg, Cin/G]
+    grad_weight = dw.permute(1, 2, 3, 0).reshape(Cout, C // group, kernel_h, kernel_w).contiguous()
+    grad_bias = dy0.sum(dim=0)
+    return [grad_input, doff, dmask, grad_weight, grad_bias]
+
+
 def modulated_deform_conv_forward(input, weight, bias, offset, mask, kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w,
                                   dilation_h, dilation_w, group, deformable_group, im2col_step):
     """-> output [B, Cout, Ho, Wo] (contiguous NCHW, as modulated_deform_conv_cuda.cu:118). im2col_step is accepted and
     irrelevant: the forward has no columns buffer to chunk.  A channels-last `input` is taken as it is and the output is channels-last
     too (the kernels' own layout: no copy on either side); grad_input follows the input's format likewise."""
+    if not _plain(input, weight, group, deformable_group):
+        return _grouped_forward(input, weight, bias, offset, mask, kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w, dilation_h,
+                                dilation_w, group, deformable_group)
     g = _geom(input, weight, kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w, group, deformable_group)
     B, H, W, C, Cout, Ho, Wo = g[:7]
     x = _to_nhwc(input)
@@ -88,6 +200,9 @@ def modulated_deform_conv_backward(input, weight, bias, offset, mask, grad_outpu
                                    pad_w, dilation_h, dilation_w, group, deformable_group, im2col_step):
     """-> [grad_input, grad_offset, grad_mask, grad_weight, grad_bias] (modulated_deform_conv_cuda.cu:127-280).
     No float atomics anywhere: the five gradients are bit-identical from run to run (include/fv2p_ops.h, A13)."""
+    if not _plain(input, weight, group, deformable_group):
+        return _grouped_backward(input, weight, offset, mask, grad_output, kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w,
+                                 dilation_h, dilation_w, group, deformable_group)
     g = _geom(input, weight, kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w, group, deformable_group)
     B, H, W, C, Cout, Ho, Wo = g[:7]
     dev = input.device

@@ -564,7 +564,8 @@ int fv2p_sa_grid_bwd_gather(const float* per_point, const float* per_centre, con
  *   x_nhwc [B,H,W,Cin], y_nhwc / dy_nhwc [B*Ho*Wo, Cout]; the weight [Cout,Cin,kh,kw] arrives permuted: forward takes
  *   wt_oc = [kh*kw][Cout][Cin] (input channels contiguous), backward wt = [kh*kw][Cin][Cout] (output channels contiguous);
  *   offset [B, dg*2*kh*kw, Ho, Wo] ((2k, 2k+1) = (dh, dw)), mask [B, dg*kh*kw, Ho, Wo] — reference layouts.
- * groups == 1; Cin / deformable_group must be a multiple of 16; Cout <= 256 (backward: Cout a multiple of 4).
+ * fv2p_dcn_forward / fv2p_dcn_backward: groups == 1, Cin / deformable_group a multiple of 16, Cout <= 256 (backward: Cout a
+ * multiple of 4).  The *_grouped entry points further below take conv groups and any Cout.
  * backward (modulated_deform_conv_cuda.cu:127-280): dx_nhwc, doffset, dmask, dwt are FULLY written, nothing to zero
  * (dwt [kh*kw][Cin][Cout]; the bias gradient is a plain column sum done by the caller).  No float atomics: the column
  * gradients go through the workspace ([B*Ho*Wo][kh*kw][Cin], the reference's `columns`), every input pixel then sums the
@@ -593,6 +594,32 @@ int fv2p_dcn_backward(const float* x_nhwc, const float* wt, const float* offset,
                       int w_out, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw,
                       int deformable_group, float* dx_nhwc, float* doffset, float* dmask, float* dwt, void* ws,
                       size_t ws_bytes, fv2p_stream_t stream);
+/* The same operator with `group` conv groups (modulated_deform_conv_cuda.cu:62-113, 171-280: the reference's per-group GEMMs) and any
+ * number of output channels.  Input channel c belongs to conv group c / (Cin/G) and samples with the offsets and mask of deformable
+ * group c / (Cin/dg); output channel o belongs to conv group o / (Cout/G) and sums over its group's Cin/G input channels only.
+ * G divides Cin and Cout, dg divides Cin; Cin/G and Cin/dg must be multiples of 16 (FV2P_ELIMIT otherwise): the caller zero-pads the
+ * input channels, in pieces gcd(Cin/G, Cin/dg) wide each padded to a multiple of 16, in x and in the weight's input-channel axis -
+ * zero channels add nothing to y, doffset or dmask (pcdet DCN.py does this and slices dx and dwt back).  With group = 1 and a geometry
+ * fv2p_dcn_forward / _backward take, both launch the same kernels with the same grids and give the same bits.
+ *   forward:  wt_oc = [kh*kw][Cout][Cin/G]: wt_oc[k][o][c] = W[o, c, k] (c within o's group).  Any Cout / G: a workgroup's columns
+ *             stay inside one group, in column blocks of at most 256.
+ *   backward: wt = [kh*kw][Cin][Cout/G]: wt[k][g*Cin/G + c][o] = W[g*Cout/G + o, c, k]; dwt has the same layout.  Cout / G must be a
+ *             multiple of 4 (the caller pads each group's output columns with zeros, in dy and wt, and slices dwt back).  Column
+ *             gradients of groups wider than 256 output channels are formed in slices of 256 added in ascending order, and a
+ *             deformable group that spans conv groups gets its grad_offset / grad_mask from the groups in ascending order: still no
+ *             float atomics, still bit-identical from run to run.  Batch chunking and the workspace rule are those above;
+ *             fv2p_dcn_backward_grouped_ws_bytes is the workspace of one chunk. */
+int fv2p_dcn_forward_grouped(const float* x_nhwc, const float* wt_oc, const float* bias, const float* offset,
+                             const float* mask, int batch, int height, int width, int c_in, int c_out, int h_out,
+                             int w_out, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw,
+                             int deformable_group, int group, float* y_nhwc, fv2p_stream_t stream);
+size_t fv2p_dcn_backward_grouped_ws_bytes(int batch, int height, int width, int h_out, int w_out, int c_in, int c_out, int kh,
+                                          int kw, int deformable_group, int group);
+int fv2p_dcn_backward_grouped(const float* x_nhwc, const float* wt, const float* offset, const float* mask,
+                              const float* dy_nhwc, int batch, int height, int width, int c_in, int c_out, int h_out,
+                              int w_out, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw,
+                              int deformable_group, int group, float* dx_nhwc, float* doffset, float* dmask, float* dwt,
+                              void* ws, size_t ws_bytes, fv2p_stream_t stream);
 
 /* Layout copies around the NHWC entry points above (and fv2p_bev_interp_*): in [batch][rows][cols] -> out [batch][cols][rows],
  * e.g. NCHW -> NHWC with rows = C, cols = H*W.  The reference does the same copies with at::permute + contiguous
