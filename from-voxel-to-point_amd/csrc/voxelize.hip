@@ -170,9 +170,316 @@ static void vox_carve(C& c, int64_t n, int max_voxels, VoxWs* w) {
   }
 }
 
+// ---- stacked batch: B clouds of any sizes in one point buffer, one pass -------------------------------------------------------------
+// The same four steps with a sample index in every key:
+//   1. insert   : key = sample * grid volume + flat cell, payload = index into the STACKED buffer, so atomicMin still keeps the
+//                 first point of every (sample, voxel); a thread finds its sample by a binary search over the B + 1 offsets;
+//   2. order    : one scan of the first-flags over the whole buffer (n + 1 entries: rank[n] = all firsts); a first point's rank
+//                 inside its sample is rank[i] - rank[off[b]];
+//   3. cut-off  : per sample, the first-flagged point of rank max_voxels (found by a binary search over the monotone rank[]: the
+//                 smallest i of the sample with rank[i + 1] > rank[off[b]] + max_voxels); the sample's later points are dropped,
+//                 other samples are unaffected.  Sample b keeps M_b = min(distinct voxels, max_voxels) voxels, its output rows
+//                 start at base[b] = sum of M_a over a < b (vox_stack_bases: one workgroup, the only per-sample pass);
+//   4. slots    : kept points are keyed (output row, stacked point index) and sorted on the row bits, then filled as before.
+// The number of launches does not depend on B (the offsets reach the device as kernel arguments, 256 per launch).
+constexpr int kOffChunk = 256;
+struct VoxOffsets { int v[kOffChunk]; };
+
+__global__ __launch_bounds__(kOffChunk) void vox_stack_offsets(VoxOffsets o, int first, int count, int* __restrict__ off) {
+  const int t = threadIdx.x;
+  int v = 0;
+  // a compile-time index per lane keeps the argument block in scalar registers (a run-time index would copy it to scratch)
+#pragma unroll
+  for (int j = 0; j < kOffChunk; ++j) v = (j == t) ? o.v[j] : v;
+  if (t < count) off[first + t] = v;
+}
+
+// sample of stacked row i: the b with off[b] <= i < off[b + 1] (empty samples have off[b] == off[b + 1] and own no row)
+__device__ __forceinline__ int vox_sample_of(const int* __restrict__ off, int batch, int i) {
+  int lo = 0, hi = batch;   // invariant: off[lo] <= i < off[hi]
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (off[mid] <= i) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+
+__global__ void vox_stack_insert(const float* __restrict__ pts, int n, int ndim, VoxGeom g, const int* __restrict__ off, int batch,
+                                 uint64_t* __restrict__ table, uint32_t mask, int* __restrict__ slot) {
+  const int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float* p = pts + i * ndim;
+  int c[3];
+  bool ok = true;
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    // fp32 subtract then fp32 divide then floor, as voxel_generator.py:188 (no reciprocal, no fma)
+    float f = floorf((p[j] - g.lo[j]) / g.vs[j]);
+    if (!(f >= 0.0f) || f >= static_cast<float>(g.grid[j])) ok = false;  // NaN -> dropped
+    c[j] = static_cast<int>(f);
+  }
+  if (!ok) { slot[i] = -1; return; }
+  const uint64_t vol = static_cast<uint64_t>(g.grid[0]) * g.grid[1] * g.grid[2];
+  const uint64_t key = static_cast<uint64_t>(vox_sample_of(off, batch, static_cast<int>(i))) * vol +
+                       (static_cast<uint64_t>(c[2]) * g.grid[1] + c[1]) * g.grid[0] + c[0];
+  const uint64_t word = slot_pack(key, static_cast<uint32_t>(i));
+  uint32_t h = hash_u64(key, mask);
+  while (true) {
+    unsigned long long old = atomicCAS(reinterpret_cast<unsigned long long*>(&table[h]),
+                                       static_cast<unsigned long long>(kEmptySlot),
+                                       static_cast<unsigned long long>(word));
+    if (old == kEmptySlot) break;
+    if (slot_key(old) == key) {
+      atomicMin(reinterpret_cast<unsigned long long*>(&table[h]), static_cast<unsigned long long>(word));
+      break;
+    }
+    h = (h + 1) & mask;
+  }
+  slot[i] = static_cast<int>(h);
+}
+
+// first[] has n + 1 entries; the last one is 0, so that the scan leaves the number of first points in rank[n]
+__global__ void vox_stack_mark_first(int n, const uint64_t* __restrict__ table, const int* __restrict__ slot, int* __restrict__ first) {
+  const int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (i > n) return;
+  int f = 0;
+  if (i < n) {
+    const int s = slot[i];
+    f = (s >= 0 && slot_val(table[s]) == static_cast<uint32_t>(i)) ? 1 : 0;
+  }
+  first[i] = f;
+}
+
+// One workgroup.  base[b] = first output row of sample b (base[batch] = rows produced), cut[b] = the stacked index at which sample b's
+// scan breaks (off[b + 1] when it does not), voxel_cnt[b] = M_b.
+__global__ __launch_bounds__(256) void vox_stack_bases(const int* __restrict__ off, int batch, const int* __restrict__ rank, int max_voxels,
+                                                       int* __restrict__ base, int* __restrict__ cut, int* __restrict__ voxel_cnt) {
+  __shared__ int lds_wave[4];
+  int carry = 0;
+  for (int c0 = 0; c0 < batch; c0 += 256) {
+    const int b = c0 + static_cast<int>(threadIdx.x);
+    int m = 0;
+    if (b < batch) {
+      const int lo = off[b], hi = off[b + 1];
+      const int r0 = rank[lo], d = rank[hi] - r0;
+      m = d < max_voxels ? d : max_voxels;
+      int stop = hi;
+      if (d > max_voxels) {
+        // smallest i in [lo, hi) with rank[i + 1] > r0 + max_voxels: the first point of the sample's voxel number max_voxels
+        int a = lo, z = hi - 1;   // rank[z + 1] = r0 + d > r0 + max_voxels holds at z = hi - 1
+        while (a < z) {
+          const int mid = (a + z) >> 1;
+          if (rank[mid + 1] > r0 + max_voxels) z = mid; else a = mid + 1;
+        }
+        stop = a;
+      }
+      cut[b] = stop;
+      voxel_cnt[b] = m;
+    }
+    int tot;
+    const int ex = block_excl_scan_256(m, lds_wave, &tot);
+    if (b < batch) base[b] = carry + ex;
+    carry += tot;
+  }
+  if (threadIdx.x == 0) base[batch] = carry;
+}
+
+// Assign and words in one pass: every kept point gets its (output row, stacked index) word and counts into its row; the first point
+// of a voxel also writes the row's (b, z, y, x).
+__global__ void vox_stack_words(int n, const uint64_t* __restrict__ table, const int* __restrict__ slot, const int* __restrict__ rank,
+                                const int* __restrict__ off, int batch, const int* __restrict__ base, const int* __restrict__ cut,
+                                VoxGeom g, uint64_t* __restrict__ words, int* __restrict__ count, int* __restrict__ coords) {
+  const int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int s = slot[i];
+  uint64_t w = ~0ull;
+  if (s >= 0) {
+    const int b = vox_sample_of(off, batch, static_cast<int>(i));
+    if (i < cut[b]) {
+      const uint64_t tw = table[s];
+      const int f = static_cast<int>(slot_val(tw));
+      const int row = base[b] + rank[f] - rank[off[b]];   // f <= i < cut[b], so the rank inside the sample is below max_voxels
+      atomicAdd(&count[row], 1);
+      w = slot_pack(static_cast<uint64_t>(row), static_cast<uint32_t>(i));
+      if (f == static_cast<int>(i)) {
+        const uint64_t vol = static_cast<uint64_t>(g.grid[0]) * g.grid[1] * g.grid[2];
+        uint64_t key = slot_key(tw) - static_cast<uint64_t>(b) * vol;
+        const int x = static_cast<int>(key % g.grid[0]); key /= g.grid[0];
+        const int y = static_cast<int>(key % g.grid[1]);
+        const int z = static_cast<int>(key / g.grid[1]);
+        int* q = coords + static_cast<int64_t>(row) * 4;
+        q[0] = b; q[1] = z; q[2] = y; q[3] = x;
+      }
+    }
+  }
+  words[i] = w;
+}
+
+// MeanVFE straight from the sorted words: the sum over a row's first min(points, max_points) slots in slot order / max(that, 1) — the
+// arithmetic of voxel_mean_collate (sparse_aux.hip), whose further slots are zero padding that leaves the fp32 sum as it is.
+__global__ __launch_bounds__(256) void vox_stack_mean(int64_t total, const float* __restrict__ pts, int ndim, const uint64_t* __restrict__ words,
+                                                      const int* __restrict__ start, const int* __restrict__ rows, int max_points,
+                                                      float* __restrict__ feats) {
+  const int64_t t = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
+  if (t >= total) return;
+  const int v = static_cast<int>(t / ndim), d = static_cast<int>(t % ndim);
+  if (v >= *rows) return;
+  const int p0 = start[v], cnt = start[v + 1] - p0;
+  const int k = cnt < max_points ? cnt : max_points;
+  float s = 0.f;
+  for (int p = 0; p < k; ++p) s += pts[static_cast<int64_t>(slot_val(words[p0 + p])) * ndim + d];
+  feats[t] = s / static_cast<float>(k < 1 ? 1 : k);
+}
+
+struct VoxStackWs {
+  uint64_t* table; uint32_t cap;
+  int* off; int* base; int* cut;
+  int* slot; int* rank; int* count; int* scalars;
+  uint64_t* words; uint64_t* tmp;
+  char* aux; size_t aux_bytes;
+};
+
+// rows_cap: an upper bound of the output rows (the call's own sum of min(n_b, max_voxels), or min(n, B * max_voxels) for the query)
+template <typename C>
+static void vox_stack_carve(C& c, int64_t n, int batch, int64_t rows_cap, VoxStackWs* w) {
+  const uint32_t cap = next_pow2(static_cast<uint64_t>(n > 512 ? n : 512) * 2);
+  size_t aux = radix_sort_ws_bytes(n);
+  const size_t a2 = scan_ws_bytes((n > rows_cap ? n : rows_cap) + 1);
+  if (a2 > aux) aux = a2;
+  VoxStackWs l;
+  l.cap = cap;
+  l.table = c.template take<uint64_t>(cap);
+  l.off = c.template take<int>(static_cast<size_t>(batch) + 1);
+  l.base = c.template take<int>(static_cast<size_t>(batch) + 1);
+  l.cut = c.template take<int>(static_cast<size_t>(batch));
+  l.slot = c.template take<int>(n);
+  l.rank = c.template take<int>(n + 1);
+  l.count = c.template take<int>(rows_cap + 2);
+  l.scalars = c.template take<int>(8);
+  l.words = c.template take<uint64_t>(n);
+  l.tmp = c.template take<uint64_t>(n);
+  l.aux = c.template take<char>(aux);
+  l.aux_bytes = aux;
+  if constexpr (std::is_same<C, Carver>::value) *w = l;
+}
+
+struct CountOnly {   // vox_stack_carve over a Sizer: take() returns nothing to point at
+  Sizer s;
+  template <typename T>
+  T* take(size_t n) { s.take<T>(n); return nullptr; }
+};
+
+static int64_t vox_stack_rows_bound(int64_t n, int batch, int max_voxels) {
+  const int64_t bm = static_cast<int64_t>(batch) * max_voxels;
+  return n < bm ? n : bm;
+}
+
+// Both forms: mean -> MeanVFE features, else padded (voxels, num_points).
+static int vox_stack_run(bool mean, const float* points, int64_t n, int ndim, int batch, const int* counts, const float voxel_size[3],
+                         const float range_lo[3], const int grid[3], int max_points, int max_voxels, float* voxels, float* feats,
+                         int* coords, int* num_points, int* voxel_cnt, void* ws, size_t ws_bytes, hipStream_t stream, const char* who) {
+  FV2P_REQUIRE(n >= 0 && ndim >= 3 && max_points >= 1 && max_voxels >= 1 && batch >= 1, FV2P_EINVAL,
+               "%s: bad sizes n=%lld ndim=%d batch=%d max_points=%d max_voxels=%d", who, (long long)n, ndim, batch, max_points, max_voxels);
+  FV2P_REQUIRE(counts && voxel_cnt && (points || n == 0), FV2P_EINVAL, "%s: null pointer", who);
+  FV2P_REQUIRE(grid[0] > 0 && grid[1] > 0 && grid[2] > 0, FV2P_EINVAL, "%s: empty grid", who);
+  FV2P_REQUIRE(n <= kMaxRows, FV2P_ELIMIT, "%s: more than %lld points", who, (long long)kMaxRows);
+  const int64_t vol = static_cast<int64_t>(grid[0]) * grid[1] * grid[2];
+  FV2P_REQUIRE(vol <= kMaxKey / batch, FV2P_ELIMIT, "%s: batch * grid volume exceeds 2^40", who);
+  FV2P_REQUIRE(static_cast<int64_t>(batch) * max_voxels <= kMaxRows, FV2P_ELIMIT, "%s: batch * max_voxels too large", who);
+  int64_t sum = 0, rows_cap = 0;
+  for (int b = 0; b < batch; ++b) {
+    FV2P_REQUIRE(counts[b] >= 0, FV2P_EINVAL, "%s: negative point count of sample %d", who, b);
+    sum += counts[b];
+    rows_cap += counts[b] < max_voxels ? counts[b] : max_voxels;
+  }
+  FV2P_REQUIRE(sum == n, FV2P_EINVAL, "%s: the counts sum to %lld, not to the %lld points", who, (long long)sum, (long long)n);
+  FV2P_REQUIRE(rows_cap == 0 || (coords && (mean ? feats != nullptr : voxels && num_points)), FV2P_EINVAL, "%s: null output pointer", who);
+  FillJobs fill;
+  if (mean) fill.add(feats, sizeof(float) * static_cast<size_t>(rows_cap) * ndim, 0u);
+  else {
+    fill.add(voxels, sizeof(float) * static_cast<size_t>(rows_cap) * max_points * ndim, 0u);
+    fill.add(num_points, sizeof(int) * static_cast<size_t>(rows_cap), 0u);
+  }
+  fill.add(coords, sizeof(int) * 4 * static_cast<size_t>(rows_cap), 0u);
+  fill.add(voxel_cnt, sizeof(int) * static_cast<size_t>(batch), 0u);
+  if (n == 0) return multi_fill(fill, stream);
+  FV2P_REQUIRE(ws && ws_bytes >= fv2p_points_to_voxel_stack_ws_bytes(n, batch, max_voxels), FV2P_EWORKSPACE, "%s: workspace too small", who);
+  Carver c(ws, ws_bytes);
+  VoxStackWs w;
+  vox_stack_carve(c, n, batch, rows_cap, &w);
+  VoxGeom g;
+  for (int j = 0; j < 3; ++j) { g.vs[j] = voxel_size[j]; g.lo[j] = range_lo[j]; g.grid[j] = grid[j]; }
+
+  fill.add(w.table, sizeof(uint64_t) * w.cap, 0xFFFFFFFFu);
+  fill.add(w.count, sizeof(int) * static_cast<size_t>(rows_cap + 2), 0u);
+  if (int rc = multi_fill(fill, stream)) return rc;
+  {
+    VoxOffsets o;
+    int64_t run = 0;   // off[k] = points before sample k, k = 0 .. batch
+    for (int first = 0; first <= batch; first += kOffChunk) {
+      const int cnt = batch + 1 - first < kOffChunk ? batch + 1 - first : kOffChunk;
+      for (int t = 0; t < kOffChunk; ++t) {
+        o.v[t] = static_cast<int>(run);
+        if (t < cnt && first + t < batch) run += counts[first + t];
+      }
+      hipLaunchKernelGGL(vox_stack_offsets, dim3(1), dim3(kOffChunk), 0, stream, o, first, cnt, w.off);
+    }
+  }
+  const int T = 256;
+  const int ni = static_cast<int>(n);
+  const dim3 gridN(static_cast<unsigned>(ceil_div(n, T))), gridN1(static_cast<unsigned>(ceil_div(n + 1, T)));
+  hipLaunchKernelGGL(vox_stack_insert, gridN, dim3(T), 0, stream, points, ni, ndim, g, w.off, batch, w.table, w.cap - 1, w.slot);
+  hipLaunchKernelGGL(vox_stack_mark_first, gridN1, dim3(T), 0, stream, ni, w.table, w.slot, w.rank);
+  int rc = exclusive_scan_i32(w.rank, w.rank, n + 1, nullptr, w.aux, w.aux_bytes, stream);
+  if (rc) return rc;
+  hipLaunchKernelGGL(vox_stack_bases, dim3(1), dim3(256), 0, stream, w.off, batch, w.rank, max_voxels, w.base, w.cut, voxel_cnt);
+  hipLaunchKernelGGL(vox_stack_words, gridN, dim3(T), 0, stream, ni, w.table, w.slot, w.rank, w.off, batch, w.base, w.cut, g, w.words,
+                     w.count, coords);
+  // rows < rows_cap <= B * max_voxels, so the all-ones word of a dropped point sorts behind every kept one
+  const int vb = bits_for(static_cast<uint64_t>(rows_cap));
+  rc = radix_sort_u64(w.words, w.tmp, n, kValBits, kValBits + vb, w.aux, w.aux_bytes, stream);
+  if (rc) return rc;
+  rc = exclusive_scan_i32(w.count, w.count, rows_cap + 1, w.scalars + 2, w.aux, w.aux_bytes, stream);
+  if (rc) return rc;
+  if (mean) {
+    const int64_t total = rows_cap * ndim;
+    hipLaunchKernelGGL(vox_stack_mean, dim3(static_cast<unsigned>(ceil_div(total, 256))), dim3(256), 0, stream, total, points, ndim,
+                       w.words, w.count, w.base + batch, max_points, feats);
+  } else {
+    hipLaunchKernelGGL(vox_fill, gridN, dim3(T), 0, stream, n, points, ndim, w.words, w.count, w.scalars, max_points, voxels, num_points);
+  }
+  FV2P_LAUNCH_CHECK();
+  return 0;
+}
+
 }  // namespace fv2p
 
 using namespace fv2p;
+
+extern "C" size_t fv2p_points_to_voxel_stack_ws_bytes(int64_t n_total, int batch, int max_voxels) {
+  if (n_total < 1) n_total = 1;
+  if (batch < 1) batch = 1;
+  if (max_voxels < 1) max_voxels = 1;
+  CountOnly s;
+  vox_stack_carve(s, n_total, batch, vox_stack_rows_bound(n_total, batch, max_voxels), static_cast<VoxStackWs*>(nullptr));
+  return s.s.bytes();
+}
+
+extern "C" int fv2p_points_to_voxel_stack(const float* points, int64_t n_total, int ndim, int batch, const int* counts,
+                                          const float voxel_size[3], const float range_lo[3], const int grid[3], int max_points,
+                                          int max_voxels, float* voxels, int* coords, int* num_points, int* voxel_cnt, void* ws,
+                                          size_t ws_bytes, fv2p_stream_t stream) {
+  return vox_stack_run(false, points, n_total, ndim, batch, counts, voxel_size, range_lo, grid, max_points, max_voxels, voxels, nullptr, coords,
+                       num_points, voxel_cnt, ws, ws_bytes, static_cast<hipStream_t>(stream), "points_to_voxel_stack");
+}
+
+extern "C" int fv2p_points_to_voxel_stack_mean(const float* points, int64_t n_total, int ndim, int batch, const int* counts,
+                                               const float voxel_size[3], const float range_lo[3], const int grid[3], int max_points,
+                                               int max_voxels, float* features, int* coords, int* voxel_cnt, void* ws, size_t ws_bytes,
+                                               fv2p_stream_t stream) {
+  return vox_stack_run(true, points, n_total, ndim, batch, counts, voxel_size, range_lo, grid, max_points, max_voxels, nullptr, features, coords,
+                       nullptr, voxel_cnt, ws, ws_bytes, static_cast<hipStream_t>(stream), "points_to_voxel_stack_mean");
+}
 
 extern "C" size_t fv2p_points_to_voxel_ws_bytes(int64_t n_points, int max_voxels) {
   if (n_points < 1) n_points = 1;

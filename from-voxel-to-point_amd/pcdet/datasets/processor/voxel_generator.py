@@ -7,7 +7,8 @@ and the same first-come / max_voxels-break semantics.  Two entry points of the n
 WHERE THE DATA IS, never by what happens to be available:
 
 * CUDA tensor in -> CUDA tensors out: the hashed HIP voxeliser `fv2p_points_to_voxel` (csrc/voxelize.hip); this is the path of the
-  models and of bench.py (`points_to_voxel_batch`).
+  models and of bench.py (`points_to_voxel_batch`).  `points_to_voxel_stack` voxelises a whole stacked batch of unequal clouds in
+  one pass of `fv2p_points_to_voxel_stack` (same tensors as `points_to_voxel_batch`, bit for bit).
 * numpy in -> numpy out: `fv2p_points_to_voxel_host`, the reference's own call site - `VoxelGenerator.generate` runs on numpy arrays in
   forked DataLoader worker processes (data_processor.py:43-81), where HIP cannot be initialised.  Like `points_in_boxes_cpu` and
   `boxes_bev_iou_cpu` it is the reference's CPU entry point served by the library (host pointers, the calling thread, no HIP call;
@@ -125,6 +126,79 @@ def points_to_voxel_batch(points_list, voxel_size, coors_range, max_points=35, m
     c = torch.cat([torch.nn.functional.pad(o[1][:m], (1, 0), value=b) for b, (o, m) in enumerate(zip(outs, counts))])
     k = torch.cat([o[2][:m] for o, m in zip(outs, counts)])
     return v, c, k
+
+
+def _stack_counts(points, batch_cnt):
+    """-> the counts as a contiguous CPU int32 tensor, after every check that needs no library call."""
+    if not torch.is_tensor(points) or points.dim() != 2:
+        raise ValueError("points_to_voxel_stack: points must be a (N_total, ndim) tensor")
+    if not points.is_cuda:
+        raise _nat.Fv2pError("points_to_voxel_stack: fv2p ops run on the GPU only: got a CPU tensor (numpy clouds go to points_to_voxel)")
+    if points.dtype != torch.float32:
+        raise TypeError(f"points_to_voxel_stack: points must be float32, got {points.dtype}")
+    if points.shape[1] < 3:
+        raise ValueError(f"points_to_voxel_stack: points must be [N, ndim >= 3], got ndim = {points.shape[1]}")
+    if torch.is_tensor(batch_cnt):
+        if batch_cnt.dim() != 1 or batch_cnt.dtype not in (torch.int32, torch.int64):
+            raise ValueError("points_to_voxel_stack: batch_cnt must be a 1-D int tensor")
+        cnt = torch.tensor(batch_cnt.tolist(), dtype=torch.int64)   # a CUDA tensor pays its one synchronisation here
+    else:
+        cnt = torch.tensor([int(c) for c in batch_cnt], dtype=torch.int64)
+    if cnt.numel() == 0:
+        raise ValueError("points_to_voxel_stack: an empty batch (batch_cnt has no entry)")
+    if int(cnt.min()) < 0:
+        raise ValueError(f"points_to_voxel_stack: negative point count in {cnt.tolist()}")
+    if int(cnt.sum()) != points.shape[0]:
+        raise ValueError(f"points_to_voxel_stack: counts {cnt.tolist()} do not sum to the {points.shape[0]} rows of points")
+    return cnt.to(torch.int32).contiguous()
+
+
+def points_to_voxel_stack(points, batch_cnt, voxel_size, coors_range, max_points=35, max_voxels=20000, mean_vfe=False):
+    """Voxelises a stacked batch in one pass (`fv2p_points_to_voxel_stack`, csrc/voxelize.hip): points is a CUDA float32
+    [N1 + N2 + ..., ndim] tensor, the clouds one after the other, batch_cnt their point counts (a list, or a CPU / CUDA int tensor; empty
+    clouds are legal).  Returns what points_to_voxel_batch returns, bit for bit - voxels [sum M, max_points, ndim], coords [sum M, 4]
+    (batch, z, y, x) int32, num_points [sum M] int32, or (features [sum M, ndim], coords) with mean_vfe=True - with a number of kernel
+    launches that does not depend on the batch size, no side stream, no per-cloud collate and one host read (the voxel counts)."""
+    cnt_host = _stack_counts(points, batch_cnt)   # stays alive until the call has returned: the library reads it through its address
+    if int(max_points) < 1 or int(max_voxels) < 1:
+        raise ValueError("points_to_voxel_stack: max_points and max_voxels must be at least 1")
+    points = points.contiguous()
+    voxel_size = np.asarray(voxel_size, dtype=np.float32)
+    coors_range = np.asarray(coors_range, dtype=np.float32)
+    grid = _grid_size(voxel_size, coors_range)
+    (n, ndim), b, dev = points.shape, cnt_host.numel(), points.device
+    max_points, max_voxels = int(max_points), int(max_voxels)
+    rows = int(torch.clamp(cnt_host, max=max_voxels).sum())
+    coords = torch.empty((rows, 4), dtype=torch.int32, device=dev)
+    voxel_cnt = torch.empty((b,), dtype=torch.int32, device=dev)
+    geom = (voxel_size.tolist(), coors_range[:3].tolist(), [int(g) for g in grid], max_points, max_voxels)
+    with _nat.device_guard(dev):
+        ws = _nat.workspace(_nat.lib().fv2p_points_to_voxel_stack_ws_bytes(n, b, max_voxels), dev)
+        if mean_vfe:
+            feats = torch.empty((rows, ndim), dtype=torch.float32, device=dev)
+            _nat.call("fv2p_points_to_voxel_stack_mean", points, n, ndim, b, cnt_host, *geom, feats, coords, voxel_cnt, ws, ws.numel(),
+                      _nat.stream())
+        else:
+            voxels = torch.empty((rows, max_points, ndim), dtype=torch.float32, device=dev)
+            num = torch.empty((rows,), dtype=torch.int32, device=dev)
+            _nat.call("fv2p_points_to_voxel_stack", points, n, ndim, b, cnt_host, *geom, voxels, coords, num, voxel_cnt, ws, ws.numel(),
+                      _nat.stream())
+    m = int(voxel_cnt.cpu().sum())   # the one synchronisation of the batch
+    if mean_vfe:
+        return feats[:m], coords[:m]
+    return voxels[:m], coords[:m], num[:m]
+
+
+def points_to_voxel_stack_list(points_list, voxel_size, coors_range, max_points=35, max_voxels=20000, mean_vfe=False):
+    """points_to_voxel_stack for a list of per-cloud CUDA tensors [N_b, ndim]: one concatenation, then the stacked call."""
+    points_list = list(points_list)
+    if not points_list:
+        raise ValueError("points_to_voxel_stack_list: an empty batch")
+    for p in points_list:
+        if not torch.is_tensor(p) or p.dim() != 2 or p.shape[1] != points_list[0].shape[1]:
+            raise ValueError("points_to_voxel_stack_list: every cloud must be a [N, ndim] tensor of the same ndim")
+    stacked = points_list[0] if len(points_list) == 1 else torch.cat(points_list)
+    return points_to_voxel_stack(stacked, [p.shape[0] for p in points_list], voxel_size, coors_range, max_points, max_voxels, mean_vfe)
 
 
 def points_to_voxel(points, voxel_size, coors_range, max_points=35, reverse_index=True, max_voxels=20000):

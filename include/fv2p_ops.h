@@ -58,6 +58,33 @@ int fv2p_points_to_voxel(const float* points, int64_t n_points, int ndim, const 
                          float* voxels, int* coors, int* num_points_per_voxel, int* num_voxels,
                          void* ws, size_t ws_bytes, fv2p_stream_t stream);
 
+/* Stacked form of A1: B clouds of any sizes, concatenated into one point buffer, voxelised in one pass whose number of kernel
+ * launches does not depend on B, written as the collated batch (pcdet/datasets/dataset.py:152-183).  Every sample is voxelised as
+ * fv2p_points_to_voxel voxelises it alone (first-come order, the break at its own voxel number max_voxels+1); empty clouds are legal.
+ *   points      [n_total, ndim] f32 (device), the clouds one after the other
+ *   counts      [batch] i32 HOST: points per cloud, >= 0, summing to n_total
+ *   voxel_size, range_lo, grid: as above;  max_voxels applies to every sample on its own
+ *   rows_cap    = sum over b of min(counts[b], max_voxels): the rows the caller allocates
+ *   voxels      [rows_cap, max_points, ndim] f32;  num_points [rows_cap] i32
+ *   coords      [rows_cap, 4] i32 (b, z, y, x);  sample b's M_b = min(distinct voxels of b, max_voxels) rows start at sum of M_a, a < b
+ *   voxel_cnt   [batch] device i32: M_b
+ *   _mean       features [rows_cap, ndim] f32 instead of voxels / num_points: the sum over a row's point slots in slot order divided
+ *               by max(num_points, 1) — MeanVFE (pcdet/models/backbones_3d/vfe/mean_vfe.py:14-31), bit for bit
+ *               fv2p_voxel_mean_collate — without the padded tensor
+ * All outputs are fully written by the call (rows past the produced total are zero); n_total == 0 zero-fills and returns.
+ * Limits (FV2P_ELIMIT): n_total <= 2^24 - 2, batch * grid volume <= 2^40 - 2, batch * max_voxels <= 2^24 - 2; batch >= 1.
+ * No host synchronisation: the counts travel as kernel arguments.
+ */
+size_t fv2p_points_to_voxel_stack_ws_bytes(int64_t n_total, int batch, int max_voxels);
+int fv2p_points_to_voxel_stack(const float* points, int64_t n_total, int ndim, int batch, const int* counts,
+                               const float voxel_size[3], const float range_lo[3], const int grid[3], int max_points,
+                               int max_voxels, float* voxels, int* coords, int* num_points, int* voxel_cnt,
+                               void* ws, size_t ws_bytes, fv2p_stream_t stream);
+int fv2p_points_to_voxel_stack_mean(const float* points, int64_t n_total, int ndim, int batch, const int* counts,
+                                    const float voxel_size[3], const float range_lo[3], const int grid[3], int max_points,
+                                    int max_voxels, float* features, int* coords, int* voxel_cnt,
+                                    void* ws, size_t ws_bytes, fv2p_stream_t stream);
+
 /* Host entry point of A1: the reference calls VoxelGenerator.generate on numpy arrays inside forked DataLoader workers
  * (pcdet/datasets/processor/data_processor.py:43-81 -> voxel_generator.py:75-207), where HIP cannot be initialised.  All
  * pointers are HOST pointers, the scan runs on the calling thread and makes no HIP call; same outputs as above (voxels,

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Per-kernel timings on one GPU (events on the launch stream). Not part of the product or of bench.py; used to
-iterate on kernel variants:  python tools/microbench.py [conv|dcn|fps|nms|all]"""
+iterate on kernel variants:  python tools/microbench.py [conv|dcn|fps|voxel|nms|all]"""
 import os
 import sys
 import time
@@ -311,6 +311,59 @@ def fps():
         print(f"three_nn 16384 x {v}: {t:8.1f} us ({8.0 * 16384 * v / t / 1e6:6.2f} TFLOP/s)")
 
 
+VOXEL_CASES = [("KITTI B=1", "kitti", (16384,), 16000), ("KITTI B=3", "kitti", (16384,) * 3, 16000),
+               ("KITTI B=4 unequal", "kitti", (14000, 16384, 9000, 18500), 16000), ("KITTI B=8", "kitti", (16384,) * 8, 16000),
+               ("Waymo B=2", "waymo", (180000, 180000), 150000)]
+
+
+def _voxel_case(kind, counts, dev):
+    from fv2p_harness import synth
+    gen, vs, rng = (synth.waymo_like_cloud, synth.WAYMO_VOXEL, synth.WAYMO_RANGE) if kind == "waymo" else (synth.lidar_cloud, synth.KITTI_VOXEL, synth.KITTI_RANGE)
+    host = [gen(100 + i, n) for i, n in enumerate(counts)]
+    return [torch.from_numpy(p).to(dev) for p in host], torch.from_numpy(np.concatenate(host)).to(dev), vs, rng
+
+
+def voxel():
+    """A batch through the voxeliser, padded and MeanVFE forms (max_points 5; every figure includes the one host read of the voxel counts):
+    "serial": points_to_voxel_batch(cloud_streams=False), the per-cloud calls one after the other on one stream; "streams": the same with one
+    stream per cloud; "stack": one points_to_voxel_stack call on the concatenated clouds; "largest": the largest cloud alone through
+    points_to_voxel_gpu.  On a tree without the stacked call (the parent commit, for the comparison) the other routes are timed."""
+    from pcdet.datasets.processor import voxel_generator as vg
+    dev = torch.device("cuda:0")
+    stack = getattr(vg, "points_to_voxel_stack", None)
+    for name, kind, counts, mv in VOXEL_CASES:
+        clouds, stacked, vs, rng = _voxel_case(kind, counts, dev)
+        largest = clouds[int(np.argmax(counts))]
+        t_one = timeit(lambda: vg.points_to_voxel_gpu(largest, vs, rng, 5, True, mv), reps=20, warm=3)
+        for mean in (False, True):
+            if stack is not None:
+                assert all(torch.equal(a, b) for a, b in zip(stack(stacked, list(counts), vs, rng, 5, mv, mean_vfe=mean),
+                                                             vg.points_to_voxel_batch(clouds, vs, rng, 5, mv, mean_vfe=mean)))
+            t_ser = timeit(lambda: vg.points_to_voxel_batch(clouds, vs, rng, 5, mv, mean_vfe=mean, cloud_streams=False), reps=20, warm=3)
+            t_str = timeit(lambda: vg.points_to_voxel_batch(clouds, vs, rng, 5, mv, mean_vfe=mean, cloud_streams=True), reps=20, warm=3)
+            line = f"voxel {name} N={counts} {'mean  ' if mean else 'padded'}: serial {t_ser:8.1f} us   streams {t_str:8.1f} us"
+            if stack is not None:
+                t_stk = timeit(lambda: stack(stacked, list(counts), vs, rng, 5, mv, mean_vfe=mean), reps=20, warm=3)
+                line += f"   stack {t_stk:8.1f} us   stack / serial {t_stk / t_ser:5.3f}   stack / streams {t_stk / t_str:5.3f}   stack / largest {t_stk / t_one:5.3f}"
+            print(line + f"   largest alone {t_one:8.1f} us")
+
+
+def voxelcount():
+    """Four calls of one route and nothing else on the GPU, to count kernel launches per call under a kernel trace:
+    python tools/microbench.py voxelcount serial|stack <case number of VOXEL_CASES> padded|mean"""
+    from pcdet.datasets.processor import voxel_generator as vg
+    route, case, form = sys.argv[2], int(sys.argv[3]), sys.argv[4]
+    name, kind, counts, mv = VOXEL_CASES[case]
+    clouds, stacked, vs, rng = _voxel_case(kind, counts, torch.device("cuda:0"))
+    for _ in range(4):
+        if route == "stack":
+            vg.points_to_voxel_stack(stacked, list(counts), vs, rng, 5, mv, mean_vfe=form == "mean")
+        else:
+            vg.points_to_voxel_batch(clouds, vs, rng, 5, mv, mean_vfe=form == "mean", cloud_streams=False)
+    torch.cuda.synchronize()
+    print(f"voxelcount {route} {name} {form}: 4 calls")
+
+
 def fpstrace():
     """Where a round of the streaming sampler goes: clocks per phase and wave (fv2p_fps_set_trace)."""
     import fv2p_native
@@ -586,7 +639,10 @@ if __name__ == "__main__":
     if which == "convone":
         conv(only=20)
         sys.exit(0)
-    for name, fn in (("conv", conv), ("dcn", dcn), ("fps", fps), ("fpstrace", fpstrace), ("nn", nn), ("nms", nms), ("sa", sa), ("bn", bn), ("bev", bev), ("oproof", oproof)):
+    if which == "voxelcount":
+        voxelcount()
+        sys.exit(0)
+    for name, fn in (("conv", conv), ("dcn", dcn), ("fps", fps), ("voxel", voxel), ("fpstrace", fpstrace), ("nn", nn), ("nms", nms), ("sa", sa), ("bn", bn), ("bev", bev), ("oproof", oproof)):
         if which in (name, "all"):
             print(f"==== {name}")
             fn()
