@@ -62,11 +62,11 @@ struct Carver {
   }
   bool ok() const { return off <= cap; }
 };
-// Same arithmetic without a buffer, for *_ws_bytes queries.
+// Same arithmetic without a buffer, for *_ws_bytes queries (take() has nothing to point at: a layout written once serves both).
 struct Sizer {
   size_t off = 0;
   template <typename T>
-  void take(size_t n) { off = align_up(off) + n * sizeof(T); }
+  T* take(size_t n) { off = align_up(off) + n * sizeof(T); return nullptr; }
   size_t bytes() const { return align_up(off); }
 };
 

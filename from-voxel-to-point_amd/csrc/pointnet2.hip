@@ -292,11 +292,10 @@ __device__ __forceinline__ uint64_t wave_max_u64(uint64_t v) {  // wave-uniform 
 // bs = 2^floor(log2 n) (<= 1024) reference threads, thread t owns points t, t+bs, ...; a thread keeps its FIRST
 // maximum (strict >); the block reduction's tie-break is reproduced below.  REG: points + running distances live
 // in registers (n <= THREADS*PPT).
-// Every sampler below is a BODY (a sample's base row `row`, its point count n and reference block bs, its output row b) behind two
-// kernels: the equal-size one, b clouds of n points each (row = b * n, n and bs launch-wide kernel arguments: the (B, N, 3) entry point),
-// and the stacked one (*_stack_k), where a workgroup reads its sample's own count from `cnt`, derives bs and the row from it and leaves
-// at once when the sample belongs to another form of the sampler (fv2p_furthest_point_sampling_stack launches each form present once
-// over all samples).
+// Every sampler below is ONE kernel templated on the call's LAYOUT, which tells a workgroup where its sample lies: FpsEqual, b clouds of
+// n points each (row = b * n, n and bs launch-wide kernel arguments: the (B, N, 3) entry point), or FpsStack, where a workgroup reads its
+// sample's own count from `cnt`, derives bs and the row from it and leaves at once when the sample belongs to another form of the
+// sampler (fps_run launches each form present once over all samples).
 __host__ __device__ inline int fps_ref_block(int n) {  // opt_n_threads (cuda_utils.h:10-14): 2^floor(log2 n) clamped to [1, 1024]
   int p = 1;
   while (p * 2 <= n && p < 1024) p *= 2;
@@ -313,42 +312,67 @@ __host__ __device__ inline int fps_family(int n, int m, bool bucketed) {
   return n > kFpsMaxSlots * kFpsWaves * 64 ? kFpsStream : kFpsWave;
 }
 __host__ __device__ inline int fps_stream_rows(int n) { return (n + kStreamBucket - 1) / kStreamBucket * kStreamBucket; }
-struct FpsStack {
-  const int* cnt;   // points per sample (device)
-  int bucketed;     // fps_family's third argument, decided by the host for the whole call
-};
 __device__ __forceinline__ int fps_wave_sum(int v) {   // wave-uniform sum over the 64 lanes (all active)
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return __builtin_amdgcn_readfirstlane(v);
 }
-// rows of the stacked arrays in front of sample `smp` (the call's total fits an int); every wave computes it for itself
-__device__ __forceinline__ int fps_stack_row(const int* __restrict__ cnt, int smp) {
-  int v = 0;
-  for (int i = static_cast<int>(threadIdx.x & 63); i < smp; i += 64) v += cnt[i];
-  return fps_wave_sum(v);
-}
-// the same for the streaming form's padded copies: only its own samples have one, each rounded up to whole buckets
-__device__ __forceinline__ int64_t fps_stack_stream_row(const FpsStack& a, int m, int smp) {
-  int v = 0;   // in buckets: the padded total may pass 2^31 rows, its bucket count cannot
-  for (int i = static_cast<int>(threadIdx.x & 63); i < smp; i += 64) {
-    const int c = a.cnt[i];
-    if (fps_family(c, m, a.bucketed) == kFpsStream) v += fps_stream_rows(c) / kStreamBucket;
+// The two layouts.  count(smp): the sample's points; block(n): its reference block; row(smp): its first row of the point arrays;
+// stream_row(m, smp): its first row of the streaming form's padded copies; has(n, m, fam): whether a launch of form `fam` samples it.
+struct FpsEqual {   // plain kernel-argument arithmetic: no loads, no reduction; the host launches the one form of the call
+  static constexpr bool kTrace = true;   // the phase-clock hook (fv2p_fps_set_trace) is instantiated for this layout only
+  int n, bs;
+  __device__ __forceinline__ int count(int) const { return n; }
+  __device__ __forceinline__ int block(int) const { return bs; }
+  __device__ __forceinline__ int64_t row(int smp) const { return static_cast<int64_t>(smp) * n; }
+  __device__ __forceinline__ int64_t stream_row(int, int smp) const { return static_cast<int64_t>(smp) * fps_stream_rows(n); }
+  __device__ __forceinline__ bool has(int, int, int) const { return true; }
+};
+struct FpsStack {
+  static constexpr bool kTrace = false;
+  const int* cnt;   // points per sample (device)
+  int bucketed;     // fps_family's third argument, decided by the host for the whole call
+  __device__ __forceinline__ int count(int smp) const { return __builtin_amdgcn_readfirstlane(cnt[smp]); }
+  __device__ __forceinline__ int block(int n) const { return fps_ref_block(n); }
+  // rows of the stacked arrays in front of sample `smp` (the call's total fits an int); every wave computes it for itself
+  __device__ __forceinline__ int64_t row(int smp) const {
+    int v = 0;
+    for (int i = static_cast<int>(threadIdx.x & 63); i < smp; i += 64) v += cnt[i];
+    return fps_wave_sum(v);
   }
-  return static_cast<int64_t>(fps_wave_sum(v)) * kStreamBucket;
-}
-// sample `smp` of a stacked launch of form `fam`: false when it belongs to another form
-__device__ __forceinline__ bool fps_stack_sample(const FpsStack& a, int m, int fam, int smp, int& n, int& bs, int64_t& row) {
-  n = __builtin_amdgcn_readfirstlane(a.cnt[smp]);
-  if (n < 1 || fps_family(n, m, a.bucketed) != fam) return false;
-  bs = fps_ref_block(n);
-  row = fps_stack_row(a.cnt, smp);
+  // the same for the streaming form's padded copies: only its own samples have one, each rounded up to whole buckets
+  __device__ __forceinline__ int64_t stream_row(int m, int smp) const {
+    int v = 0;   // in buckets: the padded total may pass 2^31 rows, its bucket count cannot
+    for (int i = static_cast<int>(threadIdx.x & 63); i < smp; i += 64) {
+      const int c = cnt[i];
+      if (fps_family(c, m, bucketed) == kFpsStream) v += fps_stream_rows(c) / kStreamBucket;
+    }
+    return static_cast<int64_t>(fps_wave_sum(v)) * kStreamBucket;
+  }
+  __device__ __forceinline__ bool has(int n, int m, int fam) const { return n >= 1 && fps_family(n, m, bucketed) == fam; }
+};
+// sample `smp` of a launch of form `fam`: false when it belongs to another form
+template <class L>
+__device__ __forceinline__ bool fps_sample(const L& lay, int m, int fam, int smp, int& n, int& bs, int64_t& row) {
+  n = lay.count(smp);
+  if (!lay.has(n, m, fam)) return false;
+  bs = lay.block(n);
+  row = lay.row(smp);
   return true;
 }
 
-template <int THREADS, int PPT, bool REG>
-__device__ __forceinline__ void fps_body(int b, int64_t row, int n, int m, int bs, const float* __restrict__ dataset, float* __restrict__ temp,
-                                         int* __restrict__ idxs) {
+// (the text sits in the kernel itself: behind a body function the equal-size 16-slot instance was allocated differently and ran 6 % slower;
+// and the layout's two fields arrive as scalar arguments, L{f0, f1}: with a struct argument hipcc allocates the equal-size 8- and 16-slot
+// instances differently again, 60 -> 62 and 120 -> 119 VGPRs)
+// Stacked: an instance sized for the largest cloud of the launch serves the smaller ones (threads >= bs own nothing: a cloud of
+// n < 1024 points has n < 2 bs, so two register slots per owner hold it under any PPT >= 2).
+template <class L, int THREADS, int PPT, bool REG, class F0, class F1>
+__global__ __launch_bounds__(THREADS) void fps_k(F0 f0, F1 f1, int m, const float* __restrict__ dataset, float* __restrict__ temp,
+                                                 int* __restrict__ idxs) {
+  const L lay = {f0, f1};
+  int n, bs;
+  int64_t row;
+  if (!fps_sample(lay, m, kFpsPlain, blockIdx.x, n, bs, row)) return;
   if (m <= 0) return;
   constexpr int NW = THREADS / 64;
   __shared__ uint64_t s_key[2][NW];
@@ -356,7 +380,7 @@ __device__ __forceinline__ void fps_body(int b, int64_t row, int n, int m, int b
   int log2bs = 0;
   while ((1 << (log2bs + 1)) <= bs) ++log2bs;
   if (log2bs == 0) log2bs = 1;  // bs == 1: a single owner, priority irrelevant (shift by 31 stays defined)
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   dataset += row * 3;
   temp += row;
   idxs += static_cast<int64_t>(b) * m;
@@ -424,95 +448,6 @@ __device__ __forceinline__ void fps_body(int b, int64_t row, int n, int m, int b
     }
   }
 }
-// (the equal-size plain kernel keeps its own text: behind fps_body its 16-slot instance was allocated differently and ran 6 % slower)
-template <int THREADS, int PPT, bool REG>
-__global__ __launch_bounds__(THREADS) void fps_k(int n, int m, int bs, const float* __restrict__ dataset, float* __restrict__ temp,
-                                                 int* __restrict__ idxs) {
-  if (m <= 0) return;
-  constexpr int NW = THREADS / 64;
-  __shared__ uint64_t s_key[2][NW];
-  __shared__ int s_idx[2][NW];
-  int log2bs = 0;
-  while ((1 << (log2bs + 1)) <= bs) ++log2bs;
-  if (log2bs == 0) log2bs = 1;  // bs == 1: a single owner, priority irrelevant (shift by 31 stays defined)
-  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  dataset += static_cast<int64_t>(b) * n * 3;
-  temp += static_cast<int64_t>(b) * n;
-  idxs += static_cast<int64_t>(b) * m;
-  float px[PPT], py[PPT], pz[PPT], pt[PPT];
-  if (REG) {
-#pragma unroll
-    for (int j = 0; j < PPT; ++j) {
-      const int k = tid + j * bs;
-      const bool ok = tid < bs && k < n;
-      px[j] = ok ? dataset[k * 3] : 0.f;
-      py[j] = ok ? dataset[k * 3 + 1] : 0.f;
-      pz[j] = ok ? dataset[k * 3 + 2] : 0.f;
-      pt[j] = ok ? temp[k] : -2.f;  // never selected: min(d, -2) = -2 < best init -1
-    }
-  }
-  int old = 0;
-  if (tid == 0) idxs[0] = 0;
-  for (int j = 1; j < m; ++j) {
-    const float x1 = dataset[old * 3], y1 = dataset[old * 3 + 1], z1 = dataset[old * 3 + 2];
-    float best = -1.f;
-    int besti = 0;
-    if (REG) {
-#pragma unroll
-      for (int q = 0; q < PPT; ++q) {
-        const float d = sqdist(px[q], py[q], pz[q], x1, y1, z1);
-        const float d2 = fminf(d, pt[q]);
-        pt[q] = d2;
-        if (d2 > best) { best = d2; besti = tid + q * bs; }
-      }
-    } else if (tid < bs) {
-      for (int k = tid; k < n; k += bs) {
-        const float d = sqdist(dataset[k * 3], dataset[k * 3 + 1], dataset[k * 3 + 2], x1, y1, z1);
-        const float d2 = fminf(d, temp[k]);
-        temp[k] = d2;
-        if (d2 > best) { best = d2; besti = k; }
-      }
-    }
-    // Block argmax with the reference's tie-break.  Its shared-memory tree (sampling_gpu.cu:93-98,150-207) merges slot
-    // t+s into slot t and keeps slot t unless the other value is strictly larger, so among equal maxima the survivor
-    // is the thread whose index is smallest in BIT-REVERSED order (the s = 1 step prefers even slots, s = 2 then
-    // prefers slots = 0 mod 4, ...).  Encode (value, ~bitrev(tid)) in one 64-bit key and take the maximum.
-    const uint32_t prio = (tid < bs) ? (__brev(static_cast<uint32_t>(tid)) >> (32 - log2bs)) : 0x7fffffffu;
-    const uint32_t vbits = best >= 0.f ? __float_as_uint(best) : 0u;
-    uint64_t key = (static_cast<uint64_t>(vbits) << 32) | static_cast<uint64_t>(0xffffffffu - prio);
-    const uint64_t wkey = wave_max_u64(key);   // DPP, no LDS round trips
-    const int leader = __builtin_amdgcn_readfirstlane(__ffsll(static_cast<long long>(__ballot(key == wkey))) - 1);
-    const int widx = __builtin_amdgcn_readlane(besti, leader);
-    const int buf = j & 1;
-    if (lane == 0) { s_key[buf][w] = wkey; s_idx[buf][w] = widx; }
-    lds_barrier();   // waves talk through LDS only: the idxs[] store of the previous round need not be drained
-    // NW (<= 16) wave keys: one per lane, row reduction, lowest wave holding the maximum wins (= ascending scan with '>')
-    const uint64_t mine = lane < NW ? s_key[buf][lane] : 0ull;
-    const uint64_t rmax = row_max_u64(mine);
-    const uint32_t ghi = __builtin_amdgcn_readfirstlane(static_cast<int>(rmax >> 32)), glo = __builtin_amdgcn_readfirstlane(static_cast<int>(rmax));
-    const uint64_t gkey = (static_cast<uint64_t>(ghi) << 32) | glo;
-    const int gw = __builtin_amdgcn_readfirstlane(__ffsll(static_cast<long long>(__ballot(lane < NW && mine == gkey))) - 1);
-    old = s_idx[buf][gw];
-    if (tid == 0) idxs[j] = old;
-  }
-  if (REG) {  // the reference leaves the final running distances in `temp` (caller-visible buffer)
-#pragma unroll
-    for (int j = 0; j < PPT; ++j) {
-      const int k = tid + j * bs;
-      if (tid < bs && k < n) temp[k] = pt[j];
-    }
-  }
-}
-// stacked: an instance sized for the largest cloud of the launch serves the smaller ones (threads >= bs own nothing: a cloud of
-// n < 1024 points has n < 2 bs, so two register slots per owner hold it under any PPT >= 2)
-template <int THREADS, int PPT, bool REG>
-__global__ __launch_bounds__(THREADS) void fps_stack_k(FpsStack a, int m, const float* __restrict__ dataset, float* __restrict__ temp,
-                                                       int* __restrict__ idxs) {
-  int n, bs;
-  int64_t row;
-  if (!fps_stack_sample(a, m, kFpsPlain, blockIdx.x, n, bs, row)) return;
-  fps_body<THREADS, PPT, REG>(blockIdx.x, row, n, m, bs, dataset, temp, idxs);
-}
 
 // ---- bucketed (lazy) furthest point sampling -------------------------------------------------------------------------
 // Same result as fps_k, bit for bit, with far less arithmetic per round.  The points of a sample are put in Morton order
@@ -547,11 +482,9 @@ __device__ __forceinline__ void fps_bbox_body(int64_t row, int n, const float* _
   }
   if (threadIdx.x < 6) bbox[blockIdx.x * 6 + threadIdx.x] = red[threadIdx.x][0];
 }
-__global__ __launch_bounds__(256) void fps_bbox_k(int n, const float* __restrict__ pts, float* __restrict__ bbox) {
-  fps_bbox_body(static_cast<int64_t>(blockIdx.x) * n, n, pts, bbox);
-}
-__global__ __launch_bounds__(256) void fps_bbox_stack_k(const int* __restrict__ cnt, const float* __restrict__ pts, float* __restrict__ bbox) {
-  fps_bbox_body(fps_stack_row(cnt, blockIdx.x), cnt[blockIdx.x], pts, bbox);
+template <class L>
+__global__ __launch_bounds__(256) void fps_bbox_k(L lay, const float* __restrict__ pts, float* __restrict__ bbox) {
+  fps_bbox_body(lay.row(blockIdx.x), lay.count(blockIdx.x), pts, bbox);
 }
 __device__ __forceinline__ uint32_t spread3(uint32_t v) {  // 8 bits -> every third bit
   v &= 0xffu;
@@ -612,12 +545,13 @@ __global__ void fps_keys_k(int b, int n, const float* __restrict__ pts, const fl
   fps_key_of(t, static_cast<int>(t / n), static_cast<int>(t % n), pts, bbox, keys);
 }
 // stacked: blockIdx.y is the sample, blockIdx.x walks the largest cloud of the call
-__global__ __launch_bounds__(256) void fps_keys_stack_k(const int* __restrict__ cnt, const float* __restrict__ pts, const float* __restrict__ bbox,
+__global__ __launch_bounds__(256) void fps_keys_stack_k(FpsStack a, const float* __restrict__ pts, const float* __restrict__ bbox,
                                                         uint64_t* __restrict__ keys) {
-  const int s = blockIdx.y, n = cnt[s];
+  const int s = blockIdx.y, n = a.count(s);
   if (static_cast<int>(blockIdx.x * 256) >= n) return;
-  const int row = fps_stack_row(cnt, s), k = static_cast<int>(blockIdx.x * 256 + threadIdx.x);
-  if (k < n) fps_key_of(static_cast<int64_t>(row) + k, s, k, pts, bbox, keys);   // (a plain-form sample's keys are sorted along and never read)
+  const int64_t row = a.row(s);
+  const int k = static_cast<int>(blockIdx.x * 256 + threadIdx.x);
+  if (k < n) fps_key_of(row + k, s, k, pts, bbox, keys);   // (a plain-form sample's keys are sorted along and never read)
 }
 
 template <int PPT>
@@ -740,18 +674,12 @@ __device__ __forceinline__ void fps_bucket_body(int b, int64_t row, int n, int m
   for (int q = 0; q < PPT; ++q)
     if (pr[q] != 0xffffffffu) temp[index_of(pr[q])] = pt[q];
 }
-template <int PPT>
-__global__ __launch_bounds__(1024) void fps_bucket_k(int n, int m, int bs, const float* __restrict__ dataset, const uint64_t* __restrict__ keys,
+template <class L, int PPT>
+__global__ __launch_bounds__(1024) void fps_bucket_k(L lay, int m, const float* __restrict__ dataset, const uint64_t* __restrict__ keys,
                                                      float* __restrict__ temp, int* __restrict__ idxs) {
-  const int b = blockIdx.x;
-  fps_bucket_body<PPT>(b, static_cast<int64_t>(b) * n, n, m, bs, dataset, keys, temp, idxs);
-}
-template <int PPT>
-__global__ __launch_bounds__(1024) void fps_bucket_stack_k(FpsStack a, int m, const float* __restrict__ dataset, const uint64_t* __restrict__ keys,
-                                                           float* __restrict__ temp, int* __restrict__ idxs) {
   int n, bs;
   int64_t row;
-  if (!fps_stack_sample(a, m, kFpsWave, blockIdx.x, n, bs, row)) return;
+  if (!fps_sample(lay, m, kFpsWave, blockIdx.x, n, bs, row)) return;
   fps_bucket_body<PPT>(blockIdx.x, row, n, m, bs, dataset, keys, temp, idxs);
 }
 
@@ -1017,24 +945,17 @@ __device__ __forceinline__ void fps_wave_body(int b, int64_t row, int n, int m, 
     if (myp != 0xffffffffu) temp[index_of(myp)] = pt.get(s);
   }
 }
-template <int S, bool TRACE, bool IDX = false>
-__global__ __launch_bounds__(kFpsWaves * 64) void fps_wave_k(int n, int m, int bs, const float* __restrict__ dataset,
-                                                             const uint64_t* __restrict__ keys, float* __restrict__ temp, int* __restrict__ idxs,
-                                                             unsigned long long* __restrict__ trace_) {
-  const int b = blockIdx.x;
-  fps_wave_body<S, TRACE, IDX>(b, static_cast<int64_t>(b) * n, n, m, bs, dataset, keys, temp, idxs, trace_);
-}
-// stacked: S holds the largest cloud of the launch.  A smaller cloud leaves its upper slots empty, which is the state the last, partly
+// Stacked: S holds the largest cloud of the launch.  A smaller cloud leaves its upper slots empty, which is the state the last, partly
 // filled slot of any cloud already has: running distance -2 in every lane, an inverted box (+inf, -inf), bucket maximum -2 - the box bound
 // of such a slot is +inf, never below -2, so it is never touched, and -2 never wins the wave's arg-max over a real maximum (>= 0).
-template <int S, bool IDX>
-__global__ __launch_bounds__(kFpsWaves * 64) void fps_wave_stack_k(FpsStack a, int m, const float* __restrict__ dataset,
-                                                                   const uint64_t* __restrict__ keys, float* __restrict__ temp,
-                                                                   int* __restrict__ idxs) {
+template <class L, int S, bool TRACE, bool IDX = false>
+__global__ __launch_bounds__(kFpsWaves * 64) void fps_wave_k(L lay, int m, const float* __restrict__ dataset,
+                                                             const uint64_t* __restrict__ keys, float* __restrict__ temp, int* __restrict__ idxs,
+                                                             unsigned long long* __restrict__ trace_) {
   int n, bs;
   int64_t row;
-  if (!fps_stack_sample(a, m, kFpsWave, blockIdx.x, n, bs, row)) return;
-  fps_wave_body<S, false, IDX>(blockIdx.x, row, n, m, bs, dataset, keys, temp, idxs, nullptr);
+  if (!fps_sample(lay, m, kFpsWave, blockIdx.x, n, bs, row)) return;
+  fps_wave_body<S, TRACE, IDX>(blockIdx.x, row, n, m, bs, dataset, keys, temp, idxs, trace_);
 }
 
 // ---- streaming furthest point sampling (clouds too large for one CU's registers: n > 24576, e.g. Waymo's ~180 k) ----------
@@ -1086,10 +1007,10 @@ __global__ __launch_bounds__(256) void fps_stream_prep_stack_k(FpsStack a, int m
                                                                float* __restrict__ sz, float* __restrict__ sd, uint32_t* __restrict__ sp) {
   int n, bs;
   int64_t row;
-  if (!fps_stack_sample(a, m, kFpsStream, blockIdx.y, n, bs, row)) return;
+  if (!fps_sample(a, m, kFpsStream, blockIdx.y, n, bs, row)) return;
   if (static_cast<int>(blockIdx.x * 256) >= fps_stream_rows(n)) return;   // whole buckets: all 256 threads of a block are inside or outside
   const int pos = static_cast<int>(blockIdx.x * 256 + threadIdx.x);
-  const int64_t t = fps_stack_stream_row(a, m, blockIdx.y) + pos;
+  const int64_t t = a.stream_row(m, blockIdx.y) + pos;
   if (pos >= n) {   // padding of the last bucket (see fps_stream_prep_k)
     sx[t] = 0.f; sy[t] = 0.f; sz[t] = 0.f; sd[t] = -2.f; sp[t] = 0xffffffffu;
     return;
@@ -1107,9 +1028,9 @@ __global__ __launch_bounds__(256) void fps_stream_post_stack_k(FpsStack a, int m
                                                                float* __restrict__ temp) {
   int n, bs;
   int64_t row;
-  if (!fps_stack_sample(a, m, kFpsStream, blockIdx.y, n, bs, row)) return;
+  if (!fps_sample(a, m, kFpsStream, blockIdx.y, n, bs, row)) return;
   if (static_cast<int>(blockIdx.x * 256) >= n) return;
-  const int64_t base = fps_stack_stream_row(a, m, blockIdx.y);
+  const int64_t base = a.stream_row(m, blockIdx.y);
   const int pos = static_cast<int>(blockIdx.x * 256 + threadIdx.x);
   if (pos < n) temp[row + static_cast<int>(keys[row + pos] & 0xffffffull)] = sd[base + pos];
 }
@@ -1277,24 +1198,17 @@ __device__ __forceinline__ void fps_stream_body(int b, int64_t row, int64_t base
     t[0] = t_test; t[1] = t_fetch; t[2] = t_first; t[3] = t_buckets; t[4] = t_best; t[5] = t_barrier; t[6] = t_pick; t[7] = n_touched;
   }
 }
-__global__ __launch_bounds__(kStreamWaves * 64) void fps_stream_k(int n, int m, int bs, const float* __restrict__ dataset,
+template <class L>
+__global__ __launch_bounds__(kStreamWaves * 64) void fps_stream_k(L lay, int m, const float* __restrict__ dataset,
                                                                   const float* __restrict__ sx_, const float* __restrict__ sy_,
                                                                   const float* __restrict__ sz_, float* __restrict__ sd_,
                                                                   const uint32_t* __restrict__ sp_, int* __restrict__ idxs,
                                                                   unsigned long long* __restrict__ trace) {
-  const int b = blockIdx.x;
-  const int nb = (n + kStreamBucket - 1) / kStreamBucket;
-  // the sorted copies are padded to whole buckets (fps_stream_prep_k)
-  fps_stream_body(b, static_cast<int64_t>(b) * n, static_cast<int64_t>(b) * nb * kStreamBucket, n, m, bs, dataset, sx_, sy_, sz_, sd_, sp_, idxs, trace);
-}
-__global__ __launch_bounds__(kStreamWaves * 64) void fps_stream_stack_k(FpsStack a, int m, const float* __restrict__ dataset,
-                                                                        const float* __restrict__ sx_, const float* __restrict__ sy_,
-                                                                        const float* __restrict__ sz_, float* __restrict__ sd_,
-                                                                        const uint32_t* __restrict__ sp_, int* __restrict__ idxs) {
   int n, bs;
   int64_t row;
-  if (!fps_stack_sample(a, m, kFpsStream, blockIdx.x, n, bs, row)) return;
-  fps_stream_body(blockIdx.x, row, fps_stack_stream_row(a, m, blockIdx.x), n, m, bs, dataset, sx_, sy_, sz_, sd_, sp_, idxs, nullptr);
+  if (!fps_sample(lay, m, kFpsStream, blockIdx.x, n, bs, row)) return;
+  // the sorted copies are padded to whole buckets (fps_stream_prep_k)
+  fps_stream_body(blockIdx.x, row, lay.stream_row(m, blockIdx.x), n, m, bs, dataset, sx_, sy_, sz_, sd_, sp_, idxs, L::kTrace ? trace : nullptr);
 }
 
 // ------------------------------------------------------------------ three_nn / interpolate --------
@@ -2051,97 +1965,8 @@ extern "C" size_t fv2p_furthest_point_sampling_ws_bytes(int b, int n) {
   return s.bytes();
 }
 
-extern "C" int fv2p_furthest_point_sampling(int b, int n, int m, const float* dataset, float* temp, int* idxs, void* ws, size_t ws_bytes,
-                                            fv2p_stream_t s) {
-  FV2P_REQUIRE(b >= 0 && n >= 1 && m >= 0, FV2P_EINVAL, "furthest_point_sampling: bad sizes");
-  if (b == 0 || m == 0) return 0;
-  FV2P_REQUIRE(dataset && temp && idxs, FV2P_EINVAL, "furthest_point_sampling: null pointer");
-  const int bs = fps_ref_block(n);
-  hipStream_t st = STREAM(s);
-  const int lazy = fps_dev_lazy();
-  if (lazy && ws && ws_bytes >= fv2p_furthest_point_sampling_ws_bytes(b, n) && fps_bucketed_applies(n, m) && b < 65536) {
-    const int64_t total = static_cast<int64_t>(b) * n;
-    Carver c(ws, ws_bytes);
-    float* bbox = c.take<float>(static_cast<size_t>(b) * 6);
-    uint64_t* keys = c.take<uint64_t>(static_cast<size_t>(total));
-    uint64_t* tmp = c.take<uint64_t>(static_cast<size_t>(total));
-    const size_t rb = radix_sort_ws_bytes(total);
-    char* rws = c.take<char>(rb);
-    hipLaunchKernelGGL(fps_bbox_k, dim3(b), dim3(256), 0, st, n, dataset, bbox);
-    hipLaunchKernelGGL(fps_keys_k, G1D(total), 0, st, b, n, dataset, bbox, keys);
-    int sbits = 0;
-    while ((1 << sbits) < b) ++sbits;
-    if (int rc = radix_sort_u64(keys, tmp, total, 24, 48 + sbits, rws, rb, st)) return rc;
-    if (n > kFpsMaxSlots * kFpsWaves * 64) {   // does not fit one CU's registers: streaming kernel on the sorted copy
-      const int ns = static_cast<int>(ceil_div(n, kStreamBucket)) * kStreamBucket;
-      const int64_t padded = static_cast<int64_t>(b) * ns;
-      float* sx = c.take<float>(static_cast<size_t>(padded) * 5);
-      float *sy = sx + padded, *sz = sy + padded, *sd = sz + padded;
-      uint32_t* sp = reinterpret_cast<uint32_t*>(sd + padded);
-      hipLaunchKernelGGL(fps_stream_prep_k, G1D(padded), 0, st, padded, n, ns, dataset, temp, keys, bs, sx, sy, sz, sd, sp);
-      hipLaunchKernelGGL(fps_stream_k, dim3(b), dim3(kStreamWaves * 64), 0, st, n, m, bs, dataset, sx, sy, sz, sd, sp, idxs, g_fps_trace);
-      hipLaunchKernelGGL(fps_stream_post_k, G1D(total), 0, st, total, n, ns, keys, sd, temp);
-      FV2P_LAUNCH_CHECK();
-      return 0;
-    }
-    const int form = fps_dev_form();
-    const int slots = static_cast<int>(ceil_div(n, kFpsWaves * 64));
-    const int ppt = static_cast<int>(ceil_div(n, 1024));
-    const int tree = fps_dev_idx();
-    // measured (us per round, run-time index against compile-time scan): 16 384 points (32 slots) 0.601 / 0.714, 20 000 (40 slots: the
-    // second vector's branch, 237 registers) 0.830 / 0.757, 24 576 (48 slots) 0.956 / 0.801 -> run-time indices up to 32 slots (2 = always)
-    const bool idx_form = tree == 2 || (tree == 1 && slots <= 32);
-    if (form == 1 || ppt > 16) {
-#define FV2P_FPS(SS)                                                                                                       \
-  do {                                                                                                                     \
-    const size_t lds = static_cast<size_t>(SS) * kFpsWaves * 64 * sizeof(uint32_t);                                         \
-    static bool big = false;                                                                                               \
-    if (lds > 48 * 1024 && !big) {                                                                                         \
-      FV2P_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&fps_wave_k<SS, false>), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                   static_cast<int>(lds)));                                                                \
-      FV2P_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&fps_wave_k<SS, true>), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                   static_cast<int>(lds)));                                                                \
-      FV2P_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&fps_wave_k<SS, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                   static_cast<int>(lds)));                                                                \
-      FV2P_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&fps_wave_k<SS, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                   static_cast<int>(lds)));                                                                \
-      big = true;                                                                                                          \
-    }                                                                                                                      \
-    if (g_fps_trace && idx_form) hipLaunchKernelGGL((fps_wave_k<SS, true, true>), dim3(b), dim3(kFpsWaves * 64), lds, st, n, m, bs, dataset, keys, temp, idxs, g_fps_trace); \
-    else if (g_fps_trace) hipLaunchKernelGGL((fps_wave_k<SS, true>), dim3(b), dim3(kFpsWaves * 64), lds, st, n, m, bs, dataset, keys, temp, idxs, g_fps_trace); \
-    else if (idx_form) hipLaunchKernelGGL((fps_wave_k<SS, false, true>), dim3(b), dim3(kFpsWaves * 64), lds, st, n, m, bs, dataset, keys, temp, idxs, nullptr); \
-    else hipLaunchKernelGGL((fps_wave_k<SS, false>), dim3(b), dim3(kFpsWaves * 64), lds, st, n, m, bs, dataset, keys, temp, idxs, nullptr); \
-  } while (0)
-      if (slots <= 8) FV2P_FPS(8);
-      else if (slots <= 16) FV2P_FPS(16);
-      else if (slots <= 24) FV2P_FPS(24);
-      else if (slots <= 32) FV2P_FPS(32);
-      else if (slots <= 40) FV2P_FPS(40);
-      else FV2P_FPS(48);
-#undef FV2P_FPS
-    } else if (ppt <= 4) hipLaunchKernelGGL((fps_bucket_k<4>), dim3(b), dim3(1024), 0, st, n, m, bs, dataset, keys, temp, idxs);
-    else if (ppt <= 8) hipLaunchKernelGGL((fps_bucket_k<8>), dim3(b), dim3(1024), 0, st, n, m, bs, dataset, keys, temp, idxs);
-    else hipLaunchKernelGGL((fps_bucket_k<16>), dim3(b), dim3(1024), 0, st, n, m, bs, dataset, keys, temp, idxs);
-    FV2P_LAUNCH_CHECK();
-    return 0;
-  }
-  if (bs == 1024) {
-    const int ppt = static_cast<int>(ceil_div(n, 1024));
-    if (ppt <= 4) hipLaunchKernelGGL((fps_k<1024, 4, true>), dim3(b), dim3(1024), 0, st, n, m, bs, dataset, temp, idxs);
-    else if (ppt <= 8) hipLaunchKernelGGL((fps_k<1024, 8, true>), dim3(b), dim3(1024), 0, st, n, m, bs, dataset, temp, idxs);
-    else if (ppt <= 16) hipLaunchKernelGGL((fps_k<1024, 16, true>), dim3(b), dim3(1024), 0, st, n, m, bs, dataset, temp, idxs);
-    else hipLaunchKernelGGL((fps_k<1024, 1, false>), dim3(b), dim3(1024), 0, st, n, m, bs, dataset, temp, idxs);
-  } else if (bs >= 256) {
-    hipLaunchKernelGGL((fps_k<512, 2, true>), dim3(b), dim3(512), 0, st, n, m, bs, dataset, temp, idxs);  // n < 1024: <= 2 points per owner
-  } else {
-    hipLaunchKernelGGL((fps_k<128, 2, true>), dim3(b), dim3(128), 0, st, n, m, bs, dataset, temp, idxs);
-  }
-  FV2P_LAUNCH_CHECK();
-  return 0;
-}
-
 // ---- stacked batch of unequal clouds ---------------------------------------------------------------------------------
-// The same kernels' bodies behind *_stack_k: every sample on the form its own count selects, the forms present launched once each.
+// The same kernels over the FpsStack layout: every sample on the form its own count selects, the forms present launched once each.
 extern "C" size_t fv2p_furthest_point_sampling_stack_ws_bytes(int b, const int* cnt_host) {
   int64_t total = 0, padded = 0;
   for (int i = 0; cnt_host && i < b; ++i) {
@@ -2159,6 +1984,127 @@ extern "C" size_t fv2p_furthest_point_sampling_stack_ws_bytes(int b, const int* 
   return s.bytes();
 }
 
+// One call's samplers, for either layout.  most[f]: the largest cloud of form f in the call (0: form absent; a non-zero bucketed form
+// means the workspace admits the Morton pre-pass); total: the rows of the call; padded: the rows of the streaming form's sorted copies.
+// Every form present is launched once, one workgroup per sample, on the instance its largest cloud would get alone.
+template <class L>
+static int fps_run(const L& lay, int b, int m, const int most[3], int64_t total, int64_t padded, const float* dataset, float* temp, int* idxs,
+                   void* ws, size_t ws_bytes, unsigned long long* trace_, hipStream_t st) {
+  constexpr bool kEqual = std::is_same<L, FpsEqual>::value;
+  unsigned long long* trace = L::kTrace ? trace_ : nullptr;
+  const unsigned ub = static_cast<unsigned>(b);
+  const dim3 one_per_sample(ub);
+  if (most[kFpsWave] || most[kFpsStream]) {
+    // Morton pre-pass over ALL points of the call: one sort keyed by sample, so that every sample's sorted keys lie at its own rows.  The
+    // plain form's samples of a stacked call ride along unused (a batch of one form, the normal case, has none; above 2^24 points their
+    // point number runs into the curve bits of keys nobody reads).
+    Carver c(ws, ws_bytes);
+    float* bbox = c.take<float>(static_cast<size_t>(b) * 6);
+    uint64_t* keys = c.take<uint64_t>(static_cast<size_t>(total));
+    uint64_t* tmp = c.take<uint64_t>(static_cast<size_t>(total));
+    const size_t rb = radix_sort_ws_bytes(total);
+    char* rws = c.take<char>(rb);
+    int most_all = 0;
+    for (int f = 0; f < 3; ++f) most_all = most[f] > most_all ? most[f] : most_all;
+    hipLaunchKernelGGL(fps_bbox_k<L>, one_per_sample, dim3(256), 0, st, lay, dataset, bbox);
+    if constexpr (kEqual) hipLaunchKernelGGL(fps_keys_k, G1D(total), 0, st, b, lay.n, dataset, bbox, keys);
+    else hipLaunchKernelGGL(fps_keys_stack_k, dim3(static_cast<unsigned>(ceil_div(most_all, 256)), ub), dim3(256), 0, st, lay, dataset, bbox, keys);
+    int sbits = 0;
+    while ((1 << sbits) < b) ++sbits;
+    if (int rc = radix_sort_u64(keys, tmp, total, 24, 48 + sbits, rws, rb, st)) return rc;
+    if (most[kFpsStream]) {   // does not fit one CU's registers: streaming kernel on the sorted copy
+      const int ns = fps_stream_rows(most[kFpsStream]);
+      float* sx = c.take<float>(static_cast<size_t>(padded) * 5);
+      float *sy = sx + padded, *sz = sy + padded, *sd = sz + padded;
+      uint32_t* sp = reinterpret_cast<uint32_t*>(sd + padded);
+      if constexpr (kEqual) hipLaunchKernelGGL(fps_stream_prep_k, G1D(padded), 0, st, padded, lay.n, ns, dataset, temp, keys, lay.bs, sx, sy, sz, sd, sp);
+      else hipLaunchKernelGGL(fps_stream_prep_stack_k, dim3(static_cast<unsigned>(ns / 256), ub), dim3(256), 0, st, lay, m, dataset, temp, keys, sx, sy, sz, sd, sp);
+      hipLaunchKernelGGL(fps_stream_k<L>, one_per_sample, dim3(kStreamWaves * 64), 0, st, lay, m, dataset, sx, sy, sz, sd, sp, idxs, trace);
+      if constexpr (kEqual) hipLaunchKernelGGL(fps_stream_post_k, G1D(total), 0, st, total, lay.n, ns, keys, sd, temp);
+      else hipLaunchKernelGGL(fps_stream_post_stack_k, dim3(static_cast<unsigned>(ceil_div(most[kFpsStream], 256)), ub), dim3(256), 0, st, lay, m, keys, sd, temp);
+    }
+    if (most[kFpsWave]) {
+      const int slots = static_cast<int>(ceil_div(most[kFpsWave], kFpsWaves * 64));
+      const int ppt = static_cast<int>(ceil_div(most[kFpsWave], 1024));
+      const int tree = fps_dev_idx();
+      // measured (us per round, run-time index against compile-time scan): 16 384 points (32 slots) 0.601 / 0.714, 20 000 (40 slots: the
+      // second vector's branch, 237 registers) 0.830 / 0.757, 24 576 (48 slots) 0.956 / 0.801 -> run-time indices up to 32 slots (2 = always)
+      const bool idx_form = tree == 2 || (tree == 1 && slots <= 32);
+      if (fps_dev_form() == 1 || ppt > 16) {
+#define FV2P_FPS_GO(SS, TRACE, IDX) \
+  hipLaunchKernelGGL((fps_wave_k<L, SS, TRACE, IDX>), one_per_sample, dim3(kFpsWaves * 64), lds, st, lay, m, dataset, keys, temp, idxs, trace)
+#define FV2P_FPS_LDS(SS, TRACE, IDX)                                                                                             \
+  FV2P_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&fps_wave_k<L, SS, TRACE, IDX>), hipFuncAttributeMaxDynamicSharedMemorySize, \
+                               static_cast<int>(lds)))
+#define FV2P_FPS(SS)                                                                                \
+  do {                                                                                              \
+    const size_t lds = static_cast<size_t>(SS) * kFpsWaves * 64 * sizeof(uint32_t);                  \
+    static bool big = false;                                                                        \
+    if (lds > 48 * 1024 && !big) {                                                                  \
+      FV2P_FPS_LDS(SS, false, false);                                                               \
+      FV2P_FPS_LDS(SS, false, true);                                                                \
+      if constexpr (L::kTrace) {                                                                    \
+        FV2P_FPS_LDS(SS, true, false);                                                              \
+        FV2P_FPS_LDS(SS, true, true);                                                               \
+      }                                                                                             \
+      big = true;                                                                                   \
+    }                                                                                               \
+    if constexpr (L::kTrace) {                                                                      \
+      if (trace && idx_form) FV2P_FPS_GO(SS, true, true);                                           \
+      else if (trace) FV2P_FPS_GO(SS, true, false);                                                 \
+    }                                                                                               \
+    if (!trace && idx_form) FV2P_FPS_GO(SS, false, true);                                           \
+    else if (!trace) FV2P_FPS_GO(SS, false, false);                                                 \
+  } while (0)
+        if (slots <= 8) FV2P_FPS(8);
+        else if (slots <= 16) FV2P_FPS(16);
+        else if (slots <= 24) FV2P_FPS(24);
+        else if (slots <= 32) FV2P_FPS(32);
+        else if (slots <= 40) FV2P_FPS(40);
+        else FV2P_FPS(48);
+#undef FV2P_FPS
+#undef FV2P_FPS_LDS
+#undef FV2P_FPS_GO
+      } else if (ppt <= 4) hipLaunchKernelGGL((fps_bucket_k<L, 4>), one_per_sample, dim3(1024), 0, st, lay, m, dataset, keys, temp, idxs);
+      else if (ppt <= 8) hipLaunchKernelGGL((fps_bucket_k<L, 8>), one_per_sample, dim3(1024), 0, st, lay, m, dataset, keys, temp, idxs);
+      else hipLaunchKernelGGL((fps_bucket_k<L, 16>), one_per_sample, dim3(1024), 0, st, lay, m, dataset, keys, temp, idxs);
+    }
+  }
+  if (most[kFpsPlain]) {
+    const int n = most[kFpsPlain], bs = fps_ref_block(n);
+    const auto [f0, f1] = lay;   // fps_k takes the layout's fields one by one
+#define FV2P_FPS_PLAIN(T, PPT, REG) hipLaunchKernelGGL((fps_k<L, T, PPT, REG>), one_per_sample, dim3(T), 0, st, f0, f1, m, dataset, temp, idxs)
+    if (bs == 1024) {
+      const int ppt = static_cast<int>(ceil_div(n, 1024));
+      if (ppt <= 4) FV2P_FPS_PLAIN(1024, 4, true);
+      else if (ppt <= 8) FV2P_FPS_PLAIN(1024, 8, true);
+      else if (ppt <= 16) FV2P_FPS_PLAIN(1024, 16, true);
+      else FV2P_FPS_PLAIN(1024, 1, false);
+    } else if (bs >= 256) {
+      FV2P_FPS_PLAIN(512, 2, true);  // n < 1024: <= 2 points per owner
+    } else {
+      FV2P_FPS_PLAIN(128, 2, true);
+    }
+#undef FV2P_FPS_PLAIN
+  }
+  FV2P_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int fv2p_furthest_point_sampling(int b, int n, int m, const float* dataset, float* temp, int* idxs, void* ws, size_t ws_bytes,
+                                            fv2p_stream_t s) {
+  FV2P_REQUIRE(b >= 0 && n >= 1 && m >= 0, FV2P_EINVAL, "furthest_point_sampling: bad sizes");
+  if (b == 0 || m == 0) return 0;
+  FV2P_REQUIRE(dataset && temp && idxs, FV2P_EINVAL, "furthest_point_sampling: null pointer");
+  const bool bucketed = fps_dev_lazy() && ws && ws_bytes >= fv2p_furthest_point_sampling_ws_bytes(b, n) && b < 65536;
+  const int f = fps_family(n, m, bucketed);   // one form for the whole call
+  int most[3] = {0, 0, 0};
+  most[f] = n;
+  const int64_t total = static_cast<int64_t>(b) * n;
+  return fps_run(FpsEqual{n, fps_ref_block(n)}, b, m, most, total, f == kFpsStream ? static_cast<int64_t>(b) * fps_stream_rows(n) : 0, dataset, temp,
+                 idxs, ws, ws_bytes, g_fps_trace, STREAM(s));
+}
+
 extern "C" int fv2p_furthest_point_sampling_stack(int b, const int* cnt_host, const int* cnt_dev, int m, const float* dataset, float* temp,
                                                   int* idxs, void* ws, size_t ws_bytes, fv2p_stream_t s) {
   FV2P_REQUIRE(b >= 0 && m >= 0, FV2P_EINVAL, "furthest_point_sampling_stack: bad sizes");
@@ -2170,93 +2116,16 @@ extern "C" int fv2p_furthest_point_sampling_stack(int b, const int* cnt_host, co
     total += cnt_host[i];
   }
   FV2P_REQUIRE(total <= INT_MAX, FV2P_EINVAL, "furthest_point_sampling_stack: more than INT_MAX rows");
-  hipStream_t st = STREAM(s);
   const bool bucketed = fps_dev_lazy() && ws && ws_bytes >= fv2p_furthest_point_sampling_stack_ws_bytes(b, cnt_host) && b < 65536;
-  // the largest cloud of every form (0: form absent) and the padded rows of the streaming form's sorted copies
-  int most[3] = {0, 0, 0}, most_all = 0;
+  // every sample on the form its own count selects (what the equal-size call would choose for the cloud alone)
+  int most[3] = {0, 0, 0};
   int64_t padded = 0;
   for (int i = 0; i < b; ++i) {
     const int n = cnt_host[i], f = fps_family(n, m, bucketed);
     if (n > most[f]) most[f] = n;
-    if (n > most_all) most_all = n;
     if (f == kFpsStream) padded += fps_stream_rows(n);
   }
-  const FpsStack a = {cnt_dev, bucketed ? 1 : 0};
-  const dim3 one_per_sample(static_cast<unsigned>(b));
-  if (most[kFpsWave] || most[kFpsStream]) {
-    // Morton pre-pass over ALL points of the call: one sort keyed by sample, so that every sample's sorted keys lie at its own rows.  The
-    // plain form's samples ride along unused (a batch of one form, the normal case, has none; above 2^24 points their point number runs
-    // into the curve bits of keys nobody reads).
-    Carver c(ws, ws_bytes);
-    float* bbox = c.take<float>(static_cast<size_t>(b) * 6);
-    uint64_t* keys = c.take<uint64_t>(static_cast<size_t>(total));
-    uint64_t* tmp = c.take<uint64_t>(static_cast<size_t>(total));
-    const size_t rb = radix_sort_ws_bytes(total);
-    char* rws = c.take<char>(rb);
-    hipLaunchKernelGGL(fps_bbox_stack_k, one_per_sample, dim3(256), 0, st, cnt_dev, dataset, bbox);
-    hipLaunchKernelGGL(fps_keys_stack_k, dim3(static_cast<unsigned>(ceil_div(most_all, 256)), static_cast<unsigned>(b)), dim3(256), 0, st, cnt_dev,
-                       dataset, bbox, keys);
-    int sbits = 0;
-    while ((1 << sbits) < b) ++sbits;
-    if (int rc = radix_sort_u64(keys, tmp, total, 24, 48 + sbits, rws, rb, st)) return rc;
-    if (most[kFpsStream]) {
-      float* sx = c.take<float>(static_cast<size_t>(padded) * 5);
-      float *sy = sx + padded, *sz = sy + padded, *sd = sz + padded;
-      uint32_t* sp = reinterpret_cast<uint32_t*>(sd + padded);
-      hipLaunchKernelGGL(fps_stream_prep_stack_k, dim3(static_cast<unsigned>(fps_stream_rows(most[kFpsStream]) / 256), static_cast<unsigned>(b)),
-                         dim3(256), 0, st, a, m, dataset, temp, keys, sx, sy, sz, sd, sp);
-      hipLaunchKernelGGL(fps_stream_stack_k, one_per_sample, dim3(kStreamWaves * 64), 0, st, a, m, dataset, sx, sy, sz, sd, sp, idxs);
-      hipLaunchKernelGGL(fps_stream_post_stack_k, dim3(static_cast<unsigned>(ceil_div(most[kFpsStream], 256)), static_cast<unsigned>(b)), dim3(256),
-                         0, st, a, m, keys, sd, temp);
-    }
-    if (most[kFpsWave]) {
-      const int slots = static_cast<int>(ceil_div(most[kFpsWave], kFpsWaves * 64));
-      const int ppt = static_cast<int>(ceil_div(most[kFpsWave], 1024));
-      const int tree = fps_dev_idx();
-      const bool idx_form = tree == 2 || (tree == 1 && slots <= 32);   // as the equal-size call, by the launch's slot count
-      if (fps_dev_form() == 1 || ppt > 16) {
-#define FV2P_FPS(SS)                                                                                                       \
-  do {                                                                                                                     \
-    const size_t lds = static_cast<size_t>(SS) * kFpsWaves * 64 * sizeof(uint32_t);                                         \
-    static bool big = false;                                                                                               \
-    if (lds > 48 * 1024 && !big) {                                                                                         \
-      FV2P_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&fps_wave_stack_k<SS, false>), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                   static_cast<int>(lds)));                                                                \
-      FV2P_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&fps_wave_stack_k<SS, true>), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                   static_cast<int>(lds)));                                                                \
-      big = true;                                                                                                          \
-    }                                                                                                                      \
-    if (idx_form) hipLaunchKernelGGL((fps_wave_stack_k<SS, true>), one_per_sample, dim3(kFpsWaves * 64), lds, st, a, m, dataset, keys, temp, idxs); \
-    else hipLaunchKernelGGL((fps_wave_stack_k<SS, false>), one_per_sample, dim3(kFpsWaves * 64), lds, st, a, m, dataset, keys, temp, idxs); \
-  } while (0)
-        if (slots <= 8) FV2P_FPS(8);
-        else if (slots <= 16) FV2P_FPS(16);
-        else if (slots <= 24) FV2P_FPS(24);
-        else if (slots <= 32) FV2P_FPS(32);
-        else if (slots <= 40) FV2P_FPS(40);
-        else FV2P_FPS(48);
-#undef FV2P_FPS
-      } else if (ppt <= 4) hipLaunchKernelGGL((fps_bucket_stack_k<4>), one_per_sample, dim3(1024), 0, st, a, m, dataset, keys, temp, idxs);
-      else if (ppt <= 8) hipLaunchKernelGGL((fps_bucket_stack_k<8>), one_per_sample, dim3(1024), 0, st, a, m, dataset, keys, temp, idxs);
-      else hipLaunchKernelGGL((fps_bucket_stack_k<16>), one_per_sample, dim3(1024), 0, st, a, m, dataset, keys, temp, idxs);
-    }
-  }
-  if (most[kFpsPlain]) {   // the instance the largest cloud of the form would get alone
-    const int n = most[kFpsPlain], bs = fps_ref_block(n);
-    if (bs == 1024) {
-      const int ppt = static_cast<int>(ceil_div(n, 1024));
-      if (ppt <= 4) hipLaunchKernelGGL((fps_stack_k<1024, 4, true>), one_per_sample, dim3(1024), 0, st, a, m, dataset, temp, idxs);
-      else if (ppt <= 8) hipLaunchKernelGGL((fps_stack_k<1024, 8, true>), one_per_sample, dim3(1024), 0, st, a, m, dataset, temp, idxs);
-      else if (ppt <= 16) hipLaunchKernelGGL((fps_stack_k<1024, 16, true>), one_per_sample, dim3(1024), 0, st, a, m, dataset, temp, idxs);
-      else hipLaunchKernelGGL((fps_stack_k<1024, 1, false>), one_per_sample, dim3(1024), 0, st, a, m, dataset, temp, idxs);
-    } else if (bs >= 256) {
-      hipLaunchKernelGGL((fps_stack_k<512, 2, true>), one_per_sample, dim3(512), 0, st, a, m, dataset, temp, idxs);
-    } else {
-      hipLaunchKernelGGL((fps_stack_k<128, 2, true>), one_per_sample, dim3(128), 0, st, a, m, dataset, temp, idxs);
-    }
-  }
-  FV2P_LAUNCH_CHECK();
-  return 0;
+  return fps_run(FpsStack{cnt_dev, bucketed ? 1 : 0}, b, m, most, total, padded, dataset, temp, idxs, ws, ws_bytes, nullptr, STREAM(s));
 }
 
 extern "C" int fv2p_three_nn_batch(int b, int n, int m, const float* unknown, const float* known, float* dist2, int* idx, fv2p_stream_t s) {

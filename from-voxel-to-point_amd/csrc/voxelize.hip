@@ -13,11 +13,24 @@
 //                 voxel-id bits (stable, so input order inside a voxel survives); the slot
 //                 of a point is its sorted position minus the voxel's start offset.
 // All integer outputs are therefore bit-identical to the sequential loop.
+//
+// One pipeline, two policies.  Steps 1, 2 and 4 are the same code for one cloud (VoxOne) and for a stacked batch of B unequal clouds in
+// one point buffer (VoxStacked): vox_insert and vox_mark_first are templated on the policy, one workspace layout (vox_carve) and one
+// host tail (vox_sort_fill) serve both.  The policy says what sample a point belongs to - with VoxOne nothing, the key is the flat
+// cell; with VoxStacked the key is sample * grid volume + flat cell, so that atomicMin keeps the first point of every (sample, voxel).
+// Step 3 is where the routes really differ and stays two sets of kernels:
+//   one cloud : vox_assign finds the one break point, vox_finalize_scalars the voxel count, vox_words keys the kept points;
+//   stacked   : one scan of the first-flags over the whole buffer (n + 1 entries: rank[n] = all firsts), a first point's rank inside its
+//               sample is rank[i] - rank[off[b]].  Per sample, the break point is the first-flagged point of rank max_voxels (a binary
+//               search over the monotone rank[]: the smallest i of the sample with rank[i + 1] > rank[off[b]] + max_voxels); the
+//               sample's later points are dropped, other samples are unaffected.  Sample b keeps M_b = min(distinct voxels,
+//               max_voxels) voxels, its output rows start at base[b] = sum of M_a over a < b (vox_stack_bases: one workgroup, the only
+//               per-sample pass); vox_stack_words keys the kept points by output row and writes the rows' (b, z, y, x).
+// The number of launches of the stacked route does not depend on B (the offsets reach the device as kernel arguments, 256 per launch).
 #include "common.hpp"
 #include <cmath>
 #include <cstring>
 #include <vector>
-#include <type_traits>
 
 namespace fv2p {
 
@@ -26,27 +39,38 @@ struct VoxGeom {
   float lo[3];   // range min x,y,z
   int grid[3];   // cells x,y,z
 };
+static VoxGeom vox_geom(const float voxel_size[3], const float range_lo[3], const int grid[3]) {
+  VoxGeom g;
+  for (int j = 0; j < 3; ++j) { g.vs[j] = voxel_size[j]; g.lo[j] = range_lo[j]; g.grid[j] = grid[j]; }
+  return g;
+}
 
-// scalars[0] = distinct voxels D, [1] = cut-off point index i*, [2] = kept points, [3] = M
-__global__ void vox_insert(const float* __restrict__ pts, int64_t n, int ndim, VoxGeom g,
-                           uint64_t* __restrict__ table, uint32_t mask, int* __restrict__ slot,
-                           int* __restrict__ scalars) {
-  const int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-  if (i == 0) { scalars[1] = static_cast<int>(n); }
-  if (i >= n) return;
-  const float* p = pts + i * ndim;
-  int c[3];
+// The cell (x, y, z) of a point; false when it lies outside the grid (NaN coordinates too).  The one line every output's bit-exactness
+// rests on: fp32 subtract, then fp32 divide, then floor, as voxel_generator.py:188 (no reciprocal, no fma: the file is built with
+// -ffp-contract=off for the host and the device).  c[] is meaningful only when the point is inside.
+__host__ __device__ __forceinline__ bool vox_cell(const float* __restrict__ p, const VoxGeom& g, int c[3]) {
   bool ok = true;
 #pragma unroll
   for (int j = 0; j < 3; ++j) {
-    // fp32 subtract then fp32 divide then floor, as voxel_generator.py:188 (no reciprocal, no fma)
-    float f = floorf((p[j] - g.lo[j]) / g.vs[j]);
-    if (!(f >= 0.0f) || f >= static_cast<float>(g.grid[j])) ok = false;  // NaN -> dropped
+    const float f = floorf((p[j] - g.lo[j]) / g.vs[j]);
+    if (!(f >= 0.0f) || f >= static_cast<float>(g.grid[j])) ok = false;  // (:189-191) NaN -> dropped
     c[j] = static_cast<int>(f);
   }
-  if (!ok) { slot[i] = -1; return; }
-  const uint64_t key = (static_cast<uint64_t>(c[2]) * g.grid[1] + c[1]) * g.grid[0] + c[0];
-  const uint64_t word = slot_pack(key, static_cast<uint32_t>(i));
+  return ok;
+}
+template <typename K>
+__host__ __device__ __forceinline__ K vox_flat_key(const int c[3], const VoxGeom& g) {
+  return (static_cast<K>(c[2]) * g.grid[1] + c[1]) * g.grid[0] + c[0];
+}
+// flat key of a cell -> (z, y, x), the order the reference stores (:192)
+__device__ __forceinline__ void vox_decode(uint64_t key, const VoxGeom& g, int& z, int& y, int& x) {
+  x = static_cast<int>(key % g.grid[0]); key /= g.grid[0];
+  y = static_cast<int>(key % g.grid[1]);
+  z = static_cast<int>(key / g.grid[1]);
+}
+// Claims the table entry of `key` for point `index` (the smallest index of a key survives); returns the entry's slot.
+__device__ __forceinline__ int vox_claim(uint64_t* __restrict__ table, uint32_t mask, uint64_t key, uint32_t index) {
+  const uint64_t word = slot_pack(key, index);
   uint32_t h = hash_u64(key, mask);
   while (true) {
     unsigned long long old = atomicCAS(reinterpret_cast<unsigned long long*>(&table[h]),
@@ -59,17 +83,62 @@ __global__ void vox_insert(const float* __restrict__ pts, int64_t n, int ndim, V
     }
     h = (h + 1) & mask;
   }
-  slot[i] = static_cast<int>(h);
+  return static_cast<int>(h);
 }
 
-__global__ void vox_mark_first(int64_t n, const uint64_t* __restrict__ table, const int* __restrict__ slot,
-                               int* __restrict__ first) {
+// ---- the two policies: which sample a row of the point buffer belongs to ------------------------------------------------------------
+struct VoxOne {   // one cloud: no sample term, nothing read
+  static constexpr int kStacked = 0;
+  __device__ __forceinline__ uint64_t key_base(int64_t, const VoxGeom&) const { return 0; }
+};
+struct VoxStacked {   // B clouds back to back: off[b] <= rows of sample b < off[b + 1]
+  static constexpr int kStacked = 1;
+  const int* off;
+  int batch;
+  // sample of stacked row i: the b with off[b] <= i < off[b + 1] (empty samples have off[b] == off[b + 1] and own no row)
+  __device__ __forceinline__ int sample_of(int i) const {
+    int lo = 0, hi = batch;   // invariant: off[lo] <= i < off[hi]
+    while (hi - lo > 1) {
+      const int mid = (lo + hi) >> 1;
+      if (off[mid] <= i) lo = mid; else hi = mid;
+    }
+    return lo;
+  }
+  __device__ __forceinline__ uint64_t volume(const VoxGeom& g) const { return static_cast<uint64_t>(g.grid[0]) * g.grid[1] * g.grid[2]; }
+  __device__ __forceinline__ uint64_t key_base(int64_t i, const VoxGeom& g) const {
+    return static_cast<uint64_t>(sample_of(static_cast<int>(i))) * volume(g);
+  }
+};
+
+// scalars[0] = distinct voxels D, [1] = cut-off point index i*, [2] = kept points, [3] = M ([0], [1] and [3]: one cloud only)
+template <class S>
+__global__ void vox_insert(const float* __restrict__ pts, int64_t n, int ndim, VoxGeom g, S smp, uint64_t* __restrict__ table, uint32_t mask,
+                           int* __restrict__ slot, int* __restrict__ scalars) {
   const int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if constexpr (!S::kStacked) {
+    if (i == 0) { scalars[1] = static_cast<int>(n); }   // no break unless vox_assign finds one
+  }
   if (i >= n) return;
-  const int s = slot[i];
-  first[i] = (s >= 0 && slot_val(table[s]) == static_cast<uint32_t>(i)) ? 1 : 0;
+  int c[3];
+  if (!vox_cell(pts + i * ndim, g, c)) { slot[i] = -1; return; }
+  slot[i] = vox_claim(table, mask, smp.key_base(i, g) + vox_flat_key<uint64_t>(c, g), static_cast<uint32_t>(i));
 }
 
+// first[i] = 1 iff point i is the first of its voxel.  Stacked: first[] has n + 1 entries, the last one 0, so that the scan leaves the
+// number of first points in rank[n].
+template <class S>
+__global__ void vox_mark_first(int64_t n, const uint64_t* __restrict__ table, const int* __restrict__ slot, int* __restrict__ first) {
+  const int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (i >= n + S::kStacked) return;
+  int f = 0;
+  if (!S::kStacked || i < n) {
+    const int s = slot[i];
+    f = (s >= 0 && slot_val(table[s]) == static_cast<uint32_t>(i)) ? 1 : 0;
+  }
+  first[i] = f;
+}
+
+// ---- step 3, one cloud ----------------------------------------------------------------------------------------------------------------
 // rank[] holds the exclusive scan of the first-flags.
 __global__ void vox_assign(int64_t n, const uint64_t* __restrict__ table, const int* __restrict__ slot,
                            const int* __restrict__ rank, VoxGeom g, int max_voxels, int* __restrict__ coors,
@@ -83,10 +152,8 @@ __global__ void vox_assign(int64_t n, const uint64_t* __restrict__ table, const 
   const int v = rank[i];
   if (v == max_voxels) scalars[1] = static_cast<int>(i);  // unique writer: the reference's break point
   if (v >= max_voxels) return;
-  uint64_t key = slot_key(w);
-  const int x = static_cast<int>(key % g.grid[0]); key /= g.grid[0];
-  const int y = static_cast<int>(key % g.grid[1]);
-  const int z = static_cast<int>(key / g.grid[1]);
+  int z, y, x;
+  vox_decode(slot_key(w), g, z, y, x);
   coors[v * 3 + 0] = z; coors[v * 3 + 1] = y; coors[v * 3 + 2] = x;
 }
 
@@ -113,75 +180,7 @@ __global__ void vox_finalize_scalars(int max_voxels, int* __restrict__ scalars, 
   *num_voxels = m;
 }
 
-// start[] = exclusive scan of count[]; scalars[2] = kept points.
-__global__ void vox_fill(int64_t n, const float* __restrict__ pts, int ndim, const uint64_t* __restrict__ words,
-                         const int* __restrict__ start, const int* __restrict__ scalars, int max_points,
-                         float* __restrict__ voxels, int* __restrict__ num_per_voxel) {
-  const int64_t p = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-  if (p >= n || p >= scalars[2]) return;
-  const uint64_t w = words[p];
-  const int v = static_cast<int>(slot_key(w));
-  const int64_t i = slot_val(w);
-  const int pos = static_cast<int>(p) - start[v];
-  if (pos == 0) {
-    const int cnt = start[v + 1] - start[v];
-    num_per_voxel[v] = cnt < max_points ? cnt : max_points;
-  }
-  if (pos < max_points) {
-    float* dst = voxels + (static_cast<int64_t>(v) * max_points + pos) * ndim;
-    const float* src = pts + i * ndim;
-    for (int j = 0; j < ndim; ++j) dst[j] = src[j];
-  }
-}
-
-struct VoxWs {
-  uint64_t* table; uint32_t cap;
-  int* slot; int* rank; int* count; int* scalars;
-  uint64_t* words; uint64_t* tmp;
-  char* aux; size_t aux_bytes;
-};
-
-template <typename C>
-static void vox_carve(C& c, int64_t n, int max_voxels, VoxWs* w) {
-  const uint32_t cap = next_pow2(static_cast<uint64_t>(n > 512 ? n : 512) * 2);
-  size_t aux = radix_sort_ws_bytes(n);
-  size_t a2 = scan_ws_bytes(n > max_voxels + 1 ? n : max_voxels + 1);
-  if (a2 > aux) aux = a2;
-  if constexpr (std::is_same<C, Carver>::value) {
-    w->cap = cap;
-    w->table = c.template take<uint64_t>(cap);
-    w->slot = c.template take<int>(n);
-    w->rank = c.template take<int>(n);
-    w->count = c.template take<int>(max_voxels + 2);
-    w->scalars = c.template take<int>(8);
-    w->words = c.template take<uint64_t>(n);
-    w->tmp = c.template take<uint64_t>(n);
-    w->aux = c.template take<char>(aux);
-    w->aux_bytes = aux;
-  } else {
-    c.template take<uint64_t>(cap);
-    c.template take<int>(n);
-    c.template take<int>(n);
-    c.template take<int>(max_voxels + 2);
-    c.template take<int>(8);
-    c.template take<uint64_t>(n);
-    c.template take<uint64_t>(n);
-    c.template take<char>(aux);
-  }
-}
-
-// ---- stacked batch: B clouds of any sizes in one point buffer, one pass -------------------------------------------------------------
-// The same four steps with a sample index in every key:
-//   1. insert   : key = sample * grid volume + flat cell, payload = index into the STACKED buffer, so atomicMin still keeps the
-//                 first point of every (sample, voxel); a thread finds its sample by a binary search over the B + 1 offsets;
-//   2. order    : one scan of the first-flags over the whole buffer (n + 1 entries: rank[n] = all firsts); a first point's rank
-//                 inside its sample is rank[i] - rank[off[b]];
-//   3. cut-off  : per sample, the first-flagged point of rank max_voxels (found by a binary search over the monotone rank[]: the
-//                 smallest i of the sample with rank[i + 1] > rank[off[b]] + max_voxels); the sample's later points are dropped,
-//                 other samples are unaffected.  Sample b keeps M_b = min(distinct voxels, max_voxels) voxels, its output rows
-//                 start at base[b] = sum of M_a over a < b (vox_stack_bases: one workgroup, the only per-sample pass);
-//   4. slots    : kept points are keyed (output row, stacked point index) and sorted on the row bits, then filled as before.
-// The number of launches does not depend on B (the offsets reach the device as kernel arguments, 256 per launch).
+// ---- step 3, stacked ------------------------------------------------------------------------------------------------------------------
 constexpr int kOffChunk = 256;
 struct VoxOffsets { int v[kOffChunk]; };
 
@@ -192,62 +191,6 @@ __global__ __launch_bounds__(kOffChunk) void vox_stack_offsets(VoxOffsets o, int
 #pragma unroll
   for (int j = 0; j < kOffChunk; ++j) v = (j == t) ? o.v[j] : v;
   if (t < count) off[first + t] = v;
-}
-
-// sample of stacked row i: the b with off[b] <= i < off[b + 1] (empty samples have off[b] == off[b + 1] and own no row)
-__device__ __forceinline__ int vox_sample_of(const int* __restrict__ off, int batch, int i) {
-  int lo = 0, hi = batch;   // invariant: off[lo] <= i < off[hi]
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (off[mid] <= i) lo = mid; else hi = mid;
-  }
-  return lo;
-}
-
-__global__ void vox_stack_insert(const float* __restrict__ pts, int n, int ndim, VoxGeom g, const int* __restrict__ off, int batch,
-                                 uint64_t* __restrict__ table, uint32_t mask, int* __restrict__ slot) {
-  const int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const float* p = pts + i * ndim;
-  int c[3];
-  bool ok = true;
-#pragma unroll
-  for (int j = 0; j < 3; ++j) {
-    // fp32 subtract then fp32 divide then floor, as voxel_generator.py:188 (no reciprocal, no fma)
-    float f = floorf((p[j] - g.lo[j]) / g.vs[j]);
-    if (!(f >= 0.0f) || f >= static_cast<float>(g.grid[j])) ok = false;  // NaN -> dropped
-    c[j] = static_cast<int>(f);
-  }
-  if (!ok) { slot[i] = -1; return; }
-  const uint64_t vol = static_cast<uint64_t>(g.grid[0]) * g.grid[1] * g.grid[2];
-  const uint64_t key = static_cast<uint64_t>(vox_sample_of(off, batch, static_cast<int>(i))) * vol +
-                       (static_cast<uint64_t>(c[2]) * g.grid[1] + c[1]) * g.grid[0] + c[0];
-  const uint64_t word = slot_pack(key, static_cast<uint32_t>(i));
-  uint32_t h = hash_u64(key, mask);
-  while (true) {
-    unsigned long long old = atomicCAS(reinterpret_cast<unsigned long long*>(&table[h]),
-                                       static_cast<unsigned long long>(kEmptySlot),
-                                       static_cast<unsigned long long>(word));
-    if (old == kEmptySlot) break;
-    if (slot_key(old) == key) {
-      atomicMin(reinterpret_cast<unsigned long long*>(&table[h]), static_cast<unsigned long long>(word));
-      break;
-    }
-    h = (h + 1) & mask;
-  }
-  slot[i] = static_cast<int>(h);
-}
-
-// first[] has n + 1 entries; the last one is 0, so that the scan leaves the number of first points in rank[n]
-__global__ void vox_stack_mark_first(int n, const uint64_t* __restrict__ table, const int* __restrict__ slot, int* __restrict__ first) {
-  const int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-  if (i > n) return;
-  int f = 0;
-  if (i < n) {
-    const int s = slot[i];
-    f = (s >= 0 && slot_val(table[s]) == static_cast<uint32_t>(i)) ? 1 : 0;
-  }
-  first[i] = f;
 }
 
 // One workgroup.  base[b] = first output row of sample b (base[batch] = rows produced), cut[b] = the stacked index at which sample b's
@@ -287,32 +230,51 @@ __global__ __launch_bounds__(256) void vox_stack_bases(const int* __restrict__ o
 // Assign and words in one pass: every kept point gets its (output row, stacked index) word and counts into its row; the first point
 // of a voxel also writes the row's (b, z, y, x).
 __global__ void vox_stack_words(int n, const uint64_t* __restrict__ table, const int* __restrict__ slot, const int* __restrict__ rank,
-                                const int* __restrict__ off, int batch, const int* __restrict__ base, const int* __restrict__ cut,
-                                VoxGeom g, uint64_t* __restrict__ words, int* __restrict__ count, int* __restrict__ coords) {
+                                VoxStacked smp, const int* __restrict__ base, const int* __restrict__ cut, VoxGeom g,
+                                uint64_t* __restrict__ words, int* __restrict__ count, int* __restrict__ coords) {
   const int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const int s = slot[i];
   uint64_t w = ~0ull;
   if (s >= 0) {
-    const int b = vox_sample_of(off, batch, static_cast<int>(i));
+    const int b = smp.sample_of(static_cast<int>(i));
     if (i < cut[b]) {
       const uint64_t tw = table[s];
       const int f = static_cast<int>(slot_val(tw));
-      const int row = base[b] + rank[f] - rank[off[b]];   // f <= i < cut[b], so the rank inside the sample is below max_voxels
+      const int row = base[b] + rank[f] - rank[smp.off[b]];   // f <= i < cut[b], so the rank inside the sample is below max_voxels
       atomicAdd(&count[row], 1);
       w = slot_pack(static_cast<uint64_t>(row), static_cast<uint32_t>(i));
       if (f == static_cast<int>(i)) {
-        const uint64_t vol = static_cast<uint64_t>(g.grid[0]) * g.grid[1] * g.grid[2];
-        uint64_t key = slot_key(tw) - static_cast<uint64_t>(b) * vol;
-        const int x = static_cast<int>(key % g.grid[0]); key /= g.grid[0];
-        const int y = static_cast<int>(key % g.grid[1]);
-        const int z = static_cast<int>(key / g.grid[1]);
+        int z, y, x;
+        vox_decode(slot_key(tw) - static_cast<uint64_t>(b) * smp.volume(g), g, z, y, x);
         int* q = coords + static_cast<int64_t>(row) * 4;
         q[0] = b; q[1] = z; q[2] = y; q[3] = x;
       }
     }
   }
   words[i] = w;
+}
+
+// ---- step 4 ---------------------------------------------------------------------------------------------------------------------------
+// start[] = exclusive scan of count[]; scalars[2] = kept points.
+__global__ void vox_fill(int64_t n, const float* __restrict__ pts, int ndim, const uint64_t* __restrict__ words,
+                         const int* __restrict__ start, const int* __restrict__ scalars, int max_points,
+                         float* __restrict__ voxels, int* __restrict__ num_per_voxel) {
+  const int64_t p = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (p >= n || p >= scalars[2]) return;
+  const uint64_t w = words[p];
+  const int v = static_cast<int>(slot_key(w));
+  const int64_t i = slot_val(w);
+  const int pos = static_cast<int>(p) - start[v];
+  if (pos == 0) {
+    const int cnt = start[v + 1] - start[v];
+    num_per_voxel[v] = cnt < max_points ? cnt : max_points;
+  }
+  if (pos < max_points) {
+    float* dst = voxels + (static_cast<int64_t>(v) * max_points + pos) * ndim;
+    const float* src = pts + i * ndim;
+    for (int j = 0; j < ndim; ++j) dst[j] = src[j];
+  }
 }
 
 // MeanVFE straight from the sorted words: the sum over a row's first min(points, max_points) slots in slot order / max(that, 1) — the
@@ -331,61 +293,109 @@ __global__ __launch_bounds__(256) void vox_stack_mean(int64_t total, const float
   feats[t] = s / static_cast<float>(k < 1 ? 1 : k);
 }
 
-struct VoxStackWs {
+// ---- host side: one workspace, one front, one tail ------------------------------------------------------------------------------------
+struct VoxWs {
   uint64_t* table; uint32_t cap;
-  int* off; int* base; int* cut;
+  int* off; int* base; int* cut;   // stacked only
   int* slot; int* rank; int* count; int* scalars;
   uint64_t* words; uint64_t* tmp;
   char* aux; size_t aux_bytes;
 };
 
-// rows_cap: an upper bound of the output rows (the call's own sum of min(n_b, max_voxels), or min(n, B * max_voxels) for the query)
+// The workspace of n points and at most `rows` output rows; batch = 0: one cloud.  C is a Carver, or a Sizer for the size queries.
+// rows: max_voxels for one cloud; stacked, an upper bound of the packed rows (the call's own sum of min(n_b, max_voxels), or
+// min(n, B * max_voxels) for the query).
 template <typename C>
-static void vox_stack_carve(C& c, int64_t n, int batch, int64_t rows_cap, VoxStackWs* w) {
-  const uint32_t cap = next_pow2(static_cast<uint64_t>(n > 512 ? n : 512) * 2);
-  size_t aux = radix_sort_ws_bytes(n);
-  const size_t a2 = scan_ws_bytes((n > rows_cap ? n : rows_cap) + 1);
-  if (a2 > aux) aux = a2;
-  VoxStackWs l;
-  l.cap = cap;
-  l.table = c.template take<uint64_t>(cap);
-  l.off = c.template take<int>(static_cast<size_t>(batch) + 1);
-  l.base = c.template take<int>(static_cast<size_t>(batch) + 1);
-  l.cut = c.template take<int>(static_cast<size_t>(batch));
-  l.slot = c.template take<int>(n);
-  l.rank = c.template take<int>(n + 1);
-  l.count = c.template take<int>(rows_cap + 2);
-  l.scalars = c.template take<int>(8);
-  l.words = c.template take<uint64_t>(n);
-  l.tmp = c.template take<uint64_t>(n);
-  l.aux = c.template take<char>(aux);
-  l.aux_bytes = aux;
-  if constexpr (std::is_same<C, Carver>::value) *w = l;
+static VoxWs vox_carve(C& c, int64_t n, int batch, int64_t rows) {
+  const int64_t ranks = n + (batch ? 1 : 0);
+  VoxWs w = {};
+  w.cap = next_pow2(static_cast<uint64_t>(n > 512 ? n : 512) * 2);
+  w.aux_bytes = radix_sort_ws_bytes(n);
+  const size_t a2 = scan_ws_bytes(ranks > rows + 1 ? ranks : rows + 1);
+  if (a2 > w.aux_bytes) w.aux_bytes = a2;
+  w.table = c.template take<uint64_t>(w.cap);
+  if (batch) {
+    w.off = c.template take<int>(static_cast<size_t>(batch) + 1);
+    w.base = c.template take<int>(static_cast<size_t>(batch) + 1);
+    w.cut = c.template take<int>(static_cast<size_t>(batch));
+  }
+  w.slot = c.template take<int>(n);
+  w.rank = c.template take<int>(ranks);
+  w.count = c.template take<int>(rows + 2);
+  w.scalars = c.template take<int>(8);
+  w.words = c.template take<uint64_t>(n);
+  w.tmp = c.template take<uint64_t>(n);
+  w.aux = c.template take<char>(w.aux_bytes);
+  return w;
+}
+static size_t vox_ws_bytes(int64_t n, int batch, int64_t rows) {
+  Sizer s;
+  vox_carve(s, n, batch, rows);
+  return s.bytes();
 }
 
-struct CountOnly {   // vox_stack_carve over a Sizer: take() returns nothing to point at
-  Sizer s;
-  template <typename T>
-  T* take(size_t n) { s.take<T>(n); return nullptr; }
-};
+// The limits both device entry points share, after their own size and pointer checks (batch = 0: one cloud).
+static int vox_check_limits(const char* who, int64_t n, int batch, int max_voxels, const int grid[3]) {
+  const char* per = batch ? "batch * " : "";
+  const int b = batch ? batch : 1;
+  FV2P_REQUIRE(grid[0] > 0 && grid[1] > 0 && grid[2] > 0, FV2P_EINVAL, "%s: empty grid", who);
+  FV2P_REQUIRE(n <= kMaxRows, FV2P_ELIMIT, "%s: more than %lld points", who, (long long)kMaxRows);
+  FV2P_REQUIRE(static_cast<int64_t>(grid[0]) * grid[1] * grid[2] <= kMaxKey / b, FV2P_ELIMIT, "%s: %sgrid volume exceeds 2^40", who, per);
+  FV2P_REQUIRE(static_cast<int64_t>(b) * max_voxels <= kMaxRows, FV2P_ELIMIT, "%s: %smax_voxels too large", who, per);
+  return 0;
+}
+
+// Carves the workspace and clears it together with the outputs the caller has listed in `fill` (one launch).
+static int vox_open(const char* who, void* ws, size_t ws_bytes, int64_t n, int batch, int max_voxels, int64_t rows, FillJobs& fill, VoxWs* w,
+                    hipStream_t stream) {
+  const size_t need = batch ? fv2p_points_to_voxel_stack_ws_bytes(n, batch, max_voxels) : fv2p_points_to_voxel_ws_bytes(n, max_voxels);
+  FV2P_REQUIRE(ws && ws_bytes >= need, FV2P_EWORKSPACE, "%s: workspace too small", who);
+  Carver c(ws, ws_bytes);
+  *w = vox_carve(c, n, batch, rows);
+  fill.add(w->table, sizeof(uint64_t) * w->cap, 0xFFFFFFFFu);
+  fill.add(w->count, sizeof(int) * static_cast<size_t>(rows + 2), 0u);
+  if (!batch) fill.add(w->scalars, sizeof(int) * 8, 0u);
+  return multi_fill(fill, stream);
+}
+
+// Steps 1 and 2: rank[] = exclusive scan of the first-flags (one cloud: their total in scalars[0]; stacked: in rank[n]).
+template <class S>
+static int vox_rank_firsts(const S& smp, const float* points, int64_t n, int ndim, const VoxGeom& g, const VoxWs& w, hipStream_t stream) {
+  const int T = 256;
+  const int64_t ranks = n + S::kStacked;
+  hipLaunchKernelGGL(vox_insert<S>, dim3(static_cast<unsigned>(ceil_div(n, T))), dim3(T), 0, stream, points, n, ndim, g, smp, w.table, w.cap - 1,
+                     w.slot, w.scalars);
+  hipLaunchKernelGGL(vox_mark_first<S>, dim3(static_cast<unsigned>(ceil_div(ranks, T))), dim3(T), 0, stream, n, w.table, w.slot, w.rank);
+  return exclusive_scan_i32(w.rank, w.rank, ranks, S::kStacked ? nullptr : w.scalars + 0, w.aux, w.aux_bytes, stream);
+}
+
+// Step 4: the words sorted by output row (rows < `rows`, so the all-ones word of a dropped point sorts behind every kept one), count[]
+// turned into the rows' start offsets, then the padded (voxels, num_points) - unless voxels is null: the caller reads the sorted words itself.
+static int vox_sort_fill(const float* points, int64_t n, int ndim, int64_t rows, int max_points, const VoxWs& w, float* voxels, int* num_points,
+                         hipStream_t stream) {
+  const int vb = bits_for(static_cast<uint64_t>(rows));
+  int rc = radix_sort_u64(w.words, w.tmp, n, kValBits, kValBits + vb, w.aux, w.aux_bytes, stream);
+  if (rc) return rc;
+  rc = exclusive_scan_i32(w.count, w.count, rows + 1, w.scalars + 2, w.aux, w.aux_bytes, stream);
+  if (rc || !voxels) return rc;
+  hipLaunchKernelGGL(vox_fill, dim3(static_cast<unsigned>(ceil_div(n, 256))), dim3(256), 0, stream, n, points, ndim, w.words, w.count, w.scalars,
+                     max_points, voxels, num_points);
+  return 0;
+}
 
 static int64_t vox_stack_rows_bound(int64_t n, int batch, int max_voxels) {
   const int64_t bm = static_cast<int64_t>(batch) * max_voxels;
   return n < bm ? n : bm;
 }
 
-// Both forms: mean -> MeanVFE features, else padded (voxels, num_points).
+// Both stacked forms: mean -> MeanVFE features, else padded (voxels, num_points).
 static int vox_stack_run(bool mean, const float* points, int64_t n, int ndim, int batch, const int* counts, const float voxel_size[3],
                          const float range_lo[3], const int grid[3], int max_points, int max_voxels, float* voxels, float* feats,
                          int* coords, int* num_points, int* voxel_cnt, void* ws, size_t ws_bytes, hipStream_t stream, const char* who) {
   FV2P_REQUIRE(n >= 0 && ndim >= 3 && max_points >= 1 && max_voxels >= 1 && batch >= 1, FV2P_EINVAL,
                "%s: bad sizes n=%lld ndim=%d batch=%d max_points=%d max_voxels=%d", who, (long long)n, ndim, batch, max_points, max_voxels);
   FV2P_REQUIRE(counts && voxel_cnt && (points || n == 0), FV2P_EINVAL, "%s: null pointer", who);
-  FV2P_REQUIRE(grid[0] > 0 && grid[1] > 0 && grid[2] > 0, FV2P_EINVAL, "%s: empty grid", who);
-  FV2P_REQUIRE(n <= kMaxRows, FV2P_ELIMIT, "%s: more than %lld points", who, (long long)kMaxRows);
-  const int64_t vol = static_cast<int64_t>(grid[0]) * grid[1] * grid[2];
-  FV2P_REQUIRE(vol <= kMaxKey / batch, FV2P_ELIMIT, "%s: batch * grid volume exceeds 2^40", who);
-  FV2P_REQUIRE(static_cast<int64_t>(batch) * max_voxels <= kMaxRows, FV2P_ELIMIT, "%s: batch * max_voxels too large", who);
+  if (int rc = vox_check_limits(who, n, batch, max_voxels, grid)) return rc;
   int64_t sum = 0, rows_cap = 0;
   for (int b = 0; b < batch; ++b) {
     FV2P_REQUIRE(counts[b] >= 0, FV2P_EINVAL, "%s: negative point count of sample %d", who, b);
@@ -403,16 +413,9 @@ static int vox_stack_run(bool mean, const float* points, int64_t n, int ndim, in
   fill.add(coords, sizeof(int) * 4 * static_cast<size_t>(rows_cap), 0u);
   fill.add(voxel_cnt, sizeof(int) * static_cast<size_t>(batch), 0u);
   if (n == 0) return multi_fill(fill, stream);
-  FV2P_REQUIRE(ws && ws_bytes >= fv2p_points_to_voxel_stack_ws_bytes(n, batch, max_voxels), FV2P_EWORKSPACE, "%s: workspace too small", who);
-  Carver c(ws, ws_bytes);
-  VoxStackWs w;
-  vox_stack_carve(c, n, batch, rows_cap, &w);
-  VoxGeom g;
-  for (int j = 0; j < 3; ++j) { g.vs[j] = voxel_size[j]; g.lo[j] = range_lo[j]; g.grid[j] = grid[j]; }
-
-  fill.add(w.table, sizeof(uint64_t) * w.cap, 0xFFFFFFFFu);
-  fill.add(w.count, sizeof(int) * static_cast<size_t>(rows_cap + 2), 0u);
-  if (int rc = multi_fill(fill, stream)) return rc;
+  VoxWs w;
+  if (int rc = vox_open(who, ws, ws_bytes, n, batch, max_voxels, rows_cap, fill, &w, stream)) return rc;
+  const VoxGeom g = vox_geom(voxel_size, range_lo, grid);
   {
     VoxOffsets o;
     int64_t run = 0;   // off[k] = points before sample k, k = 0 .. batch
@@ -425,28 +428,16 @@ static int vox_stack_run(bool mean, const float* points, int64_t n, int ndim, in
       hipLaunchKernelGGL(vox_stack_offsets, dim3(1), dim3(kOffChunk), 0, stream, o, first, cnt, w.off);
     }
   }
-  const int T = 256;
-  const int ni = static_cast<int>(n);
-  const dim3 gridN(static_cast<unsigned>(ceil_div(n, T))), gridN1(static_cast<unsigned>(ceil_div(n + 1, T)));
-  hipLaunchKernelGGL(vox_stack_insert, gridN, dim3(T), 0, stream, points, ni, ndim, g, w.off, batch, w.table, w.cap - 1, w.slot);
-  hipLaunchKernelGGL(vox_stack_mark_first, gridN1, dim3(T), 0, stream, ni, w.table, w.slot, w.rank);
-  int rc = exclusive_scan_i32(w.rank, w.rank, n + 1, nullptr, w.aux, w.aux_bytes, stream);
-  if (rc) return rc;
+  const VoxStacked smp = {w.off, batch};
+  if (int rc = vox_rank_firsts(smp, points, n, ndim, g, w, stream)) return rc;
   hipLaunchKernelGGL(vox_stack_bases, dim3(1), dim3(256), 0, stream, w.off, batch, w.rank, max_voxels, w.base, w.cut, voxel_cnt);
-  hipLaunchKernelGGL(vox_stack_words, gridN, dim3(T), 0, stream, ni, w.table, w.slot, w.rank, w.off, batch, w.base, w.cut, g, w.words,
-                     w.count, coords);
-  // rows < rows_cap <= B * max_voxels, so the all-ones word of a dropped point sorts behind every kept one
-  const int vb = bits_for(static_cast<uint64_t>(rows_cap));
-  rc = radix_sort_u64(w.words, w.tmp, n, kValBits, kValBits + vb, w.aux, w.aux_bytes, stream);
-  if (rc) return rc;
-  rc = exclusive_scan_i32(w.count, w.count, rows_cap + 1, w.scalars + 2, w.aux, w.aux_bytes, stream);
-  if (rc) return rc;
+  hipLaunchKernelGGL(vox_stack_words, dim3(static_cast<unsigned>(ceil_div(n, 256))), dim3(256), 0, stream, static_cast<int>(n), w.table, w.slot,
+                     w.rank, smp, w.base, w.cut, g, w.words, w.count, coords);
+  if (int rc = vox_sort_fill(points, n, ndim, rows_cap, max_points, w, mean ? nullptr : voxels, num_points, stream)) return rc;
   if (mean) {
     const int64_t total = rows_cap * ndim;
     hipLaunchKernelGGL(vox_stack_mean, dim3(static_cast<unsigned>(ceil_div(total, 256))), dim3(256), 0, stream, total, points, ndim,
                        w.words, w.count, w.base + batch, max_points, feats);
-  } else {
-    hipLaunchKernelGGL(vox_fill, gridN, dim3(T), 0, stream, n, points, ndim, w.words, w.count, w.scalars, max_points, voxels, num_points);
   }
   FV2P_LAUNCH_CHECK();
   return 0;
@@ -460,9 +451,7 @@ extern "C" size_t fv2p_points_to_voxel_stack_ws_bytes(int64_t n_total, int batch
   if (n_total < 1) n_total = 1;
   if (batch < 1) batch = 1;
   if (max_voxels < 1) max_voxels = 1;
-  CountOnly s;
-  vox_stack_carve(s, n_total, batch, vox_stack_rows_bound(n_total, batch, max_voxels), static_cast<VoxStackWs*>(nullptr));
-  return s.s.bytes();
+  return vox_ws_bytes(n_total, batch, vox_stack_rows_bound(n_total, batch, max_voxels));
 }
 
 extern "C" int fv2p_points_to_voxel_stack(const float* points, int64_t n_total, int ndim, int batch, const int* counts,
@@ -484,9 +473,7 @@ extern "C" int fv2p_points_to_voxel_stack_mean(const float* points, int64_t n_to
 extern "C" size_t fv2p_points_to_voxel_ws_bytes(int64_t n_points, int max_voxels) {
   if (n_points < 1) n_points = 1;
   if (max_voxels < 1) max_voxels = 1;
-  Sizer s;
-  vox_carve(s, n_points, max_voxels, static_cast<VoxWs*>(nullptr));
-  return s.bytes();
+  return vox_ws_bytes(n_points, 0, max_voxels);
 }
 
 extern "C" int fv2p_points_to_voxel(const float* points, int64_t n, int ndim, const float voxel_size[3],
@@ -494,50 +481,26 @@ extern "C" int fv2p_points_to_voxel(const float* points, int64_t n, int ndim, co
                                     float* voxels, int* coors, int* num_points_per_voxel, int* num_voxels,
                                     void* ws, size_t ws_bytes, fv2p_stream_t stream_) {
   hipStream_t stream = static_cast<hipStream_t>(stream_);
+  const char* who = "points_to_voxel";
   FV2P_REQUIRE(n >= 0 && ndim >= 3 && max_points >= 1 && max_voxels >= 1, FV2P_EINVAL,
-               "points_to_voxel: bad sizes n=%lld ndim=%d max_points=%d max_voxels=%d", (long long)n, ndim,
-               max_points, max_voxels);
-  FV2P_REQUIRE(voxels && coors && num_points_per_voxel && num_voxels && (points || n == 0), FV2P_EINVAL,
-               "points_to_voxel: null pointer");
-  FV2P_REQUIRE(grid[0] > 0 && grid[1] > 0 && grid[2] > 0, FV2P_EINVAL, "points_to_voxel: empty grid");
-  FV2P_REQUIRE(n <= kMaxRows, FV2P_ELIMIT, "points_to_voxel: more than %lld points", (long long)kMaxRows);
-  FV2P_REQUIRE(static_cast<int64_t>(grid[0]) * grid[1] * grid[2] <= kMaxKey, FV2P_ELIMIT,
-               "points_to_voxel: grid volume exceeds 2^40");
-  FV2P_REQUIRE(max_voxels <= kMaxRows, FV2P_ELIMIT, "points_to_voxel: max_voxels too large");
+               "%s: bad sizes n=%lld ndim=%d max_points=%d max_voxels=%d", who, (long long)n, ndim, max_points, max_voxels);
+  FV2P_REQUIRE(voxels && coors && num_points_per_voxel && num_voxels && (points || n == 0), FV2P_EINVAL, "%s: null pointer", who);
+  if (int rc = vox_check_limits(who, n, 0, max_voxels, grid)) return rc;
   FillJobs fill;
   fill.add(voxels, sizeof(float) * max_voxels * (size_t)max_points * ndim, 0u);
   fill.add(coors, sizeof(int) * 3 * (size_t)max_voxels, 0u);
   fill.add(num_points_per_voxel, sizeof(int) * (size_t)max_voxels, 0u);
   fill.add(num_voxels, sizeof(int), 0u);
   if (n == 0) return multi_fill(fill, stream);
-  FV2P_REQUIRE(ws && ws_bytes >= fv2p_points_to_voxel_ws_bytes(n, max_voxels), FV2P_EWORKSPACE,
-               "points_to_voxel: workspace too small");
-  Carver c(ws, ws_bytes);
   VoxWs w;
-  vox_carve(c, n, max_voxels, &w);
-  VoxGeom g;
-  for (int j = 0; j < 3; ++j) { g.vs[j] = voxel_size[j]; g.lo[j] = range_lo[j]; g.grid[j] = grid[j]; }
-
-  fill.add(w.table, sizeof(uint64_t) * w.cap, 0xFFFFFFFFu);
-  fill.add(w.count, sizeof(int) * (max_voxels + 2), 0u);
-  fill.add(w.scalars, sizeof(int) * 8, 0u);
-  if (int rc = multi_fill(fill, stream)) return rc;
-  const int T = 256;
-  const dim3 gridN(static_cast<unsigned>(ceil_div(n, T)));
-  hipLaunchKernelGGL(vox_insert, gridN, dim3(T), 0, stream, points, n, ndim, g, w.table, w.cap - 1, w.slot, w.scalars);
-  hipLaunchKernelGGL(vox_mark_first, gridN, dim3(T), 0, stream, n, w.table, w.slot, w.rank);
-  int rc = exclusive_scan_i32(w.rank, w.rank, n, w.scalars + 0, w.aux, w.aux_bytes, stream);
-  if (rc) return rc;
-  hipLaunchKernelGGL(vox_assign, gridN, dim3(T), 0, stream, n, w.table, w.slot, w.rank, g, max_voxels, coors, w.scalars);
+  if (int rc = vox_open(who, ws, ws_bytes, n, 0, max_voxels, max_voxels, fill, &w, stream)) return rc;
+  const VoxGeom g = vox_geom(voxel_size, range_lo, grid);
+  if (int rc = vox_rank_firsts(VoxOne{}, points, n, ndim, g, w, stream)) return rc;
+  const dim3 gridN(static_cast<unsigned>(ceil_div(n, 256))), block(256);
+  hipLaunchKernelGGL(vox_assign, gridN, block, 0, stream, n, w.table, w.slot, w.rank, g, max_voxels, coors, w.scalars);
   hipLaunchKernelGGL(vox_finalize_scalars, dim3(1), dim3(1), 0, stream, max_voxels, w.scalars, num_voxels);
-  hipLaunchKernelGGL(vox_words, gridN, dim3(T), 0, stream, n, w.table, w.slot, w.rank, w.scalars, w.words, w.count);
-  const int vb = bits_for(static_cast<uint64_t>(max_voxels));
-  rc = radix_sort_u64(w.words, w.tmp, n, kValBits, kValBits + vb, w.aux, w.aux_bytes, stream);
-  if (rc) return rc;
-  rc = exclusive_scan_i32(w.count, w.count, max_voxels + 1, w.scalars + 2, w.aux, w.aux_bytes, stream);
-  if (rc) return rc;
-  hipLaunchKernelGGL(vox_fill, gridN, dim3(T), 0, stream, n, points, ndim, w.words, w.count, w.scalars, max_points,
-                     voxels, num_points_per_voxel);
+  hipLaunchKernelGGL(vox_words, gridN, block, 0, stream, n, w.table, w.slot, w.rank, w.scalars, w.words, w.count);
+  if (int rc = vox_sort_fill(points, n, ndim, max_voxels, max_points, w, voxels, num_points_per_voxel, stream)) return rc;
   FV2P_LAUNCH_CHECK();
   return 0;
 }
@@ -562,19 +525,13 @@ extern "C" int fv2p_points_to_voxel_host(const float* points, int64_t n, int ndi
   while (cap < 2 * static_cast<size_t>(max_voxels) + 2) cap <<= 1;
   std::vector<long long> keys(cap, -1);
   std::vector<int> vals(cap, 0);
+  const VoxGeom g = vox_geom(voxel_size, range_lo, grid);
   int count = 0;
   for (int64_t i = 0; i < n; ++i) {
     const float* p = points + i * ndim;
     int c[3];
-    bool inside = true;
-    for (int j = 0; j < 3; ++j) {
-      // fp32 subtract, fp32 divide, floor (voxel_generator.py:188); the file is built with -ffp-contract=off
-      const float q = std::floor((p[j] - range_lo[j]) / voxel_size[j]);
-      if (!(q >= 0.0f) || !(q < static_cast<float>(grid[j]))) { inside = false; break; }   // (:189-191; NaN coordinates are dropped too)
-      c[j] = static_cast<int>(q);
-    }
-    if (!inside) continue;
-    const long long key = (static_cast<long long>(c[2]) * grid[1] + c[1]) * grid[0] + c[0];
+    if (!vox_cell(p, g, c)) continue;
+    const long long key = vox_flat_key<long long>(c, g);
     size_t h = static_cast<size_t>(static_cast<unsigned long long>(key) * 0x9E3779B97F4A7C15ull) & (cap - 1);
     while (keys[h] != -1 && keys[h] != key) h = (h + 1) & (cap - 1);
     int idx;

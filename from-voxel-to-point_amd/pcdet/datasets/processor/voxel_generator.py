@@ -28,38 +28,6 @@ def _grid_size(voxel_size, coors_range):
     return np.round(g).astype(np.int64)
 
 
-def points_to_voxel_gpu(points, voxel_size, coors_range, max_points=35, reverse_index=True, max_voxels=20000):
-    """points: CUDA float32 tensor [N, ndim>=3]. Returns CUDA tensors sliced to the voxel count."""
-    import torch
-    _nat.require_cuda(points)
-    if points.dtype != torch.float32:
-        raise TypeError("points must be float32")
-    points = points.contiguous()
-    voxel_size = np.asarray(voxel_size, dtype=np.float32)
-    coors_range = np.asarray(coors_range, dtype=np.float32)
-    grid = _grid_size(voxel_size, coors_range)
-    n, ndim = points.shape
-    dev = points.device
-    voxels = torch.empty((max_voxels, max_points, ndim), dtype=torch.float32, device=dev)
-    coors = torch.empty((max_voxels, 3), dtype=torch.int32, device=dev)
-    num = torch.empty((max_voxels,), dtype=torch.int32, device=dev)
-    count = torch.empty((1,), dtype=torch.int32, device=dev)
-    with _nat.device_guard(dev):
-        ws_bytes = _nat.lib().fv2p_points_to_voxel_ws_bytes(n, max_voxels)
-        ws = _nat.workspace(ws_bytes, dev)
-        _nat.call("fv2p_points_to_voxel", points, n, ndim, voxel_size.tolist(), coors_range[:3].tolist(),
-                  [int(g) for g in grid], int(max_points), int(max_voxels), voxels, coors, num, count,
-                  ws, ws.numel(), _nat.stream())
-    m = int(count.item())
-    voxels, coors, num = voxels[:m], coors[:m], num[:m]
-    if not reverse_index:
-        coors = coors.flip(1).contiguous()
-    return voxels, coors, num
-
-
-_STREAMS = {}
-
-
 def _launch(points, voxel_size, coors_range, grid, max_points, max_voxels):
     """Enqueues one cloud's voxelisation on the current stream; no host synchronisation."""
     n, ndim = points.shape
@@ -73,6 +41,26 @@ def _launch(points, voxel_size, coors_range, grid, max_points, max_voxels):
     _nat.call("fv2p_points_to_voxel", points, n, ndim, voxel_size.tolist(), coors_range[:3].tolist(), [int(g) for g in grid],
               int(max_points), int(max_voxels), voxels, coors, num, count, ws, ws.numel(), _nat.stream())
     return voxels, coors, num, count
+
+
+def points_to_voxel_gpu(points, voxel_size, coors_range, max_points=35, reverse_index=True, max_voxels=20000):
+    """points: CUDA float32 tensor [N, ndim>=3]. Returns CUDA tensors sliced to the voxel count."""
+    _nat.require_cuda(points)
+    if points.dtype != torch.float32:
+        raise TypeError("points must be float32")
+    voxel_size = np.asarray(voxel_size, dtype=np.float32)
+    coors_range = np.asarray(coors_range, dtype=np.float32)
+    with _nat.device_guard(points.device):
+        voxels, coors, num, count = _launch(points.contiguous(), voxel_size, coors_range, _grid_size(voxel_size, coors_range), max_points,
+                                            max_voxels)
+    m = int(count.item())
+    voxels, coors, num = voxels[:m], coors[:m], num[:m]
+    if not reverse_index:
+        coors = coors.flip(1).contiguous()
+    return voxels, coors, num
+
+
+_STREAMS = {}
 
 
 def points_to_voxel_batch(points_list, voxel_size, coors_range, max_points=35, max_voxels=20000, mean_vfe=False, cloud_streams=True):
@@ -203,7 +191,6 @@ def points_to_voxel_stack_list(points_list, voxel_size, coors_range, max_points=
 
 def points_to_voxel(points, voxel_size, coors_range, max_points=35, reverse_index=True, max_voxels=20000):
     """Drop-in for the reference function of the same name (voxel_generator.py:75-133)."""
-    import torch
     if isinstance(points, torch.Tensor):
         return points_to_voxel_gpu(points, voxel_size, coors_range, max_points, reverse_index, max_voxels)
     pts = np.ascontiguousarray(points)
