@@ -38,34 +38,34 @@ __device__ __forceinline__ void static_for(F&& f) {
   }
 }
 
-struct ConvArgs {
-  const float* src; int ld_src; int c_src;          // c_src: valid source channels in this launch
-  const float* w; long long w_kstride; int w_ld;     // W_k = w + k*w_kstride, row stride w_ld
-  const int* tab; int n_dst; int kvol; int flip;
-  const float* bias;
-  float* dst; int ld_dst; int c_dst;                 // c_dst: valid destination channels in this launch
-  int accumulate;                                    // dst += result (used when the host splits c_src)
-  unsigned long long* trace;                         // optional per-workgroup placement/timing trace (test hook)
-  double* stats;                                     // optional [kStatSlots][2][stats_ld]: per-column sum / sum of squares of dst
-  int stats_ld;
+struct ConvArgs {   // a kernel argument: trivially copyable.  A launch starts from ConvArgs a{} and sets what it uses
+  const float* src = nullptr; int ld_src = 0; int c_src = 0;          // c_src: valid source channels in this launch
+  const float* w = nullptr; long long w_kstride = 0; int w_ld = 0;     // W_k = w + k*w_kstride, row stride w_ld
+  const int* tab = nullptr; int n_dst = 0; int kvol = 0; int flip = 0;
+  const float* bias = nullptr;
+  float* dst = nullptr; int ld_dst = 0; int c_dst = 0;                 // c_dst: valid destination channels in this launch
+  int accumulate = 0;                                                  // dst += result (used when the host splits c_src)
+  unsigned long long* trace = nullptr;                                 // optional per-workgroup placement/timing trace (test hook)
+  double* stats = nullptr;                                             // optional [kStatSlots][2][stats_ld]: per-column sum / sum of squares of dst
+  int stats_ld = 0;
   // backward-data conv whose result is the gradient of a BatchNorm(+ReLU) output: stats then receive that layer's
   // backward sums  (sum dz, sum dz * xhat), dz = dst * [y > 0], from the BatchNorm input bn_x (same shape as dst)
-  const float* bn_x; const float* bn_mean; const float* bn_invstd; const float* bn_gamma; const float* bn_beta; int bn_relu;
+  const float* bn_x = nullptr; const float* bn_mean = nullptr; const float* bn_invstd = nullptr; const float* bn_gamma = nullptr; const float* bn_beta = nullptr; int bn_relu = 0;
   // statistics finalised by the launch's LAST workgroup (conv_stats_done; bn_fold.hpp): on when fin_counter != nullptr
-  unsigned* fin_counter;                             // zero before the launch, zero again after it
-  double* fin_rows; double* fin_gslots; int fin_c;   // [tiles][2][stats_ld] rows, [groups][2][stats_ld] group slots (this launch's columns, unshifted by the kernels' column split), their number
-  int fin_groups, fin_col0;                          // groups the tiles fall into (tile % groups, <= kFinSubs); first column of the block a column-split kernel computes (set by the kernel)
-  BnFwdFin fin_fwd;                                  // forward statistics (bn_x == nullptr): mean / invstd / running statistics of these columns
-  BnBwdFin fin_bwd;                                  // backward sums (bn_x != nullptr): dgamma / dbeta / coef of these columns; coef rows are stats_ld apart
-  int fin_bump;                                      // forward: this launch also advances num_batches_tracked (the last column block of a layer)
+  unsigned* fin_counter = nullptr;                                     // zero before the launch, zero again after it
+  double* fin_rows = nullptr; double* fin_gslots = nullptr; int fin_c = 0;   // [tiles][2][stats_ld] rows, [groups][2][stats_ld] group slots (this launch's columns, unshifted by the kernels' column split), their number
+  int fin_groups = 1, fin_col0 = 0;                                    // groups the tiles fall into (tile % groups, <= kFinSubs); first column of the block a column-split kernel computes (set by the kernel)
+  BnFwdFin fin_fwd = {nullptr, nullptr, nullptr, nullptr, nullptr, 0.f, 0.f};   // forward statistics (bn_x == nullptr): mean / invstd / running statistics of these columns
+  BnBwdFin fin_bwd = {nullptr, nullptr, nullptr, 1};                   // backward sums (bn_x != nullptr): dgamma / dbeta / coef of these columns; coef rows are stats_ld apart
+  int fin_bump = 0;                                                    // forward: this launch also advances num_batches_tracked (the last column block of a layer)
   // BatchNorm (+ReLU) of the SOURCE rows applied on the gather (the reference's bn1 -> relu -> conv2 of a residual block in one kernel):
   // gathered value v of source channel c becomes relu?((v - pre_mean[c]) * pre_invstd[c] * pre_gamma[c] + pre_beta[c]); "no neighbour" stays 0
-  const float* pre_mean; const float* pre_invstd; const float* pre_gamma; const float* pre_beta; int pre_relu;
-  int dry;                                           // host only: choose the kernel, launch nothing (fv2p_sparse_conv_prenorm_supported)
-  const int* perm;                                   // optional row order: tile t owns destination rows perm[64t .. 64t+63]
-  const int* plan;                                   // optional cost-balanced tiling (conv_rows_ksplit): tile t owns rows [plan[t], plan[t+1])
-  int col_blocks;                                    // conv_rows_ksplit: 64-column blocks of a tile, decoded from blockIdx.x (0 / 1: one)
+  const float* pre_mean = nullptr; const float* pre_invstd = nullptr; const float* pre_gamma = nullptr; const float* pre_beta = nullptr; int pre_relu = 0;
+  const int* perm = nullptr;                                           // optional row order: tile t owns destination rows perm[64t .. 64t+63]
+  const int* plan = nullptr;                                           // optional cost-balanced tiling (conv_rows_ksplit): tile t owns rows [plan[t], plan[t+1])
+  int col_blocks = 0;                                                  // conv_rows_ksplit: 64-column blocks of a tile, decoded from blockIdx.x (0 / 1: one)
 };
+static_assert(std::is_trivially_copyable<ConvArgs>::value, "ConvArgs is passed to the kernels by value");
 
 // ---- BatchNorm statistics in the epilogue --------------------------------------------------------
 // Every conv of the reference's backbones feeds BatchNorm1d (spconv_backbone.py:8-27); its per-channel sum and sum of
@@ -2050,8 +2050,8 @@ __global__ __launch_bounds__(256) void wgrad_reduce(const float* __restrict__ pa
 }
 
 // ---- dispatch -----------------------------------------------------------------------------------
-// kernel variant: 0 = heuristic (LDS-DMA tile when the shapes allow, else the register-staged pipeline), 1 = plain
-// dense tile, 2 = compacted tile, 3 = register-staged pipeline.  FV2P_CONV_IMPL=dense|cmp|pipe presets it;
+// kernel variant: 0 = auto (the rules of choose_vec / choose_scalar), 1 = plain dense tile, 2 = compacted tile, 3 = register-staged
+// pipeline, 4 = the pair-compacted K-split tile wherever its shapes allow, else as 3.  FV2P_CONV_IMPL=dense|cmp|pipe|ksplit presets it;
 // fv2p_sparse_conv_set_impl() lets the parity tests run every variant in one process.
 static int g_conv_impl = -1;
 static int g_ksplit_auto = 1;   // FV2P_CONV_KSPLIT=0 keeps the round-1 kernels in auto mode (comparison runs)
@@ -2071,8 +2071,8 @@ static int conv_cu_count() {
 // -1 = not read yet (FV2P_CONV_THIN / FV2P_CONV_RES preset them, default on); fv2p_sparse_conv_set_paths() switches them at run time
 // so that the parity tests hold each kernel against the staged kernel it replaces in one process.
 static int g_thin_on = -1, g_res_on = -1, g_first_on = -1;
-constexpr int kThinDepth = 2;      // offsets in flight per wave of conv_rows_thin (measured: see launch_vec)
-constexpr int kRes16Default = 1;   // conv_rows_res at 16 source channels: the plain forward 16 -> 16 (see launch_vec)
+constexpr int kThinDepth = 2;      // offsets in flight per wave of conv_rows_thin (measured: see choose_vec)
+constexpr int kRes16Default = 1;   // conv_rows_res at 16 source channels: the plain forward 16 -> 16 (see choose_vec)
 static bool path_on(int& flag, const char* e) {   // e: the development preset (FV2P_DEV_ENV), null in the release library
   if (flag < 0) flag = (!e || atoi(e) != 0) ? 1 : 0;
   return flag != 0;
@@ -2168,80 +2168,88 @@ static int ksplit_rows(const ConvArgs& a) {
   return (!WT && a.n_dst < 65536) ? 32 : 64;
 }
 
-// launch unless the call only asks which kernel would run (a.dry: fv2p_sparse_conv_prenorm_supported)
-#define FV2P_LAUNCH(kern, grid, block, lds, stream, ...) do { if (!a.dry) hipLaunchKernelGGL(kern, grid, block, lds, stream, __VA_ARGS__); } while (0)
+// ---- choose, then launch ----------------------------------------------------------------------------------------------------------
+// choose_*: the kernel of a launch, ONE ordered list of rules each, the first that holds wins (table: DESIGN.md 3.2); launch_*: its launch
+enum class ConvKernel { ksplit, res, thin, act, dma, dma_split, pipe, vec, cmp, scalar, first,
+                        no_prenorm };   // a.pre_mean, and the kernel this launch would get cannot normalise its source rows
+struct ConvChoice {
+  ConvKernel kernel = ConvKernel::vec;
+  int rows = 64, level = -1, gps = 1;              // ksplit: rows per tile (32 / 64), level of the plan behind the table (plan_tiles(level) tiles; -1: equal-row tiles), row groups per step
+  int abl = 0;                                     // ksplit, development builds: timing-only ablation instance (FV2P_KSPLIT_ABL)
+  int depth = kThinDepth;                          // thin: offsets in flight per wave
+  int groups_per_wg = 0;                           // res: 16-row groups of a persistent workgroup (> 0: choose_vec sets it with every res choice; launch_vec divides by it)
+};
+using ConvLaunch = void (*)(const ConvChoice&, const ConvArgs&, hipStream_t);
+static ConvChoice choice_of(ConvKernel k) { ConvChoice c; c.kernel = k; return c; }
+static ConvArgs traced(ConvArgs a) { a.trace = g_conv_trace; return a; }   // ksplit, dma: with the test hook's trace
+// More dynamic LDS than the 64 KB a kernel gets by default, asked for once per instance.  false (the runtime refused): the rule that
+// wanted the kernel does not hold and the choice goes on to the next one.
+template <auto Kernel, int Bytes = 160 * 1024>
+static bool big_lds() {
+  static const bool ok = hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, Bytes) == hipSuccess;
+  return ok;
+}
+// "whole fragments, aligned": the launch fills its instance's channel padding and the named operands' 16-byte accesses exist and are aligned:
+//   ksplit, act, dma, dma_split: weights and destination (+ bias); their source is whole aligned float4 rows already (choose_conv's `vec`);
+//   res:  the source only - the weights go through scalar staging into LDS and the rows leave through conv_epilogue's dword stores;
+//   thin: the source, and the weights where transposed - W_k^T is one 16-byte load per lane, W_k four dword loads; conv_epilogue again.
+enum : unsigned { kOpSrc = 1, kOpW = 2, kOpDst = 4 };
+template <int CINP, int NB>
+static bool whole_fragments(const ConvArgs& a, unsigned ops) {
+  const bool src = (a.ld_src & 3) == 0 && (reinterpret_cast<uintptr_t>(a.src) & 15) == 0;
+  const bool w = (a.w_ld & 3) == 0 && (a.w_kstride & 3) == 0 && (reinterpret_cast<uintptr_t>(a.w) & 15) == 0;
+  const bool dst = (a.ld_dst & 3) == 0 && (reinterpret_cast<uintptr_t>(a.dst) & 15) == 0 && (!a.bias || (reinterpret_cast<uintptr_t>(a.bias) & 15) == 0);
+  return a.c_src == CINP && a.c_dst == NB * 16 && (src || !(ops & kOpSrc)) && (w || !(ops & kOpW)) && (dst || !(ops & kOpDst));
+}
+// the kernel templates that have an instance at <CINP, NB, WT>: what choose_vec may name and launch_vec must be able to launch
 template <int CINP, int NB, bool WT>
-static int launch_vec(const ConvArgs& a, hipStream_t s) {   // 0: launched (or chosen, a.dry); 1: the chosen kernel cannot normalise its source rows (a.pre_mean)
-  constexpr int TM = 128;
-  constexpr size_t cmp_lds = (static_cast<size_t>(CINP) * NB * 16 + static_cast<size_t>(TM) * (NB * 16 + 16)) * sizeof(float) + 2 * TM * sizeof(int);
-  const int impl = conv_impl();
-  const bool use_cmp = impl == 2 && cmp_lds <= 64 * 1024;  // measured slower than the dense tile at KITTI sizes (profiles/r01_*): opt-in
-  if (use_cmp) {
-    if (a.pre_mean) return 1;
-    const unsigned blocks = static_cast<unsigned>(ceil_div(a.n_dst, TM));
-    FV2P_LAUNCH((conv_rows_cmp<CINP, NB, WT, TM>), dim3(blocks), dim3(256), cmp_lds, s, a);
-    return 0;
-  }
-  const unsigned blocks = static_cast<unsigned>(ceil_div(a.n_dst, 64));
-  if constexpr ((CINP == 64 || CINP == 128) && NB % 4 == 0) {
-    // pair-compacted K-split tile: whole 64-column blocks, whole fragments
-    const bool whole = a.c_src == CINP && a.c_dst == NB * 16 && (a.w_ld & 3) == 0 && (a.w_kstride & 3) == 0 &&
-                       (reinterpret_cast<uintptr_t>(a.w) & 15) == 0 && (a.ld_dst & 3) == 0 &&
-                       (reinterpret_cast<uintptr_t>(a.dst) & 15) == 0 && (!a.bias || (reinterpret_cast<uintptr_t>(a.bias) & 15) == 0);
-    if (whole && a.kvol <= 27 && ksplit_wanted<CINP>(a)) {   // 27: a wave's step list holds 27 * MAXG + 1 entries (112 bytes, conv_rows_ksplit)
-      ConvArgs b = a; b.trace = g_conv_trace;
-      const int level = a.plan ? plan_pick_level(a.n_dst, NB / 4) : -1;   // a.plan: the plan header behind the table
-      b.plan = level >= 0 ? a.plan + plan_level_offset(level) : nullptr;
-      const unsigned tiles = level >= 0 ? static_cast<unsigned>(plan_tiles(level)) : 0u;
-      // row groups per step (FV2P_KSPLIT_GPS=2: two, the second multiplied only where it holds pairs)
-      const int gps = g_ksplit_gps == 2 ? 2 : 1;   // measured: two groups per step gain nothing at either size (KITTI 55 vs 53 us, Waymo 254 vs 256): opt-in
-      const size_t lds64 = ksplit_lds(64) + g_ksplit_pad;
-      if (level >= 0 || ksplit_rows<WT>(a) == 64) {
-        b.col_blocks = NB / 4;
-        const dim3 grid((level >= 0 ? tiles : blocks) * (NB / 4));
+struct VecShapes {
+  static constexpr bool ksplit = (CINP == 64 || CINP == 128) && NB % 4 == 0;
+  static constexpr bool res = (CINP == 32 || CINP == 16) && NB <= 2;
+  static constexpr bool thin = CINP == 16 && NB == 1;
+  static constexpr bool dma = CINP * NB <= 512 && (WT || NB % 4 == 0);   // conv_rows_act as well
+  static constexpr bool dma_split = CINP * NB == 1024 && NB == 8;
+  static constexpr bool pipe = CINP * NB <= 256;
+  static constexpr size_t cmp_lds = (static_cast<size_t>(CINP) * NB * 16 + static_cast<size_t>(128) * (NB * 16 + 16)) * sizeof(float) + 2 * 128 * sizeof(int);   // 128-row tiles
+  static constexpr size_t act_lds = 2 * CINP * NB * 16 * sizeof(float) + 32 * 64 * sizeof(int) + 16;
+};
+static int res16_mask() { static const int v = [] { const char* e = FV2P_DEV_ENV("FV2P_CONV_RES16"); return e ? atoi(e) : kRes16Default; }(); return v; }
+static int thin_depth() { static const int v = [] { const char* e = FV2P_DEV_ENV("FV2P_THIN_DEPTH"); return e ? atoi(e) : kThinDepth; }(); return v; }   // development overrides, read once: 2 / 4 / 6
 #ifdef FV2P_DEV   // timing-only ablation instances: development builds only (results INVALID by construction)
-        static const int abl = [] { const char* e = FV2P_DEV_ENV("FV2P_KSPLIT_ABL"); return e ? atoi(e) : 0; }();
-        if constexpr (CINP == 128 && !WT) {
-          if (abl) {   // timing-only ablations of the roofline layer's forward kernel (see the template's comment)
-#define FV2P_ABL(V) case V: { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_rows_ksplit<CINP, WT, 64, 1, V>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-                              FV2P_LAUNCH((conv_rows_ksplit<CINP, WT, 64, 1, V>), grid, dim3(256), lds64, s, b); return 0; }
-            switch (abl) { FV2P_ABL(1) FV2P_ABL(2) FV2P_ABL(3) FV2P_ABL(4) FV2P_ABL(5) FV2P_ABL(6) FV2P_ABL(7) FV2P_ABL(8) FV2P_ABL(9) FV2P_ABL(11) FV2P_ABL(15) default: break; }
-#undef FV2P_ABL
-          }
-        }
+#define FV2P_KSPLIT_ABLS(X) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(11) X(15)
+static int ksplit_abl() {   // FV2P_KSPLIT_ABL: one of the instances above, anything else counts as 0 (none)
+  static const int v = [] { const char* e = FV2P_DEV_ENV("FV2P_KSPLIT_ABL"); const int x = e ? atoi(e) : 0; return ((x >= 1 && x <= 9) || x == 11 || x == 15) ? x : 0; }();
+  return v;
+}
 #endif
-        if (a.pre_mean) {   // source rows normalised on the gather: forward convs only
-          if constexpr (!WT) {
-            static bool once = [] { return hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_rows_ksplit<CINP, WT, 64, 1, 0, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess; }();
-            if (once) { FV2P_LAUNCH((conv_rows_ksplit<CINP, WT, 64, 1, 0, true>), grid, dim3(256), lds64, s, b); return 0; }
-          }
-          return 1;
-        }
-        if (gps == 2) {
-          static bool once = [] { return hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_rows_ksplit<CINP, WT, 64, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess; }();
-          if (once) { FV2P_LAUNCH((conv_rows_ksplit<CINP, WT, 64, 2>), grid, dim3(256), lds64, s, b); return 0; }
-        } else {
-          static bool once = [] { return hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_rows_ksplit<CINP, WT, 64>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess; }();
-          if (once) { FV2P_LAUNCH((conv_rows_ksplit<CINP, WT, 64>), grid, dim3(256), lds64, s, b); return 0; }
-        }
+template <int CINP, int NB, bool WT>
+static ConvChoice choose_vec(const ConvArgs& a) {
+  using S = VecShapes<CINP, NB, WT>;
+  const ConvChoice no_prenorm = choice_of(ConvKernel::no_prenorm);
+  const int impl = conv_impl();
+  const bool pre = a.pre_mean != nullptr;
+  if (impl == 2 && S::cmp_lds <= 64 * 1024) return pre ? no_prenorm : choice_of(ConvKernel::cmp);  // measured slower than the dense tile at KITTI sizes (profiles/r01_*): opt-in
+  if constexpr (S::ksplit) {
+    // pair-compacted K-split tile: whole 64-column blocks, whole fragments
+    if (whole_fragments<CINP, NB>(a, kOpW | kOpDst) && a.kvol <= 27 && ksplit_wanted<CINP>(a)) {   // 27: a wave's step list holds 27 * MAXG + 1 entries (112 bytes, conv_rows_ksplit)
+      ConvChoice c = choice_of(ConvKernel::ksplit);
+      c.level = a.plan ? plan_pick_level(a.n_dst, NB / 4) : -1;   // a.plan: the plan header behind the table
+      if (c.level >= 0 || ksplit_rows<WT>(a) == 64) {
+#ifdef FV2P_DEV   // timing-only ablations of the roofline layer's forward kernel (see the template's comment)
+        if constexpr (CINP == 128 && !WT) { if ((c.abl = ksplit_abl()) != 0) return c; }
+#endif
+        // source rows normalised on the gather: forward convs only
+        if (pre) { if constexpr (!WT) { if (big_lds<&conv_rows_ksplit<CINP, WT, 64, 1, 0, true>>()) return c; } return no_prenorm; }
+        // row groups per step (FV2P_KSPLIT_GPS=2: two, the second multiplied only where it holds pairs)
+        c.gps = g_ksplit_gps == 2 ? 2 : 1;   // measured: two groups per step gain nothing at either size (KITTI 55 vs 53 us, Waymo 254 vs 256): opt-in
+        if (c.gps == 2 ? big_lds<&conv_rows_ksplit<CINP, WT, 64, 2>>() : big_lds<&conv_rows_ksplit<CINP, WT, 64>>()) return c;
       }
-      b.plan = nullptr;
-      {
-        const size_t lds = ksplit_lds(32) + g_ksplit_pad;
-        static bool once = [] { return hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_rows_ksplit<CINP, WT, 32>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess; }();
-        b.col_blocks = NB / 4;
-        if (a.pre_mean) {
-          if constexpr (!WT) {
-            static bool once_pre = [] { return hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_rows_ksplit<CINP, WT, 32, 1, 0, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess; }();
-            if (once_pre) { FV2P_LAUNCH((conv_rows_ksplit<CINP, WT, 32, 1, 0, true>), dim3(static_cast<unsigned>(ceil_div(a.n_dst, 32)) * (NB / 4)), dim3(256), lds, s, b); return 0; }
-          }
-          return 1;
-        }
-        if (once) { FV2P_LAUNCH((conv_rows_ksplit<CINP, WT, 32>), dim3(static_cast<unsigned>(ceil_div(a.n_dst, 32)) * (NB / 4)), dim3(256), lds, s, b); return 0; }
-      }
+      c = choice_of(ConvKernel::ksplit); c.rows = 32;   // 32-row tiles: no plan, one group per step
+      if (pre) { if constexpr (!WT) { if (big_lds<&conv_rows_ksplit<CINP, WT, 32, 1, 0, true>>()) return c; } return no_prenorm; }
+      if (big_lds<&conv_rows_ksplit<CINP, WT, 32>>()) return c;
     }
   }
-  if constexpr ((CINP == 32 || CINP == 16) && NB <= 2) {
+  if constexpr (S::res) {
     // 32 source channels, full 3 x 3 x 3 kernel: every W_k resident in LDS, one persistent workgroup of 16 waves per CU
     // 16 source channels, FORWARD only: 11.7 against 14.0 us of conv_rows_thin at 35 k rows (whose non-transposed weight fragment is four
     // dword loads per offset and wave); backward data (one 16-byte load) is equal on both, 11.7 / 11.8, and stays on conv_rows_thin.
@@ -2249,152 +2257,152 @@ static int launch_vec(const ConvArgs& a, hipStream_t s) {   // 0: launched (or c
     // backbone (batch 4) / plain backbone, ms per step: 0: 3.738 / 1.690, 1: 3.758 / 1.645, 3: 3.703 / -, 7: 3.835 / 1.669 (all within the
     // +- 0.03 of repeated runs).  Inside the FV2P step (rocprofv3, launches that also finalise their BatchNorm sums): plain forward 22.7 us
     // on either kernel, the PRE form 26.1 here against 24.2 on conv_rows_thin -> 1: the plain forward only.
-    static const int res16 = [] { const char* e = FV2P_DEV_ENV("FV2P_CONV_RES16"); return e ? atoi(e) : kRes16Default; }();
-    const bool pre = a.pre_mean != nullptr;
+    const int res16 = res16_mask();
     const bool res16_here = !WT && (res16 & 1) && (NB == 1 || (res16 & 4)) && (!pre || (res16 & 2));
     const bool res_on = path_on(g_res_on, FV2P_DEV_ENV("FV2P_CONV_RES")) && (CINP == 32 || res16_here);
-    const bool whole = a.c_src == CINP && a.c_dst == NB * 16 && (a.ld_src & 3) == 0 && (reinterpret_cast<uintptr_t>(a.src) & 15) == 0;
-    constexpr size_t res_lds = static_cast<size_t>(27) * CINP * NB * 16 * sizeof(float);
     // measured (tools/microbench.py conv): subm 32 -> 32 at 39 k rows 29.4 us forward / 29.4 us backward data against 34.7 / 32.3 us of the
     // staged kernels; at 286 k rows (Waymo) 170 / 170 against 168 / 156 us - with several groups per wave the staged kernels' shared fragment wins back
-    if (impl == 0 && res_on && whole && a.kvol == 27 && !a.perm && a.n_dst <= 65536) {
+    if (impl == 0 && res_on && whole_fragments<CINP, NB>(a, kOpSrc) && a.kvol == 27 && !a.perm && a.n_dst <= 65536) {
+      ConvChoice c = choice_of(ConvKernel::res);
       const int groups = static_cast<int>(ceil_div(a.n_dst, 16));
-      const int wgs = std::min(groups, conv_cu_count());
-      const int per = static_cast<int>(ceil_div(groups, wgs));
-      if (pre) {
-        // (no PRE form at 32 channels: normalising the gathered rows pushed this 128-register, 16-wave kernel into scratch - 66.8 against
-        //  47.1 us at 39 k rows, more than the 5.6 us apply launch it saves; 32-channel consumers read materialised rows)
-        if constexpr (CINP == 16 && !WT) {
-          static bool once_pre = [] { return hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_rows_res<CINP, NB, WT, 27, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess; }();
-          if (once_pre) { FV2P_LAUNCH((conv_rows_res<CINP, NB, WT, 27, true>), dim3(static_cast<unsigned>(ceil_div(groups, per))), dim3(1024), std::max(res_lds, kStatsDoneLds), s, a, per); return 0; }
-        }
-        return 1;
-      }
-      static bool once = [] { return hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_rows_res<CINP, NB, WT, 27>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess; }();
-      if (once) {
-        FV2P_LAUNCH((conv_rows_res<CINP, NB, WT, 27>), dim3(static_cast<unsigned>(ceil_div(groups, per))), dim3(1024), std::max(res_lds, kStatsDoneLds), s, a, per);
-        return 0;
-      }
+      c.groups_per_wg = static_cast<int>(ceil_div(groups, std::min(groups, conv_cu_count())));
+      // (no PRE form at 32 channels: normalising the gathered rows pushed this 128-register, 16-wave kernel into scratch - 66.8 against
+      //  47.1 us at 39 k rows, more than the 5.6 us apply launch it saves; 32-channel consumers read materialised rows)
+      if (pre) { if constexpr (CINP == 16 && !WT) { if (big_lds<&conv_rows_res<CINP, NB, WT, 27, true>>()) return c; } return no_prenorm; }
+      if (big_lds<&conv_rows_res<CINP, NB, WT, 27>>()) return c;
     }
   }
-  if constexpr (CINP == 16 && NB == 1) {
+  if constexpr (S::thin) {
     // 16 -> 16 with the full 3 x 3 x 3 kernel: one wave per 16 rows, operands straight into registers two offsets ahead.  Measured
     // (FV2P_RES=1 tools/microbench.py conv, 35 k rows): 13.4 us forward / 11.5 us backward data against 14.9 / 13.5 us of the staged
     // kernels.  NOT at 32 channels: 49 against 35 us (subm 32 -> 32, 39 k rows), 22.4 against 20.1 us (16 -> 32) - a 4 KB weight
     // fragment per wave and offset through the vector-memory path costs more than the barrier it removes (LDS staging shares it
     // between the four waves of a workgroup).
     const bool thin_on = path_on(g_thin_on, FV2P_DEV_ENV("FV2P_CONV_THIN"));
-    const bool whole = a.c_src == CINP && a.c_dst == NB * 16 && (a.ld_src & 3) == 0 && (reinterpret_cast<uintptr_t>(a.src) & 15) == 0 &&
-                       (!WT || ((a.w_ld & 3) == 0 && (a.w_kstride & 3) == 0 && (reinterpret_cast<uintptr_t>(a.w) & 15) == 0));
-    if (impl == 0 && thin_on && whole && a.kvol == 27 && !a.perm) {
-      const unsigned groups = static_cast<unsigned>(ceil_div(a.n_dst, 16));
-      static const int depth = [] { const char* e = FV2P_DEV_ENV("FV2P_THIN_DEPTH"); return e ? atoi(e) : kThinDepth; }();   // development: 2 / 4 / 6
-      if (a.pre_mean) {
-        if constexpr (!WT) {
-          if (depth == 4) FV2P_LAUNCH((conv_rows_thin<CINP, NB, WT, 27, true, 4>), dim3(ceil_div(groups, 4u)), dim3(256), kStatsDoneLds, s, a);
-          else if (depth == 6) FV2P_LAUNCH((conv_rows_thin<CINP, NB, WT, 27, true, 6>), dim3(ceil_div(groups, 4u)), dim3(256), kStatsDoneLds, s, a);
-          else FV2P_LAUNCH((conv_rows_thin<CINP, NB, WT, 27, true>), dim3(ceil_div(groups, 4u)), dim3(256), kStatsDoneLds, s, a);
-          return 0;
-        }
-        return 1;
-      }
-      if (depth == 4) FV2P_LAUNCH((conv_rows_thin<CINP, NB, WT, 27, false, 4>), dim3(ceil_div(groups, 4u)), dim3(256), kStatsDoneLds, s, a);
-      else if (depth == 6) FV2P_LAUNCH((conv_rows_thin<CINP, NB, WT, 27, false, 6>), dim3(ceil_div(groups, 4u)), dim3(256), kStatsDoneLds, s, a);
-      else FV2P_LAUNCH((conv_rows_thin<CINP, NB, WT, 27>), dim3(ceil_div(groups, 4u)), dim3(256), kStatsDoneLds, s, a);
-      return 0;
+    if (impl == 0 && thin_on && whole_fragments<CINP, NB>(a, WT ? kOpSrc | kOpW : kOpSrc) && a.kvol == 27 && !a.perm) {
+      ConvChoice c = choice_of(ConvKernel::thin);
+      c.depth = thin_depth();
+      return pre && WT ? no_prenorm : c;   // the PRE form: forward convs only
     }
   }
-  if (a.pre_mean) return 1;   // the staged kernels below read their source rows as they are
-  if constexpr (CINP * NB <= 512 && (WT || NB % 4 == 0)) {
+  if (pre) return no_prenorm;   // the staged kernels below read their source rows as they are
+  if constexpr (S::dma) {
     // LDS-DMA kernel: whole fragments only (every lane's 16-byte source must exist and be aligned)
-    const bool whole = a.c_src == CINP && a.c_dst == NB * 16 && (a.w_ld & 3) == 0 && (a.w_kstride & 3) == 0 &&
-                       (reinterpret_cast<uintptr_t>(a.w) & 15) == 0 && (a.ld_dst & 3) == 0 &&
-                       (reinterpret_cast<uintptr_t>(a.dst) & 15) == 0 && (!a.bias || (reinterpret_cast<uintptr_t>(a.bias) & 15) == 0);
-    constexpr size_t act_lds = 2 * CINP * NB * 16 * sizeof(float) + 32 * 64 * sizeof(int) + 16;
-    if (a.perm && impl == 0 && whole && a.kvol > 1 && a.kvol <= 32 && act_lds <= 64 * 1024) {
-      FV2P_LAUNCH((conv_rows_act<CINP, NB, WT>), dim3(blocks), dim3(256), act_lds, s, a);
-      return 0;
-    }
-    if (impl == 0 && whole && a.kvol > 1) {
-      ConvArgs b = a; b.trace = g_conv_trace;
-      FV2P_LAUNCH((conv_rows_dma<CINP, NB, WT>), dim3(blocks), dim3(256), std::max<size_t>(2 * CINP * NB * 16 * sizeof(float), kStatsDoneLds), s, b);
-      return 0;
-    }
+    const bool whole = whole_fragments<CINP, NB>(a, kOpW | kOpDst);
+    if (a.perm && impl == 0 && whole && a.kvol > 1 && a.kvol <= 32 && S::act_lds <= 64 * 1024) return choice_of(ConvKernel::act);
+    if (impl == 0 && whole && a.kvol > 1) return choice_of(ConvKernel::dma);
   }
-  if constexpr (CINP * NB == 1024 && NB == 8) {
+  if constexpr (S::dma_split) {
     // 128 -> 128: the LDS-DMA kernel on two column halves (grid.y), 2 x 32 KB of weights per workgroup.  The gathered rows are
     // read by both halves (L2 hits); twice the workgroups also fill the chip better at the 10 k rows these layers have.
-    const bool whole = a.c_src == CINP && a.c_dst == NB * 16 && (a.w_ld & 3) == 0 && (a.w_kstride & 3) == 0 &&
-                       (reinterpret_cast<uintptr_t>(a.w) & 15) == 0 && (a.ld_dst & 3) == 0 &&
-                       (reinterpret_cast<uintptr_t>(a.dst) & 15) == 0 && (!a.bias || (reinterpret_cast<uintptr_t>(a.bias) & 15) == 0);
-    if (impl == 0 && whole && a.kvol > 1) {
-      ConvArgs b = a; b.trace = nullptr;
-      FV2P_LAUNCH((conv_rows_dma<CINP, 4, WT>), dim3(blocks, 2), dim3(256), 2 * CINP * 4 * 16 * sizeof(float), s, b);
-      return 0;
-    }
+    if (impl == 0 && whole_fragments<CINP, NB>(a, kOpW | kOpDst) && a.kvol > 1) return choice_of(ConvKernel::dma_split);
   }
-  if constexpr (CINP * NB <= 256) {
-    if (impl != 1 && a.kvol > 1) {  // FV2P_CONV_IMPL=dense keeps the unpipelined tile, =pipe the register-staged pipeline (parity tests run all)
-      // KU = 2 (two offsets per barrier) measured slower than KU = 1 on MI355X (93.9 vs 89.6 us, 64->64 N=29k)
-      FV2P_LAUNCH((conv_rows_pipe<CINP, NB, WT, 1>), dim3(blocks), dim3(256), std::max<size_t>(2 * CINP * NB * 16 * sizeof(float), kStatsDoneLds), s, a);
-      return 0;
-    }
+  if constexpr (S::pipe) {
+    // FV2P_CONV_IMPL=dense keeps the unpipelined tile, =pipe the register-staged pipeline (parity tests run all)
+    // KU = 2 (two offsets per barrier) measured slower than KU = 1 on MI355X (93.9 vs 89.6 us, 64->64 N=29k)
+    if (impl != 1 && a.kvol > 1) return choice_of(ConvKernel::pipe);
   }
-  FV2P_LAUNCH((conv_rows_vec<CINP, NB, WT>), dim3(blocks), dim3(256), std::max<size_t>(CINP * NB * 16 * sizeof(float), kStatsDoneLds), s, a);
-  return 0;
+  return choice_of(ConvKernel::vec);
+}
+template <int CINP, int NB, bool WT>
+static void launch_vec(const ConvChoice& c, const ConvArgs& a, hipStream_t s) {
+  using S = VecShapes<CINP, NB, WT>;
+  const dim3 tiles64(static_cast<unsigned>(ceil_div(a.n_dst, 64))), block(256);
+  const unsigned groups = static_cast<unsigned>(ceil_div(a.n_dst, 16));
+  const bool pre = a.pre_mean != nullptr;
+  constexpr size_t w_lds = CINP * NB * 16 * sizeof(float);   // one W_k
+  switch (c.kernel) {
+    case ConvKernel::cmp: hipLaunchKernelGGL((conv_rows_cmp<CINP, NB, WT, 128>), dim3(static_cast<unsigned>(ceil_div(a.n_dst, 128))), block, S::cmp_lds, s, a); break;
+    case ConvKernel::ksplit:
+      if constexpr (S::ksplit) {
+        ConvArgs b = traced(a); b.col_blocks = NB / 4;
+        b.plan = c.level >= 0 ? a.plan + plan_level_offset(c.level) : nullptr;
+        const dim3 grid((c.level >= 0 ? static_cast<unsigned>(plan_tiles(c.level)) : static_cast<unsigned>(ceil_div(a.n_dst, c.rows))) * (NB / 4));
+        const size_t lds = ksplit_lds(c.rows) + g_ksplit_pad;
+#define FV2P_KSPLIT(...) hipLaunchKernelGGL((conv_rows_ksplit<CINP, WT, __VA_ARGS__>), grid, block, lds, s, b)
+#ifdef FV2P_DEV
+#define FV2P_ABL(V) case V: (void)big_lds<&conv_rows_ksplit<CINP, WT, 64, 1, V>>(); FV2P_KSPLIT(64, 1, V); break;
+        if constexpr (CINP == 128 && !WT) { if (c.abl) { switch (c.abl) { FV2P_KSPLIT_ABLS(FV2P_ABL) default: break; } break; } }
+#undef FV2P_ABL
+#endif
+        if (pre) {
+          if constexpr (!WT) { if (c.rows == 64) FV2P_KSPLIT(64, 1, 0, true); else FV2P_KSPLIT(32, 1, 0, true); }
+        } else if (c.gps == 2) FV2P_KSPLIT(64, 2);
+        else if (c.rows == 64) FV2P_KSPLIT(64);
+        else FV2P_KSPLIT(32);
+#undef FV2P_KSPLIT
+      }
+      break;
+    case ConvKernel::res:
+      if constexpr (S::res) {
+        const dim3 grid(static_cast<unsigned>(ceil_div(groups, c.groups_per_wg)));
+        const size_t lds = std::max(27 * w_lds, kStatsDoneLds);
+        if (!pre) hipLaunchKernelGGL((conv_rows_res<CINP, NB, WT, 27>), grid, dim3(1024), lds, s, a, c.groups_per_wg);
+        if constexpr (CINP == 16 && !WT) { if (pre) hipLaunchKernelGGL((conv_rows_res<CINP, NB, WT, 27, true>), grid, dim3(1024), lds, s, a, c.groups_per_wg); }
+      }
+      break;
+    case ConvKernel::thin:
+      if constexpr (S::thin) {
+        const dim3 grid(static_cast<unsigned>(ceil_div(groups, 4)));
+#define FV2P_THIN(PRE, DEPTH) hipLaunchKernelGGL((conv_rows_thin<CINP, NB, WT, 27, PRE, DEPTH>), grid, block, kStatsDoneLds, s, a)
+#define FV2P_THIN_DEPTH(PRE) do { if (c.depth == 4) FV2P_THIN(PRE, 4); else if (c.depth == 6) FV2P_THIN(PRE, 6); else FV2P_THIN(PRE, kThinDepth); } while (0)
+        if (pre) { if constexpr (!WT) FV2P_THIN_DEPTH(true); } else FV2P_THIN_DEPTH(false);
+#undef FV2P_THIN_DEPTH
+#undef FV2P_THIN
+      }
+      break;
+    case ConvKernel::act: if constexpr (S::dma) hipLaunchKernelGGL((conv_rows_act<CINP, NB, WT>), tiles64, block, S::act_lds, s, a); break;
+    case ConvKernel::dma: if constexpr (S::dma) hipLaunchKernelGGL((conv_rows_dma<CINP, NB, WT>), tiles64, block, std::max(2 * w_lds, kStatsDoneLds), s, traced(a)); break;
+    case ConvKernel::dma_split: if constexpr (S::dma_split) hipLaunchKernelGGL((conv_rows_dma<CINP, 4, WT>), dim3(tiles64.x, 2), block, 2 * CINP * 4 * 16 * sizeof(float), s, a); break;   // (untraced)
+    case ConvKernel::pipe: if constexpr (S::pipe) hipLaunchKernelGGL((conv_rows_pipe<CINP, NB, WT, 1>), tiles64, block, std::max(2 * w_lds, kStatsDoneLds), s, a); break;
+    case ConvKernel::vec: hipLaunchKernelGGL((conv_rows_vec<CINP, NB, WT>), tiles64, block, std::max(w_lds, kStatsDoneLds), s, a); break;
+    default: break;   // scalar, first: launch_scalar's; no_prenorm: nothing to launch
+  }
 }
 template <int STEPS, int NB, bool WT>
-static int launch_scalar(const ConvArgs& a, hipStream_t s) {
-  if (a.pre_mean) return 1;
-  const unsigned blocks = static_cast<unsigned>(ceil_div(a.n_dst, 64));
-  if constexpr (!WT && STEPS * NB <= 2) {
-    // the backbones' first layer (4 or 5 point features -> 16 / 32 channels, 27 offsets): everything in registers, no barrier.  Measured
-    // (FV2P_RES=1 tools/microbench.py conv, subm 4 -> 16 at 35 146 rows): see profiles/README.md, round 6
-    if (conv_impl() == 0 && path_on(g_first_on, FV2P_DEV_ENV("FV2P_CONV_FIRST")) && a.kvol == 27 && !a.perm) {
-      FV2P_LAUNCH((conv_rows_first<STEPS, NB, 27>), dim3(blocks), dim3(256), kStatsDoneLds, s, a);
-      return 0;
-    }
-  }
-  FV2P_LAUNCH((conv_rows_scalar<STEPS, NB, WT>), dim3(blocks), dim3(256), std::max<size_t>(STEPS * 4 * NB * 16 * sizeof(float), kStatsDoneLds), s, a);
-  return 0;
+static ConvChoice choose_scalar(const ConvArgs& a) {
+  if (a.pre_mean) return choice_of(ConvKernel::no_prenorm);
+  // the backbones' first layer (4 or 5 point features -> 16 / 32 channels, 27 offsets): everything in registers, no barrier.  Measured
+  // (FV2P_RES=1 tools/microbench.py conv, subm 4 -> 16 at 35 146 rows): see profiles/README.md, round 6
+  const bool first = !WT && STEPS * NB <= 2 && conv_impl() == 0 && path_on(g_first_on, FV2P_DEV_ENV("FV2P_CONV_FIRST")) && a.kvol == 27 && !a.perm;
+  return choice_of(first ? ConvKernel::first : ConvKernel::scalar);
 }
-
+template <int STEPS, int NB, bool WT>
+static void launch_scalar(const ConvChoice& c, const ConvArgs& a, hipStream_t s) {
+  const dim3 tiles64(static_cast<unsigned>(ceil_div(a.n_dst, 64))), block(256);
+  if (c.kernel == ConvKernel::scalar)
+    hipLaunchKernelGGL((conv_rows_scalar<STEPS, NB, WT>), tiles64, block, std::max<size_t>(STEPS * 4 * NB * 16 * sizeof(float), kStatsDoneLds), s, a);
+  if constexpr (!WT && STEPS * NB <= 2) {
+    if (c.kernel == ConvKernel::first) hipLaunchKernelGGL((conv_rows_first<STEPS, NB, 27>), tiles64, block, kStatsDoneLds, s, a);
+  }
+}
+// Channel counts are padded to 1 / 2 / 4 / 8 blocks, which select the template instance: f(integral_constant<MB>{}, integral_constant<NB>{})
+static int pad_blocks(int blocks) { return blocks <= 1 ? 1 : blocks <= 2 ? 2 : blocks <= 4 ? 4 : 8; }   // callers bound blocks to 8 (<= 128 channels per launch)
+template <int N> using Blocks = std::integral_constant<int, N>;
+template <class F> static void for_blocks(int padded, F&& f) {
+  switch (padded) { case 1: f(Blocks<1>{}); break; case 2: f(Blocks<2>{}); break; case 4: f(Blocks<4>{}); break; default: f(Blocks<8>{}); break; }
+}
+template <class F> static void for_block_pair(int mb_padded, int nb_padded, F&& f) {
+  for_blocks(mb_padded, [&](auto mb) { for_blocks(nb_padded, [&](auto nb) { f(mb, nb); }); });
+}
+// the instance of a launch (padded source channels, column blocks): its choice and the function that launches it
 template <bool WT>
-static int dispatch_conv(const ConvArgs& a, hipStream_t s) {
-  const int nb = static_cast<int>(ceil_div(a.c_dst, 16));
-  const int nbp = nb <= 1 ? 1 : nb <= 2 ? 2 : nb <= 4 ? 4 : 8;
-  const bool vec = (a.c_src % 4 == 0) && (a.ld_src % 4 == 0) && a.c_src >= 16 &&
-                   (reinterpret_cast<uintptr_t>(a.src) % 16 == 0);
-  int unsupported = 0;   // 1: a.pre_mean with a kernel that cannot normalise its source rows (nothing was launched)
-#define FV2P_VEC_CASE(CINP)                                            \
-  switch (nbp) {                                                       \
-    case 1: unsupported = launch_vec<CINP, 1, WT>(a, s); break;        \
-    case 2: unsupported = launch_vec<CINP, 2, WT>(a, s); break;        \
-    case 4: unsupported = launch_vec<CINP, 4, WT>(a, s); break;        \
-    default: unsupported = launch_vec<CINP, 8, WT>(a, s); break;       \
+static int choose_conv(const ConvArgs& a, ConvChoice& c, ConvLaunch* launch = nullptr) {   // launch: null when only the choice is asked
+  const int nbp = pad_blocks(ceil_div(a.c_dst, 16));
+  const bool vec = (a.c_src % 4 == 0) && (a.ld_src % 4 == 0) && a.c_src >= 16 && (reinterpret_cast<uintptr_t>(a.src) % 16 == 0);
+  if (vec) {   // 16 / 32 / 64 / 128 padded source channels, 16-byte row loads
+    for_block_pair(pad_blocks(ceil_div(a.c_src, 16)), nbp, [&](auto mb, auto nb) {
+      c = choose_vec<16 * decltype(mb)::value, decltype(nb)::value, WT>(a);
+      if (launch) *launch = launch_vec<16 * decltype(mb)::value, decltype(nb)::value, WT>;
+    });
+    return 0;
   }
-#define FV2P_SCALAR_CASE(STEPS)                                        \
-  switch (nbp) {                                                       \
-    case 1: unsupported = launch_scalar<STEPS, 1, WT>(a, s); break;    \
-    case 2: unsupported = launch_scalar<STEPS, 2, WT>(a, s); break;    \
-    case 4: unsupported = launch_scalar<STEPS, 4, WT>(a, s); break;    \
-    default: unsupported = launch_scalar<STEPS, 8, WT>(a, s); break;   \
-  }
-  if (vec) {
-    if (a.c_src <= 16) { FV2P_VEC_CASE(16) }
-    else if (a.c_src <= 32) { FV2P_VEC_CASE(32) }
-    else if (a.c_src <= 64) { FV2P_VEC_CASE(64) }
-    else { FV2P_VEC_CASE(128) }
-  } else {
-    if (a.c_src <= 4) { FV2P_SCALAR_CASE(1) }
-    else if (a.c_src <= 8) { FV2P_SCALAR_CASE(2) }
-    else if (a.c_src <= 16) { FV2P_SCALAR_CASE(4) }
-    else if (a.c_src <= 32) { FV2P_SCALAR_CASE(8) }
-    else return set_error(FV2P_ELIMIT, "sparse conv: %d source channels (not a multiple of 4) unsupported above 32", a.c_src);
-  }
-#undef FV2P_VEC_CASE
-#undef FV2P_SCALAR_CASE
-  return unsupported;   // (> 0: not an error code; conv_rows_impl turns it into one or into the answer of the support query)
+  if (a.c_src > 32) return set_error(FV2P_ELIMIT, "sparse conv: %d source channels (not a multiple of 4) unsupported above 32", a.c_src);
+  for_block_pair(pad_blocks(ceil_div(a.c_src, 4)), nbp, [&](auto steps, auto nb) {   // 4 / 8 / 16 / 32 padded source channels
+    c = choose_scalar<decltype(steps)::value, decltype(nb)::value, WT>(a);
+    if (launch) *launch = launch_scalar<decltype(steps)::value, decltype(nb)::value, WT>;
+  });
+  return 0;
 }
 
 // ---- exact plan for tables of <= kPlanExactRows rows ------------------------------------------------------------------------------
@@ -2603,85 +2611,88 @@ static int64_t fin_tile_cap(int64_t n_dst) {
 extern "C" size_t fv2p_sparse_conv_fin_ws_bytes(int64_t n_dst, int c_dst) {
   return align_up(static_cast<size_t>(fin_tile_cap(n_dst) + kFinSubs) * 2 * static_cast<size_t>(c_dst > 0 ? c_dst : 1) * sizeof(double));
 }
-// what a call adds to the plain conv: statistics finalised by the last workgroup, source rows normalised on the gather, a support query
+// what a call adds to the plain conv: a row order, statistics finalised by the last workgroup, a BatchNorm behind the rows, one on the gather
 struct ConvExtra {
+  const int* perm = nullptr;   // honoured by the LDS-DMA tile for permuted rows, ignored (plain row order, same result) by the others
   unsigned* fin_counter = nullptr;
   BnFwdFin fwd = {nullptr, nullptr, nullptr, nullptr, nullptr, 0.f, 0.f};   // forward statistics (all columns; moved per column block here)
   BnBwdFin bwd = {nullptr, nullptr, nullptr, 1};                              // backward sums
+  // backward data only, bn_x != nullptr: stats are that BatchNorm's backward sums (ConvArgs::bn_*; all columns)
+  const float* bn_x = nullptr; const float* bn_mean = nullptr; const float* bn_invstd = nullptr; const float* bn_gamma = nullptr; const float* bn_beta = nullptr; int bn_relu = 0;
   const float* pre_mean = nullptr; const float* pre_invstd = nullptr; const float* pre_gamma = nullptr; const float* pre_beta = nullptr; int pre_relu = 0;
-  int dry = 0;
 };
+// epilogue statistics need the whole sum in one launch per column block and a kernel with the shared epilogue;
+// otherwise the columns are summed by a BatchNorm reduce pass right after the conv (same slots, same meaning)
+static bool stats_in_epilogue(int c_src, int64_t n_dst) { return c_src <= 128 && conv_impl() != 2 && n_dst > 0; }
+// the launch of destination columns d0 .. d0 + 127 from source channels s0 .. s0 + 127 of a call (the kernels take <= 128 x 128)
+static ConvArgs conv_block_args(const float* src, int c_src, const float* weight, int kvol, const int* tab, int64_t n_dst, int c_dst, int flip_k,
+                                int transpose_w, const float* bias, float* dst, double* stats, const ConvExtra& ex, int d0, int s0) {
+  // weight is [K][Cin][Cout] in the reference layout (spconv/conv.py:98-99); with transpose_w the roles of the
+  // two channel axes are swapped: W_k^T is used, i.e. weight is [K][c_dst][c_src].
+  const int w_rows = transpose_w ? c_dst : c_src, w_cols = transpose_w ? c_src : c_dst;
+  const int cd = std::min(c_dst - d0, 128), cs = std::min(c_src - s0, 128);
+  ConvArgs a{};
+  a.src = src + s0; a.ld_src = c_src; a.c_src = cs;
+  a.w = transpose_w ? weight + static_cast<long long>(d0) * w_cols + s0 : weight + static_cast<long long>(s0) * w_cols + d0;
+  a.w_kstride = static_cast<long long>(w_rows) * w_cols; a.w_ld = w_cols;
+  a.tab = tab; a.n_dst = static_cast<int>(n_dst); a.kvol = kvol; a.flip = flip_k & 1; a.perm = ex.perm;
+  // FV2P_TAB_PLANNED: the caller's table allocation continues with the plan fv2p_conv_plan_build wrote
+  a.plan = (flip_k & 2) ? tab + static_cast<long long>(kvol) * n_dst : nullptr;
+  a.bias = (bias && s0 == 0) ? bias + d0 : nullptr;
+  a.dst = dst + d0; a.ld_dst = c_dst; a.c_dst = cd; a.accumulate = s0 > 0;
+  a.stats = stats ? stats + d0 : nullptr; a.stats_ld = c_dst;
+  if (ex.pre_mean) {   // parameters of the SOURCE channels of this launch
+    a.pre_mean = ex.pre_mean + s0; a.pre_invstd = ex.pre_invstd + s0;
+    a.pre_gamma = ex.pre_gamma ? ex.pre_gamma + s0 : nullptr; a.pre_beta = ex.pre_beta ? ex.pre_beta + s0 : nullptr; a.pre_relu = ex.pre_relu;
+  }
+  if (ex.fin_counter && stats && c_src <= 128) {   // one launch per column block holds the whole sum: its last workgroup finalises
+    // stats: the workspace of fv2p_sparse_conv_fin_ws_bytes - [tile cap][2][c_dst] rows, then kFinSubs group slots
+    a.fin_counter = ex.fin_counter; a.fin_rows = stats + d0; a.fin_c = cd;
+    a.fin_gslots = stats + static_cast<long long>(fin_tile_cap(n_dst)) * 2 * c_dst + d0;
+    a.fin_groups = n_dst > 32768 ? static_cast<int>(kFinSubs) : 16;   // ~15 - 35 rows per group fold either way
+    if (ex.bn_x) {
+      a.fin_bwd = BnBwdFin{ex.bwd.dgamma + d0, ex.bwd.dbeta + d0, ex.bwd.coef + d0, ex.bwd.batch_stats};
+    } else {
+      a.fin_fwd = ex.fwd; a.fin_fwd.mean += d0; a.fin_fwd.invstd += d0;
+      if (a.fin_fwd.running_mean) { a.fin_fwd.running_mean += d0; a.fin_fwd.running_var += d0; }
+      a.fin_bump = d0 + 128 >= c_dst;
+    }
+  }
+  if (ex.bn_x && stats) {   // per-column pointers move with the column block, bn_x is addressed like dst (row * ld_dst + col)
+    a.bn_x = ex.bn_x + d0; a.bn_mean = ex.bn_mean + d0; a.bn_invstd = ex.bn_invstd + d0;
+    a.bn_gamma = ex.bn_gamma ? ex.bn_gamma + d0 : nullptr; a.bn_beta = ex.bn_beta ? ex.bn_beta + d0 : nullptr; a.bn_relu = ex.bn_relu;
+  }
+  return a;
+}
+
 static int conv_rows_impl(const float* src, int64_t n_src, int c_src, const float* weight, int kvol, const int* tab, int64_t n_dst, int c_dst,
-                          int flip_k, int transpose_w, const float* bias, float* dst, double* stats, hipStream_t stream,
-                          const ConvArgs* bn = nullptr, const int* perm = nullptr, const ConvExtra* ex = nullptr) {
+                          int flip_k, int transpose_w, const float* bias, float* dst, double* stats, hipStream_t stream, const ConvExtra& ex = ConvExtra{}) {
   FV2P_REQUIRE(c_src >= 1 && c_dst >= 1 && kvol >= 1 && n_dst >= 0 && n_src >= 0, FV2P_EINVAL, "sparse_conv_rows: bad sizes");
   if (n_dst == 0) return 0;
   FV2P_REQUIRE(weight && tab && dst && (src || n_src == 0), FV2P_EINVAL, "sparse_conv_rows: null pointer");
   FV2P_REQUIRE(n_dst < (1ll << 31) - 64, FV2P_ELIMIT, "sparse_conv_rows: too many rows");
-  // weight is [K][Cin][Cout] in the reference layout (spconv/conv.py:98-99); with transpose_w the roles of the
-  // two channel axes are swapped: W_k^T is used, i.e. weight is [K][c_dst][c_src].
-  const int w_rows = transpose_w ? c_dst : c_src, w_cols = transpose_w ? c_src : c_dst;
   int probe_slot = -1;
-  if (g_probe.armed && !(ex && ex->dry)) {   // (unlocked read of a flag: the probe is armed and read by the thread that measures)
+  if (g_probe.armed) {   // (unlocked read of a flag: the probe is armed and read by the thread that measures)
     std::lock_guard<std::mutex> lock(g_probe.mu);
     if (g_probe.armed && g_probe.used < kProbePairs && c_src == g_probe.c_src && c_dst == g_probe.c_dst && kvol == g_probe.kvol &&
-        n_dst == g_probe.n_dst && (flip_k & 1) == g_probe.flip && !transpose_w && !bn && !(ex && ex->pre_mean)) {   // the plain-gather launches: the kernel instance the isolated probe times
+        n_dst == g_probe.n_dst && (flip_k & 1) == g_probe.flip && !transpose_w && !ex.bn_x && !ex.pre_mean) {   // the plain-gather launches: the kernel instance the isolated probe times
       probe_slot = g_probe.used++;
       FV2P_HIP(hipEventRecord(g_probe.ev[2 * probe_slot], stream));
     }
   }
   for (int d0 = 0; d0 < c_dst; d0 += 128) {
-    const int cd = (c_dst - d0) < 128 ? (c_dst - d0) : 128;
     for (int s0 = 0; s0 < c_src; s0 += 128) {
-      const int cs = (c_src - s0) < 128 ? (c_src - s0) : 128;
-      ConvArgs a;
-      a.trace = nullptr;
-      a.col_blocks = 0;
-      a.stats = stats ? stats + d0 : nullptr; a.stats_ld = c_dst;
-      a.bn_x = nullptr; a.bn_mean = a.bn_invstd = a.bn_gamma = a.bn_beta = nullptr; a.bn_relu = 0;
-      a.perm = perm;   // honoured by the LDS-DMA tile for permuted rows, ignored (plain row order, same result) by the others
-      a.fin_counter = nullptr; a.fin_rows = a.fin_gslots = nullptr; a.fin_c = 0; a.fin_groups = 1; a.fin_col0 = 0; a.fin_bump = 0; a.dry = ex ? ex->dry : 0;
-      a.fin_fwd = BnFwdFin{nullptr, nullptr, nullptr, nullptr, nullptr, 0.f, 0.f};
-      a.fin_bwd = BnBwdFin{nullptr, nullptr, nullptr, 1};
-      a.pre_mean = a.pre_invstd = a.pre_gamma = a.pre_beta = nullptr; a.pre_relu = 0;
-      if (ex && ex->pre_mean) {   // parameters of the SOURCE channels of this launch
-        a.pre_mean = ex->pre_mean + s0; a.pre_invstd = ex->pre_invstd + s0;
-        a.pre_gamma = ex->pre_gamma ? ex->pre_gamma + s0 : nullptr; a.pre_beta = ex->pre_beta ? ex->pre_beta + s0 : nullptr; a.pre_relu = ex->pre_relu;
-      }
-      if (ex && ex->fin_counter && stats && c_src <= 128) {   // one launch per column block holds the whole sum: its last workgroup finalises
-        // stats: the workspace of fv2p_sparse_conv_fin_ws_bytes - [tile cap][2][c_dst] rows, then kFinSubs group slots
-        a.fin_counter = ex->fin_counter; a.fin_rows = stats + d0; a.fin_c = cd;
-        a.fin_gslots = stats + static_cast<long long>(fin_tile_cap(n_dst)) * 2 * c_dst + d0;
-        a.fin_groups = n_dst > 32768 ? static_cast<int>(kFinSubs) : 16;   // ~15 - 35 rows per group fold either way
-        if (bn) {
-          a.fin_bwd = BnBwdFin{ex->bwd.dgamma + d0, ex->bwd.dbeta + d0, ex->bwd.coef + d0, ex->bwd.batch_stats};
-        } else {
-          a.fin_fwd = ex->fwd;
-          a.fin_fwd.mean += d0; a.fin_fwd.invstd += d0;
-          if (a.fin_fwd.running_mean) { a.fin_fwd.running_mean += d0; a.fin_fwd.running_var += d0; }
-          a.fin_bump = d0 + 128 >= c_dst;
-        }
-      }
-      if (bn && stats) {   // per-column pointers move with the column block, bn_x is addressed like dst (row * ld_dst + col)
-        a.bn_x = bn->bn_x + d0; a.bn_mean = bn->bn_mean + d0; a.bn_invstd = bn->bn_invstd + d0;
-        a.bn_gamma = bn->bn_gamma ? bn->bn_gamma + d0 : nullptr; a.bn_beta = bn->bn_beta ? bn->bn_beta + d0 : nullptr; a.bn_relu = bn->bn_relu;
-      }
-      a.src = src + s0; a.ld_src = c_src; a.c_src = cs;
-      a.w = transpose_w ? weight + static_cast<long long>(d0) * w_cols + s0 : weight + static_cast<long long>(s0) * w_cols + d0;
-      a.w_kstride = static_cast<long long>(w_rows) * w_cols; a.w_ld = w_cols;
-      a.tab = tab; a.n_dst = static_cast<int>(n_dst); a.kvol = kvol; a.flip = flip_k & 1;
-      // FV2P_TAB_PLANNED: the caller's table allocation continues with the plan fv2p_conv_plan_build wrote
-      a.plan = (flip_k & 2) ? tab + static_cast<long long>(kvol) * n_dst : nullptr;
-      a.bias = (bias && s0 == 0) ? bias + d0 : nullptr;
-      a.dst = dst + d0; a.ld_dst = c_dst; a.c_dst = cd; a.accumulate = s0 > 0;
-      int rc = transpose_w ? dispatch_conv<true>(a, stream) : dispatch_conv<false>(a, stream);
-      if (rc > 0) return a.dry ? 1 : set_error(FV2P_EINVAL, "sparse conv: the kernel for %d -> %d channels, %d offsets cannot normalise its source rows "
-                                                            "(ask fv2p_sparse_conv_prenorm_supported first)", c_src, c_dst, kvol);
-      if (rc) return rc;
+      const ConvArgs a = conv_block_args(src, c_src, weight, kvol, tab, n_dst, c_dst, flip_k, transpose_w, bias, dst, stats, ex, d0, s0);
+      ConvChoice choice;
+      ConvLaunch launch = nullptr;
+      if (int rc = transpose_w ? choose_conv<true>(a, choice, &launch) : choose_conv<false>(a, choice, &launch)) return rc;
+      if (choice.kernel == ConvKernel::no_prenorm)
+        return set_error(FV2P_EINVAL, "sparse conv: the kernel for %d -> %d channels, %d offsets cannot normalise its source rows "
+                                      "(ask fv2p_sparse_conv_prenorm_supported first)", c_src, c_dst, kvol);
+      launch(choice, a, stream);
     }
   }
   if (probe_slot >= 0) FV2P_HIP(hipEventRecord(g_probe.ev[2 * probe_slot + 1], stream));
-  if (ex && ex->dry) return 0;   // nothing was launched
   FV2P_LAUNCH_CHECK();
   return 0;
 }
@@ -2696,8 +2707,10 @@ extern "C" int fv2p_sparse_conv_rows(const float* src, int64_t n_src, int c_src,
 extern "C" int fv2p_sparse_conv_rows_perm(const float* src, int64_t n_src, int c_src, const float* weight, int kvol, const int* tab,
                                           int64_t n_dst, int c_dst, int flip_k, int transpose_w, const float* bias, float* dst, const int* perm,
                                           fv2p_stream_t stream_) {
+  ConvExtra ex;
+  ex.perm = perm;
   return conv_rows_impl(src, n_src, c_src, weight, kvol, tab, n_dst, c_dst, flip_k, transpose_w, bias, dst, nullptr,
-                        static_cast<hipStream_t>(stream_), nullptr, perm);
+                        static_cast<hipStream_t>(stream_), ex);
 }
 
 extern "C" int fv2p_sparse_conv_stat_slots(void) { return kStatSlots; }
@@ -2736,7 +2749,7 @@ extern "C" int fv2p_conv_plan_build(int* tab, int kvol, int64_t n_dst, void* ws,
   static int exact = -1;   // FV2P_PLAN_EXACT=0 keeps the equal-cost bounds (comparison runs)
   if (exact < 0) { const char* e = FV2P_DEV_ENV("FV2P_PLAN_EXACT"); exact = e ? atoi(e) : 1; }
   const size_t lds = 2 * static_cast<size_t>(n_dst + 1) * sizeof(unsigned short);
-  static bool big = [] { return hipFuncSetAttribute(reinterpret_cast<const void*>(&plan_walk_k), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64) == hipSuccess; }();
+  const bool big = big_lds<&plan_walk_k, 160 * 1024 - 64>();
   if (exact && kvol >= 8 && kvol <= 27 && n_dst >= 1024 && n_dst <= kPlanExactRows && (big || lds <= 48 * 1024)) {
     // group-balanced bounds: four launches (row words, reach of 16 budgets, one chain walk per budget, selection per level)
     unsigned long long* words = c.take<unsigned long long>(3 * static_cast<size_t>(n_dst));
@@ -2764,9 +2777,7 @@ extern "C" int fv2p_sparse_conv_rows_stats(const float* src, int64_t n_src, int 
                                            double* stats, fv2p_stream_t stream_) {
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   FV2P_REQUIRE(stats, FV2P_EINVAL, "sparse_conv_rows_stats: null stats");
-  // epilogue statistics need the whole sum in one launch per column block and a kernel with the shared epilogue;
-  // otherwise the columns are summed by the BatchNorm reduce pass right after the conv (same slots, same meaning)
-  const bool fused = c_src <= 128 && conv_impl() != 2 && n_dst > 0;
+  const bool fused = stats_in_epilogue(c_src, n_dst);
   if (int rc = conv_rows_impl(src, n_src, c_src, weight, kvol, tab, n_dst, c_dst, flip_k, transpose_w, bias, dst, fused ? stats : nullptr, stream))
     return rc;
   if (!fused && n_dst > 0) return bn_column_sums(dst, n_dst, c_dst, stats, stream);
@@ -2789,11 +2800,10 @@ extern "C" int fv2p_sparse_conv_rows_bnfin(const float* src, int64_t n_src, int 
                FV2P_EINVAL, "sparse_conv_rows_bnfin: source BatchNorm parameters must be 16-byte aligned, channels a multiple of 4");
   ConvExtra ex;
   ex.pre_mean = pre_mean; ex.pre_invstd = pre_invstd; ex.pre_gamma = pre_gamma; ex.pre_beta = pre_beta; ex.pre_relu = pre_relu;
-  const bool fused = stats && c_src <= 128 && conv_impl() != 2 && n_dst > 0;
+  const bool fused = stats && stats_in_epilogue(c_src, n_dst);
   const BnFwdFin ff{mean, invstd, running_mean, running_var, reinterpret_cast<long long*>(num_batches_tracked), momentum, eps};
   if (fused) { ex.fin_counter = counter; ex.fwd = ff; }
-  if (int rc = conv_rows_impl(src, n_src, c_src, weight, kvol, tab, n_dst, c_dst, flip_k, transpose_w, bias, dst, fused ? stats : nullptr, stream,
-                              nullptr, nullptr, &ex))
+  if (int rc = conv_rows_impl(src, n_src, c_src, weight, kvol, tab, n_dst, c_dst, flip_k, transpose_w, bias, dst, fused ? stats : nullptr, stream, ex))
     return rc;
   if (stats && !fused && n_dst > 0) {   // sums by a pass over dst, finalised by one workgroup (the workspace's head serves as its slots)
     FV2P_HIP(hipMemsetAsync(stats, 0, sizeof(double) * kStatSlots * 2 * static_cast<size_t>(c_dst), stream));
@@ -2807,13 +2817,16 @@ extern "C" int fv2p_sparse_conv_rows_bnfin(const float* src, int64_t n_src, int 
 // choose has the PRE form: conv_rows_thin 16 -> 16, conv_rows_ksplit 64 / 128 source channels), else 0.
 extern "C" int fv2p_sparse_conv_prenorm_supported(int c_src, int c_dst, int kvol, int64_t n_dst, int flip_k, int transpose_w) {
   if (c_src < 1 || c_dst < 1 || kvol < 1 || n_dst < 1 || transpose_w || c_src > 128 || c_dst > 128 || (c_src & 3)) return 0;
+  if (n_dst >= (1ll << 31) - 64) return 0;   // conv_rows_impl's limit
+  // the one block of such a call: the choice reads sizes, strides, alignment and which pointers are null, and dereferences nothing
+  float* aligned = reinterpret_cast<float*>(static_cast<uintptr_t>(4096));
   ConvExtra ex;
-  ex.dry = 1;
-  float* fake = reinterpret_cast<float*>(static_cast<uintptr_t>(4096));   // never dereferenced: a dry run launches nothing
-  ex.pre_mean = ex.pre_invstd = fake;
-  const int rc = conv_rows_impl(fake, n_dst, c_src, fake, kvol, reinterpret_cast<const int*>(fake), n_dst, c_dst, flip_k, 0, nullptr, fake, nullptr, nullptr,
-                                nullptr, nullptr, &ex);
-  return rc == 0 ? 1 : 0;
+  ex.pre_mean = ex.pre_invstd = aligned;
+  const ConvArgs a = conv_block_args(aligned, c_src, aligned, kvol, reinterpret_cast<const int*>(aligned), n_dst, c_dst, flip_k, 0, nullptr, aligned,
+                                     nullptr, ex, 0, 0);
+  ConvChoice choice;
+  if (choose_conv<false>(a, choice)) return 0;
+  return choice.kernel != ConvKernel::no_prenorm ? 1 : 0;
 }
 
 extern "C" int fv2p_sparse_conv_rows_bnbwd_fin(const float* src, int64_t n_src, int c_src, const float* weight, int kvol, const int* tab,
@@ -2823,14 +2836,15 @@ extern "C" int fv2p_sparse_conv_rows_bnbwd_fin(const float* src, int64_t n_src, 
                                                const int* perm, fv2p_stream_t stream_) {
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   FV2P_REQUIRE(stats && counter && bn_x && bn_mean && bn_invstd && dgamma && dbeta && coef, FV2P_EINVAL, "sparse_conv_rows_bnbwd_fin: null pointer");
-  const bool fused = c_src <= 128 && conv_impl() != 2 && n_dst > 0;
-  ConvArgs bn;
-  bn.bn_x = bn_x; bn.bn_mean = bn_mean; bn.bn_invstd = bn_invstd; bn.bn_gamma = bn_gamma; bn.bn_beta = bn_beta; bn.bn_relu = relu;
+  const bool fused = stats_in_epilogue(c_src, n_dst);
   ConvExtra ex;
+  ex.perm = perm;
   const BnBwdFin bf{dgamma, dbeta, coef, batch_stats};
-  if (fused) { ex.fin_counter = counter; ex.bwd = bf; }
-  if (int rc = conv_rows_impl(src, n_src, c_src, weight, kvol, tab, n_dst, c_dst, flip_k, transpose_w, nullptr, dst, fused ? stats : nullptr, stream,
-                              fused ? &bn : nullptr, perm, &ex))
+  if (fused) {
+    ex.fin_counter = counter; ex.bwd = bf;
+    ex.bn_x = bn_x; ex.bn_mean = bn_mean; ex.bn_invstd = bn_invstd; ex.bn_gamma = bn_gamma; ex.bn_beta = bn_beta; ex.bn_relu = relu;
+  }
+  if (int rc = conv_rows_impl(src, n_src, c_src, weight, kvol, tab, n_dst, c_dst, flip_k, transpose_w, nullptr, dst, fused ? stats : nullptr, stream, ex))
     return rc;
   if (!fused && n_dst > 0) {
     FV2P_HIP(hipMemsetAsync(stats, 0, sizeof(double) * kStatSlots * 2 * static_cast<size_t>(c_dst), stream));
@@ -2846,11 +2860,11 @@ extern "C" int fv2p_sparse_conv_rows_bnbwd(const float* src, int64_t n_src, int 
                                            double* stats, const int* perm, fv2p_stream_t stream_) {
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   FV2P_REQUIRE(stats && bn_x && bn_mean && bn_invstd, FV2P_EINVAL, "sparse_conv_rows_bnbwd: null pointer");
-  const bool fused = c_src <= 128 && conv_impl() != 2 && n_dst > 0;   // as in fv2p_sparse_conv_rows_stats
-  ConvArgs bn;
-  bn.bn_x = bn_x; bn.bn_mean = bn_mean; bn.bn_invstd = bn_invstd; bn.bn_gamma = bn_gamma; bn.bn_beta = bn_beta; bn.bn_relu = relu;
-  if (int rc = conv_rows_impl(src, n_src, c_src, weight, kvol, tab, n_dst, c_dst, flip_k, transpose_w, nullptr, dst, fused ? stats : nullptr, stream,
-                              fused ? &bn : nullptr, perm))
+  const bool fused = stats_in_epilogue(c_src, n_dst);
+  ConvExtra ex;
+  ex.perm = perm;
+  if (fused) { ex.bn_x = bn_x; ex.bn_mean = bn_mean; ex.bn_invstd = bn_invstd; ex.bn_gamma = bn_gamma; ex.bn_beta = bn_beta; ex.bn_relu = relu; }
+  if (int rc = conv_rows_impl(src, n_src, c_src, weight, kvol, tab, n_dst, c_dst, flip_k, transpose_w, nullptr, dst, fused ? stats : nullptr, stream, ex))
     return rc;
   if (!fused && n_dst > 0) return bn_backward_sums(bn_x, dst, n_dst, c_dst, bn_mean, bn_invstd, bn_gamma, bn_beta, relu, stats, stream);
   return 0;
@@ -2922,9 +2936,6 @@ extern "C" int fv2p_sparse_conv_wgrad_pre(const float* src, int64_t n_src, int c
     a.pre_mean = pre_mean ? pre_mean + s0 : nullptr; a.pre_invstd = pre_invstd ? pre_invstd + s0 : nullptr;
     a.pre_gamma = pre_gamma ? pre_gamma + s0 : nullptr; a.pre_beta = pre_beta ? pre_beta + s0 : nullptr; a.pre_relu = pre_relu;
     const int mb = static_cast<int>(ceil_div(cs, 16));
-    const int nb = static_cast<int>(ceil_div(cd, 16));
-    const int nbp = nb <= 1 ? 1 : nb <= 2 ? 2 : nb <= 4 ? 4 : 8;
-    const int mbp = mb <= 1 ? 1 : mb <= 2 ? 2 : mb <= 4 ? 4 : 8;
     FV2P_REQUIRE(mb <= 8, FV2P_ELIMIT, "sparse_conv_wgrad: more than 128 source channels per launch (split on the host)");
     // pass 0: every offset except the dense one, rpc rows per workgroup; pass 1: the dense (identity) offset, whose pair
     // count equals the row count, in shorter chunks so that it is not the straggler of the launch
@@ -2935,13 +2946,7 @@ extern "C" int fv2p_sparse_conv_wgrad_pre(const float* src, int64_t n_src, int c
       a.rows_per_chunk = pass ? kDenseRpc : rpc;
       float* pp = pass ? dpartial : partial;
       const unsigned nch = pass ? dchunks : chunks;
-#define FV2P_WG(MB, NB) wgrad_launch<MB, NB>(a, pp, nch, stream)
-#define FV2P_WG_NB(MB)                                                                   \
-      switch (nbp) { case 1: FV2P_WG(MB, 1); break; case 2: FV2P_WG(MB, 2); break;      \
-                     case 4: FV2P_WG(MB, 4); break; default: FV2P_WG(MB, 8); break; }
-      switch (mbp) { case 1: FV2P_WG_NB(1) break; case 2: FV2P_WG_NB(2) break; case 4: FV2P_WG_NB(4) break; default: FV2P_WG_NB(8) break; }
-#undef FV2P_WG_NB
-#undef FV2P_WG
+      for_block_pair(pad_blocks(mb), pad_blocks(ceil_div(cd, 16)), [&](auto mbp, auto nbp) { wgrad_launch<decltype(mbp)::value, decltype(nbp)::value>(a, pp, nch, stream); });
       const long long per_chunk = static_cast<long long>(a.k_count) * cs * cd;
       hipLaunchKernelGGL(wgrad_reduce, dim3(static_cast<unsigned>(ceil_div(per_chunk, 16))), dim3(256), 0, stream, pp, (int)nch, a.k_base,
                          a.k_count, cs, cd, a.dw, a.dw_kstride, a.dw_ld, a.skip_k);
@@ -3004,9 +3009,6 @@ extern "C" int fv2p_sparse_conv_wgrad_pairs_pre(const float* src, int64_t n_src,
       a.pairs = pairs; a.pair_len = pair_len; a.pair_num = pair_num; a.side_src = side_src; a.kvol = kvol; a.chunk = chunk;
       a.pre_mean = pre_mean ? pre_mean + s0 : nullptr; a.pre_invstd = pre_invstd ? pre_invstd + s0 : nullptr;
       a.pre_gamma = pre_gamma ? pre_gamma + s0 : nullptr; a.pre_beta = pre_beta ? pre_beta + s0 : nullptr; a.pre_relu = pre_relu;
-      const int mb = static_cast<int>(ceil_div(cs, 16)), nb = static_cast<int>(ceil_div(cd, 16));
-      const int nbp = nb <= 1 ? 1 : nb <= 2 ? 2 : nb <= 4 ? 4 : 8;
-      const int mbp = mb <= 1 ? 1 : mb <= 2 ? 2 : mb <= 4 ? 4 : 8;
       const bool dma_ok = (cs == 64 || cs == 128) && (cd == 64 || cd == 128) && (c_src & 3) == 0 && (c_dst & 3) == 0 &&
                           (reinterpret_cast<uintptr_t>(a.src) & 15) == 0 && (reinterpret_cast<uintptr_t>(a.grad) & 15) == 0 && g_wgrad_dma;
       if (dma_ok) {
@@ -3025,13 +3027,7 @@ extern "C" int fv2p_sparse_conv_wgrad_pairs_pre(const float* src, int64_t n_src,
         else if (as == 1 && bs == 2) hipLaunchKernelGGL((conv_wgrad_pairs_dma<1, 2, 32>), grid, block, lds, stream, a, partial);
         else hipLaunchKernelGGL((conv_wgrad_pairs_dma<2, 2, 32>), grid, block, lds, stream, a, partial);
       } else {
-#define FV2P_WGP(MB, NB) wgrad_pairs_launch<MB, NB>(a, partial, chunks, stream)
-#define FV2P_WGP_NB(MB)                                                                    \
-      switch (nbp) { case 1: FV2P_WGP(MB, 1); break; case 2: FV2P_WGP(MB, 2); break;      \
-                     case 4: FV2P_WGP(MB, 4); break; default: FV2P_WGP(MB, 8); break; }
-      switch (mbp) { case 1: FV2P_WGP_NB(1) break; case 2: FV2P_WGP_NB(2) break; case 4: FV2P_WGP_NB(4) break; default: FV2P_WGP_NB(8) break; }
-#undef FV2P_WGP_NB
-#undef FV2P_WGP
+        for_block_pair(pad_blocks(ceil_div(cs, 16)), pad_blocks(ceil_div(cd, 16)), [&](auto mbp, auto nbp) { wgrad_pairs_launch<decltype(mbp)::value, decltype(nbp)::value>(a, partial, chunks, stream); });
       }
       const long long per_chunk = static_cast<long long>(kvol) * cs * cd;
       hipLaunchKernelGGL(wgrad_reduce_pairs, dim3(static_cast<unsigned>(ceil_div(per_chunk, 16))), dim3(256), 0, stream, partial, pair_num, kvol,

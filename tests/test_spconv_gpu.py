@@ -168,6 +168,26 @@ def test_strided_conv_vs_oracle_and_dense(gpu, front_end, k, s, p):
     assert rel_err(conv.bias.grad.cpu().numpy(), g.sum(0)) < RTOL
 
 
+def test_128_channels_with_more_than_27_offsets_vs_oracle(gpu):
+    """128 -> 128 with a 4 x 2 x 4 kernel (32 offsets): past the 27 offsets the K-split tile's step list holds, so the auto mode
+    takes the LDS-DMA tile on two column halves (conv_rows_dma<128, 4> on grid.y = 2), forward and backward data."""
+    batch, shape, cin, cout, k, s, p = 2, [9, 16, 14], 128, 128, [4, 2, 4], [1, 1, 1], [1, 0, 1]
+    ind, feats, x = make_input(17, batch, shape, 300, cin, gpu)
+    conv = spconv.SparseConv3d(cin, cout, k, stride=s, padding=p, bias=True).to(gpu)
+    x.features.requires_grad_(True)
+    y = conv(x)
+    w, b = conv.weight.detach().cpu().numpy(), conv.bias.detach().cpu().numpy()
+    outids, pairs, num = oracle.indice_pairs(ind, batch, shape, k, s, p, [1, 1, 1])
+    assert np.array_equal(y.indices.cpu().numpy(), outids) and outids.shape[0] > 128   # more than one 64-row tile
+    ref = oracle.indice_conv(feats, w, pairs, num, outids.shape[0]).numpy() + b
+    assert rel_err(y.features.detach().cpu().numpy(), ref) < RTOL
+    g = np.random.default_rng(3).standard_normal(ref.shape).astype(np.float32)
+    y.features.backward(torch.from_numpy(g).to(gpu))
+    din, dw = oracle.indice_conv_backward(feats, w, g, pairs, num)
+    assert rel_err(x.features.grad.cpu().numpy(), din.numpy()) < RTOL
+    assert rel_err(conv.weight.grad.cpu().numpy(), dw.numpy()) < RTOL
+
+
 def test_subm_conv_equals_masked_dense_conv_and_autograd(gpu):
     batch, shape, cin, cout = 2, [7, 12, 10], 8, 16
     ind, feats, x = make_input(5, batch, shape, 400, cin, gpu)
