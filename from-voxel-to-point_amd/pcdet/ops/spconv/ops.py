@@ -367,22 +367,38 @@ def _rulebook_of(indice_pairs, indice_pair_num, n_src_rows, num_activate_out, in
     return rb
 
 
+_DT16 = {torch.float16: 1, torch.bfloat16: 2}   # FV2P_DT_F16 / FV2P_DT_BF16 (include/fv2p_ops.h)
+
+
+def _conv_dtype(*tensors):
+    """The one dtype of a sparse conv call's floating operands: float32 (the fp32 kernels) or a key of _DT16 (the 16-bit MFMA
+    kernels of csrc/sparse_conv_h.hip).  Nothing is converted on the way, so every operand has to have it."""
+    dts = {t.dtype for t in tensors if t is not None}
+    if len(dts) > 1:
+        raise TypeError("sparse conv: features, weights, bias and gradients must share one dtype, got "
+                        + ", ".join(sorted(str(d) for d in dts)) + " (convert the module or the features; nothing is cast here)")
+    dt = dts.pop()
+    if dt != torch.float32 and dt not in _DT16:
+        raise NotImplementedError("sparse conv: float32, float16 and bfloat16 only, got %s" % dt)
+    return dt
+
+
 def _conv_rows(src, weight, table, flip, n_dst, c_dst, transpose_w, bias=None):
     _nat.require_cuda(src, weight, table)
-    half = src.dtype == torch.half
-    if half:  # the reference binds *_half entry points (all.cc:36-51); computed here in fp32
-        src, weight = src.float(), weight.float()
-        bias = None if bias is None else bias.float()
-    if src.dtype != torch.float32 or weight.dtype != torch.float32:
-        raise NotImplementedError("sparse conv: float32 / float16 only")
+    dt = _conv_dtype(src, weight, bias)
     src = src.contiguous()
     w = weight.contiguous()
     kvol = table.shape[0]
-    dst = torch.empty((n_dst, c_dst), dtype=torch.float32, device=src.device)
+    dst = torch.empty((n_dst, c_dst), dtype=dt, device=src.device)
+    bias = bias.contiguous() if bias is not None else None
     with _nat.device_guard(src.device):
-        _nat.call("fv2p_sparse_conv_rows", src, src.shape[0], src.shape[1], w, kvol, table, n_dst, c_dst, int(flip),
-                  int(transpose_w), bias.contiguous() if bias is not None else None, dst, _nat.stream())
-    return dst.half() if half else dst
+        if dt == torch.float32:
+            _nat.call("fv2p_sparse_conv_rows", src, src.shape[0], src.shape[1], w, kvol, table, n_dst, c_dst, int(flip),
+                      int(transpose_w), bias, dst, _nat.stream())
+        else:   # 16-bit storage, 16-bit MFMA, fp32 accumulators, one rounding (the reference's *_half entry points, all.cc:36-51)
+            _nat.call("fv2p_sparse_conv_rows_h", src, src.shape[0], src.shape[1], w, kvol, table, n_dst, c_dst, int(flip),
+                      int(transpose_w), bias, dst, _DT16[dt], _nat.stream())
+    return dst
 
 
 def indice_conv(features, filters, indice_pairs, indice_pair_num, num_activate_out, inverse=False, subm=False, bias=None):
@@ -403,12 +419,21 @@ def indice_conv_backward(features, filters, out_bp, indice_pairs, indice_pair_nu
     """Returns [d_features, d_filters] (reference ops.py:142-157 -> spconv_ops.h:364-457)."""
     rb = _rulebook_of(indice_pairs, indice_pair_num, features.shape[0], out_bp.shape[0], inverse)
     cin, cout = filters.shape[-2], filters.shape[-1]
-    half = features.dtype == torch.half
-    f32 = lambda t: t.float() if half else t
-    feats, w, g = f32(features).contiguous(), f32(filters).reshape(-1, cin, cout).contiguous(), f32(out_bp).contiguous()
+    dt = _conv_dtype(features, filters, out_bp)
+    feats, w, g = features.contiguous(), filters.reshape(-1, cin, cout).contiguous(), out_bp.contiguous()
     kvol = w.shape[0]
     # forward used table F (dst rows = outputs); its transpose-direction table B has dst rows = inputs
     (tab_f, flip_f), (tab_b, flip_b) = (rb.in_table(), rb.out_table(cout)) if inverse else (rb.out_table(), rb.in_table(cout))
+    if dt != torch.float32:
+        din = _conv_rows(g, w, tab_b, flip_b, features.shape[0], cin, True)
+        if g.shape[0] == 0:
+            return [din, torch.zeros_like(filters)]
+        dw = torch.empty_like(w)
+        with _nat.device_guard(feats.device):
+            ws = _nat.workspace(_nat.lib().fv2p_sparse_conv_wgrad_h_ws_bytes(g.shape[0], cin, cout, kvol), feats.device)
+            _nat.call("fv2p_sparse_conv_wgrad_h", feats, feats.shape[0], cin, g, tab_f, g.shape[0], cout, kvol, int(flip_f), dw, _DT16[dt],
+                      ws, ws.numel(), _nat.stream())
+        return [din, dw.reshape(filters.shape)]
     if cout in _PLAN_CHANNELS and cin % 64 == 0 and cin <= 128 and kvol > 1:
         # the K-split tile's shapes: W_k^T materialised once and read as a plain weight (csrc_torch/fv2p_torch.cpp has the measurement)
         din = _conv_rows(g, w.transpose(1, 2).contiguous(), tab_b, flip_b, features.shape[0], cin, False)
@@ -431,10 +456,7 @@ def indice_conv_backward(features, filters, out_bp, indice_pairs, indice_pair_nu
             centre = (kvol // 2) if (rb.subm and rb.tab_out is None and not inverse) else -1
             _nat.call("fv2p_sparse_conv_wgrad", feats, feats.shape[0], cin, g, tab_f, g.shape[0], cout, kvol, int(flip_f), centre, dw, ws,
                       ws.numel(), _nat.stream())
-    dw = dw.reshape(filters.shape)
-    if half:
-        din, dw = din.half(), dw.half()
-    return [din, dw]
+    return [din, dw.reshape(filters.shape)]
 
 
 # ---- max-pool / group over the same tables (A7; reference pool_ops.h:25-94, group_ops.h:29-291) ----

@@ -1,6 +1,9 @@
 """`pcdet.ops.spconv.sparse_conv_ext` — the 17 functions the reference binds with pybind11
 (pcdet/ops/spconv/src/all.cc:22-71), same names, argument order and return conventions, implemented
-over the C ABI of libfv2p_ops so third-party code written against the extension keeps working."""
+over the C ABI of libfv2p_ops so third-party code written against the extension keeps working.
+
+The conv functions take float32, float16 and bfloat16 tensors under either name (`*_fp32`, `*_half`): the dtype of the tensors
+selects the kernels, see the note at the `*_half` aliases."""
 import torch
 
 from . import ops as _ops
@@ -50,6 +53,10 @@ def fused_indice_conv_fp32(features, filters, bias, indicePairs, indiceNum, numA
     return _ops.fused_indice_conv(features, filters, bias, indicePairs, indiceNum, numActOut, bool(inverse), bool(subM))
 
 
+# The reference binds separate half instantiations (all.cc:36-51).  Here the dispatch is by the tensors' dtype inside ops.py, so the
+# names stay aliases: float32 tensors run the fp32 kernels, float16 (and bfloat16, which the reference lacks) tensors run the
+# 16-bit MFMA kernels of csrc/sparse_conv_h.hip - 16-bit storage, fp32 accumulation, one rounding, no fp32 copy of any operand.
+# Features, filters, bias and gradients of one call share one dtype (TypeError otherwise).
 indice_conv_half = indice_conv_fp32
 indice_conv_backward_half = indice_conv_backward_fp32
 fused_indice_conv_half = fused_indice_conv_fp32

@@ -297,6 +297,36 @@ int fv2p_sparse_conv_wgrad_pairs(const float* src, int64_t n_src, int c_src, con
                                  int c_dst, const int* pairs, const int* pair_num, int kvol, int64_t pair_len,
                                  int side_src, float* dweight, void* ws, size_t ws_bytes, fv2p_stream_t stream);
 
+/* ---- fused sparse convolution on 16-bit operands ----------------------------------------------
+ * What the reference binds as indice_conv_half / indice_conv_backward_half / fused_indice_conv_half (all.cc:36-51), plus
+ * bfloat16, which it does not have.  `dtype` names the 16-bit format of EVERY operand and result of a call (features,
+ * weight, bias, gradients, outputs): FV2P_DT_F16 = IEEE binary16, FV2P_DT_BF16 = bfloat16; any other value returns
+ * FV2P_EINVAL and launches nothing.  The fp32 entry points above are not involved and no operand is converted to fp32 in
+ * memory: products run on v_mfma_f32_16x16x32_f16 / _bf16 with fp32 accumulators.
+ *   fv2p_sparse_conv_rows_h : the contract of fv2p_sparse_conv_rows,
+ *                               dst[r,:] = bias + sum_k src[tab[k][r],:] . W_k     (W_k^T with transpose_w = 1)
+ *     on the [K][Cin][Cout] parameter layout; entries with tab == -1 are skipped, flip_k bit 0 (FV2P_TAB_FLIP) reads table
+ *     row K-1-k for offset k, FV2P_TAB_PLANNED may be set and is ignored (these kernels take no tiling plan).  Each element
+ *     is summed over ascending k (all source channels of an offset before the next offset) inside one workgroup, without
+ *     atomics; bias [c_dst] (NULL = none; in the call's dtype) is widened to fp32 and added to the fp32 sum, which is then
+ *     rounded to nearest even ONCE, at the store.  Results are bit-identical from run to run.  Any c_src, c_dst >= 1
+ *     (counts that are not a multiple of 8, or pointers that are not 16-byte aligned, take an element-wise fetch).
+ *     n_dst == 0 returns 0 and launches nothing.
+ *   fv2p_sparse_conv_wgrad_h : dW_k[cs][cd] = sum_r src[tab[k][r], cs] . grad[r, cd], table-driven like fv2p_sparse_conv_wgrad
+ *     (no dense_k, no pair-list form).  Chunks of destination rows leave fp32 partial tiles in the workspace
+ *     (fv2p_sparse_conv_wgrad_h_ws_bytes); the partials are summed in ascending chunk order, no atomics, and rounded once
+ *     to the 16-bit dweight [K][c_src][c_dst], which is fully written.  n_dst == 0 returns 0, launches nothing and leaves
+ *     dweight as it is. */
+#define FV2P_DT_F16 1
+#define FV2P_DT_BF16 2
+int fv2p_sparse_conv_rows_h(const void* src, int64_t n_src, int c_src, const void* weight, int kvol, const int* tab,
+                            int64_t n_dst, int c_dst, int flip_k, int transpose_w, const void* bias, void* dst,
+                            int dtype, fv2p_stream_t stream);
+size_t fv2p_sparse_conv_wgrad_h_ws_bytes(int64_t n_dst, int c_src, int c_dst, int kvol);
+int fv2p_sparse_conv_wgrad_h(const void* src, int64_t n_src, int c_src, const void* grad, const int* tab, int64_t n_dst,
+                             int c_dst, int kvol, int flip_k, void* dweight, int dtype, void* ws, size_t ws_bytes,
+                             fv2p_stream_t stream);
+
 /* ---- A7: sparse max-pool / neighbour group over the same tables ------------------------------
  * Replace sparse_conv_ext.indice_maxpool_fp32(+backward) (all.cc:52-63 -> pool_ops.h:25-94; output starts
  * at zero so the result is max(0, .)) and indice_group_fp32(+backward) (all.cc:64-71 -> group_ops.h:29-291):

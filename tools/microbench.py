@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Per-kernel timings on one GPU (events on the launch stream). Not part of the product or of bench.py; used to
-iterate on kernel variants:  python tools/microbench.py [conv|dcn|fps|voxel|nms|all]"""
+iterate on kernel variants:  python tools/microbench.py [conv|conv16|dcn|fps|voxel|nms|all]"""
 import os
 import sys
 import time
@@ -258,6 +258,77 @@ def conv(only=None):
     pts = torch.from_numpy(synth.lidar_cloud(0, 16384)).to(dev)
     t = timeit(lambda: points_to_voxel_gpu(pts, synth.KITTI_VOXEL, synth.KITTI_RANGE, 5, True, 16000), reps=20)
     print(f"points_to_voxel 16384 pts: {t:.1f} us")
+
+
+def conv16():
+    """The 16-bit sparse conv (csrc/sparse_conv_h.hip) beside the fp32 kernels, layer by layer at the shapes `conv` uses (plain
+    VoxelBackBone8x, KITTI clouds, batch 4).  Per layer, in us: forward, backward data (dX) and weight gradient (dW, table-driven) for
+      fp32     : the fp32 kernels on fp32 tensors;
+      via fp32 : float16 tensors converted to fp32, the fp32 kernels, results converted back - the route float16 took before the
+                 16-bit kernels existed (three conversion passes per operand set);
+      fp16/bf16: the 16-bit kernels on float16 / bfloat16 tensors.
+    The versions are timed alternately, layer by layer, in one process."""
+    from fv2p_harness import synth
+    from fv2p_harness.backbone import VoxelBackBone8x, mean_vfe
+    from pcdet.datasets.processor.voxel_generator import points_to_voxel_gpu
+    from pcdet.ops.spconv import ops
+    from pcdet.ops.spconv.conv import SparseConvolution
+    dev = torch.device("cuda:0")
+    torch.manual_seed(0)
+    model = VoxelBackBone8x(4, [1408, 1600, 40]).to(dev)
+    feats, coords = [], []
+    for b in range(4):
+        v, c, n = points_to_voxel_gpu(torch.from_numpy(synth.lidar_cloud(b, 16384)).to(dev), synth.KITTI_VOXEL, synth.KITTI_RANGE, 5, True, 16000)
+        feats.append(mean_vfe(v, n))
+        coords.append(torch.nn.functional.pad(c, (1, 0), value=b))
+    recs = []
+
+    def hook(mod, inp, out):
+        if mod.indice_key is not None:
+            recs.append((mod, inp[0].features.detach(), inp[0].indice_dict[mod.indice_key], out.features.shape[0]))
+    hs = [m.register_forward_hook(hook) for m in model.modules() if isinstance(m, SparseConvolution)]
+    with torch.no_grad():
+        model(torch.cat(feats), torch.cat(coords), 4)
+    for h in hs:
+        h.remove()
+
+    def via_fp32_fwd(f, w, rb, n_out, subm):
+        return ops.indice_conv(f.float(), w.float(), rb, None, n_out, False, subm).half()
+
+    def via_fp32_bwd(f, w, g, rb, subm):
+        din, dw = ops.indice_conv_backward(f.float(), w.float(), g.float(), rb, None, False, subm)
+        return din.half(), dw.half()
+
+    print(f"{'layer':30s} {'n_in':>6s} {'n_out':>6s} {'pairs':>8s} | {'fp32 fwd':>8s} {'dX':>7s} {'dW':>7s} | {'via fp32 fwd':>12s} {'dX+dW':>7s} |"
+          f" {'fp16 fwd':>8s} {'dX':>7s} {'dW':>7s} | {'bf16 fwd':>8s} {'dX':>7s} {'dW':>7s}")
+    seen = set()
+    for mod, f, rb, n_out in recs:
+        cin, cout = mod.in_channels, mod.out_channels
+        key = (mod.subm, cin, cout, f.shape[0], n_out)
+        if key in seen:
+            continue
+        seen.add(key)
+        p = int(rb.indice_pair_num.sum().item())
+        w = mod.weight.detach()
+        g = torch.randn((n_out, cout), device=dev)
+        (tab_b, flip_b) = rb.in_table(cout)
+        pairs_saved, rb._wpairs = rb._wpairs, None     # table-driven weight gradient on both sides
+        row = []
+        for dt in (torch.float32, "via", torch.float16, torch.bfloat16):
+            if dt == "via":
+                fh, wh, gh = f.half(), w.half(), g.half()
+                row += [timeit(lambda: via_fp32_fwd(fh, wh, rb, n_out, mod.subm)), timeit(lambda: via_fp32_bwd(fh, wh, gh, rb, mod.subm))]
+                continue
+            fd, wd, gd = f.to(dt), w.to(dt), g.to(dt)
+            w3 = wd.reshape(-1, cin, cout)
+            t_f = timeit(lambda: ops.indice_conv(fd, wd, rb, None, n_out, False, mod.subm))
+            t_dx = timeit(lambda: ops._conv_rows(gd, w3, tab_b, flip_b, fd.shape[0], cin, True))
+            t_all = timeit(lambda: ops.indice_conv_backward(fd, wd, gd, rb, None, False, mod.subm))
+            row += [t_f, t_dx, t_all - t_dx]
+        rb._wpairs = pairs_saved
+        name = f"{'subm' if mod.subm else 'conv'} {cin}->{cout} {mod.indice_key}"
+        print(f"{name:30s} {f.shape[0]:6d} {n_out:6d} {p:8d} | {row[0]:8.1f} {row[1]:7.1f} {row[2]:7.1f} | {row[3]:12.1f} {row[4]:7.1f} |"
+              f" {row[5]:8.1f} {row[6]:7.1f} {row[7]:7.1f} | {row[8]:8.1f} {row[9]:7.1f} {row[10]:7.1f}")
 
 
 def dcn():
@@ -642,7 +713,7 @@ if __name__ == "__main__":
     if which == "voxelcount":
         voxelcount()
         sys.exit(0)
-    for name, fn in (("conv", conv), ("dcn", dcn), ("fps", fps), ("voxel", voxel), ("fpstrace", fpstrace), ("nn", nn), ("nms", nms), ("sa", sa), ("bn", bn), ("bev", bev), ("oproof", oproof)):
+    for name, fn in (("conv", conv), ("conv16", conv16), ("dcn", dcn), ("fps", fps), ("voxel", voxel), ("fpstrace", fpstrace), ("nn", nn), ("nms", nms), ("sa", sa), ("bn", bn), ("bev", bev), ("oproof", oproof)):
         if which in (name, "all"):
             print(f"==== {name}")
             fn()
