@@ -3,6 +3,7 @@
 // src/maxpool_cuda.cu:28-454) and indice_group_fp32(+backward) (include/spconv/group_ops.h:29-291).
 // Both are pure gathers once the rulebook is a table: one thread per (row, channel quad), no atomics.
 #include "common.hpp"
+#include "dt16.hpp"
 
 namespace fv2p {
 
@@ -37,6 +38,57 @@ __global__ void maxpool_bwd(const float* __restrict__ in, const float* __restric
     if (o >= 0 && out[static_cast<int64_t>(o) * c + ch] == v) g += dout[static_cast<int64_t>(o) * c + ch];
   }
   din[t] = g;
+}
+
+// The same two on 16-bit rows (float16 / bfloat16): one thread per (row, V channels), V = 8 as one 16-byte access when c % 8 == 0.
+// Compared on the widened values; the forward result is one of its inputs or 0 (exact), the backward sum runs in fp32 over
+// ascending k and is rounded once.
+template <class T, int V>
+__global__ __launch_bounds__(256) void maxpool_fwd_h(const u16* __restrict__ in, int c, const int* __restrict__ tab, int kvol, int n_out, int flip,
+                                                     u16* __restrict__ out) {
+  const int cv = c / V;
+  const int64_t t = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
+  if (t >= static_cast<int64_t>(n_out) * cv) return;
+  const int o = static_cast<int>(t / cv), ch = static_cast<int>(t % cv) * V;
+  Row16<T, V> m;
+#pragma unroll
+  for (int j = 0; j < V; ++j) m.v[j] = 0.f;
+  for (int k = 0; k < kvol; ++k) {
+    const int i = tab[static_cast<int64_t>(flip ? kvol - 1 - k : k) * n_out + o];
+    if (i >= 0) {
+      Row16<T, V> v;
+      v.load(in + static_cast<int64_t>(i) * c + ch);
+#pragma unroll
+      for (int j = 0; j < V; ++j)
+        if (v.v[j] > m.v[j]) m.v[j] = v.v[j];
+    }
+  }
+  m.store(out + static_cast<int64_t>(o) * c + ch);
+}
+
+template <class T, int V>
+__global__ __launch_bounds__(256) void maxpool_bwd_h(const u16* __restrict__ in, const u16* __restrict__ out, const u16* __restrict__ dout, int n_in,
+                                                     int c, const int* __restrict__ tab_in, int kvol, u16* __restrict__ din) {
+  const int cv = c / V;
+  const int64_t t = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
+  if (t >= static_cast<int64_t>(n_in) * cv) return;
+  const int i = static_cast<int>(t / cv), ch = static_cast<int>(t % cv) * V;
+  Row16<T, V> v, g;
+  v.load(in + static_cast<int64_t>(i) * c + ch);
+#pragma unroll
+  for (int j = 0; j < V; ++j) g.v[j] = 0.f;
+  for (int k = 0; k < kvol; ++k) {
+    const int o = tab_in[static_cast<int64_t>(k) * n_in + i];
+    if (o >= 0) {
+      Row16<T, V> ov, dv;
+      ov.load(out + static_cast<int64_t>(o) * c + ch);
+      dv.load(dout + static_cast<int64_t>(o) * c + ch);
+#pragma unroll
+      for (int j = 0; j < V; ++j)
+        if (ov.v[j] == v.v[j]) g.v[j] += dv.v[j];
+    }
+  }
+  g.store(din + static_cast<int64_t>(i) * c + ch);
 }
 
 // out[k, o, :] = in[tab[k][o], :] or 0
@@ -138,6 +190,43 @@ extern "C" int fv2p_sparse_maxpool_bwd(const float* in, const float* out, const 
   if (n_in == 0) return 0;
   FV2P_REQUIRE(in && out && dout && tab_in && din, FV2P_EINVAL, "maxpool_bwd: null pointer");
   hipLaunchKernelGGL(maxpool_bwd, FV2P_GRID1D(n_in * c), 0, static_cast<hipStream_t>(s), in, out, dout, (int)n_in, c, tab_in, kvol, din);
+  FV2P_LAUNCH_CHECK();
+  return 0;
+}
+template <class T>
+static void launch_maxpool_fwd_h(bool vec, const void* in, int c, const int* tab, int kvol, int64_t n_out, int flip, void* out, hipStream_t s) {
+  if (vec) hipLaunchKernelGGL((maxpool_fwd_h<T, 8>), FV2P_GRID1D(n_out * (c / 8)), 0, s, static_cast<const u16*>(in), c, tab, kvol, (int)n_out, flip, static_cast<u16*>(out));
+  else hipLaunchKernelGGL((maxpool_fwd_h<T, 1>), FV2P_GRID1D(n_out * c), 0, s, static_cast<const u16*>(in), c, tab, kvol, (int)n_out, flip, static_cast<u16*>(out));
+}
+template <class T>
+static void launch_maxpool_bwd_h(bool vec, const void* in, const void* out, const void* dout, int64_t n_in, int c, const int* tab_in, int kvol, void* din,
+                                 hipStream_t s) {
+  if (vec) hipLaunchKernelGGL((maxpool_bwd_h<T, 8>), FV2P_GRID1D(n_in * (c / 8)), 0, s, static_cast<const u16*>(in), static_cast<const u16*>(out),
+                              static_cast<const u16*>(dout), (int)n_in, c, tab_in, kvol, static_cast<u16*>(din));
+  else hipLaunchKernelGGL((maxpool_bwd_h<T, 1>), FV2P_GRID1D(n_in * c), 0, s, static_cast<const u16*>(in), static_cast<const u16*>(out),
+                          static_cast<const u16*>(dout), (int)n_in, c, tab_in, kvol, static_cast<u16*>(din));
+}
+extern "C" int fv2p_sparse_maxpool_fwd_h(const void* in, int64_t n_in, int c, const int* tab, int kvol, int64_t n_out, int flip_k, void* out, int dtype,
+                                         fv2p_stream_t s) {
+  FV2P_REQUIRE(dtype == FV2P_DT_F16 || dtype == FV2P_DT_BF16, FV2P_EINVAL, "maxpool_fwd_h: dtype %d is neither fp16 (1) nor bf16 (2)", dtype);
+  FV2P_REQUIRE(c >= 1 && kvol >= 1 && n_out >= 0 && n_in >= 0, FV2P_EINVAL, "maxpool_fwd_h: bad sizes");
+  if (n_out == 0) return 0;
+  FV2P_REQUIRE(in && tab && out, FV2P_EINVAL, "maxpool_fwd_h: null pointer");
+  const bool vec = (c % 8 == 0) && aligned16(in) && aligned16(out);
+  if (dtype == FV2P_DT_F16) launch_maxpool_fwd_h<H16>(vec, in, c, tab, kvol, n_out, flip_k & 1, out, static_cast<hipStream_t>(s));
+  else launch_maxpool_fwd_h<B16>(vec, in, c, tab, kvol, n_out, flip_k & 1, out, static_cast<hipStream_t>(s));
+  FV2P_LAUNCH_CHECK();
+  return 0;
+}
+extern "C" int fv2p_sparse_maxpool_bwd_h(const void* in, const void* out, const void* dout, int64_t n_in, int c, const int* tab_in, int kvol, void* din,
+                                         int dtype, fv2p_stream_t s) {
+  FV2P_REQUIRE(dtype == FV2P_DT_F16 || dtype == FV2P_DT_BF16, FV2P_EINVAL, "maxpool_bwd_h: dtype %d is neither fp16 (1) nor bf16 (2)", dtype);
+  FV2P_REQUIRE(c >= 1 && kvol >= 1 && n_in >= 0, FV2P_EINVAL, "maxpool_bwd_h: bad sizes");
+  if (n_in == 0) return 0;
+  FV2P_REQUIRE(in && out && dout && tab_in && din, FV2P_EINVAL, "maxpool_bwd_h: null pointer");
+  const bool vec = (c % 8 == 0) && aligned16(in) && aligned16(out) && aligned16(dout) && aligned16(din);
+  if (dtype == FV2P_DT_F16) launch_maxpool_bwd_h<H16>(vec, in, out, dout, n_in, c, tab_in, kvol, din, static_cast<hipStream_t>(s));
+  else launch_maxpool_bwd_h<B16>(vec, in, out, dout, n_in, c, tab_in, kvol, din, static_cast<hipStream_t>(s));
   FV2P_LAUNCH_CHECK();
   return 0;
 }

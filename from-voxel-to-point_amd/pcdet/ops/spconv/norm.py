@@ -5,8 +5,13 @@ nn.ReLU())`` (pcdet/models/backbones_3d/spconv_backbone.py:8-27, :75) and ``Spar
 torch modules to ``.features`` (pcdet/ops/spconv/modules.py:86-100).  ``batch_norm_relu`` is what this package's
 ``SparseSequential`` calls for that pair instead: same parameters, same running-statistics update, same result within
 fp32 rounding, kernels in csrc/batchnorm.hip.  It returns None whenever the situation is not the plain one (hooks on
-the modules, autocast, non-fp32, CPU tensors, a single row in training mode ...) and the caller then runs the torch
+the modules, autocast, CPU tensors, a single row in training mode ...) and the caller then runs the torch
 modules one by one, so error behaviour stays torch's.
+
+float16 / bfloat16 features take a route of their own (`fusable16`, `_BatchNormReLU16`, kernels in csrc/batchnorm_h.hip): x, y and
+the gradients stay in 16 bits, the arithmetic is fp32 with one rounding at the store, and the module's parameters and buffers are
+either all fp32 or all of x's dtype.  Nothing is cast on the way.  That route also takes the `residual` of a residual block's tail,
+y = relu(bn(x) + residual).
 """
 import os
 
@@ -70,8 +75,102 @@ class _BatchNormReLU(Function):
                 dbeta if (bias is not None and ctx.needs_input_grad[2]) else None, None, None)
 
 
+_DT16 = {torch.float16: 1, torch.bfloat16: 2}   # FV2P_DT_F16 / FV2P_DT_BF16 (include/fv2p_ops.h)
+_WS_BYTES16 = {}
+
+
+def _ws_bytes16(c):
+    b = _WS_BYTES16.get(c)
+    if b is None:
+        b = _WS_BYTES16[c] = _nat.call("fv2p_batchnorm_h_ws_bytes", 0, c)
+    return b
+
+
+class _BatchNormReLU16(Function):
+    """y = relu?(bn(x) [+ residual]) on float16 / bfloat16 rows.  Saves x, the fp32 mean / invstd and the parameters (and y in the
+    residual form, whose ReLU mask cannot be recomputed from x alone)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, residual, bn, relu):
+        n, c = x.shape
+        dev = x.device
+        dt = _DT16[x.dtype]
+        pd = 0 if _param_dtype(bn) in (None, torch.float32) else dt
+        batch_stats = bn.training or bn.running_mean is None
+        y = torch.empty_like(x)
+        with _nat.device_guard(dev):
+            if batch_stats:
+                stats = torch.empty((2, c), dtype=torch.float32, device=dev)
+                mean, invstd = stats[0], stats[1]
+                track = bn.training and bn.running_mean is not None
+                ws = _nat.workspace(_ws_bytes16(c), dev)
+                _nat.call("fv2p_batchnorm_forward_h", x, n, c, float(bn.eps), -1.0 if bn.momentum is None else float(bn.momentum),
+                          weight, bias, int(relu), residual, bn.running_mean if track else None, bn.running_var if track else None,
+                          bn.num_batches_tracked if track else None, mean, invstd, y, dt, pd, ws, ws.numel(), _nat.stream())
+            else:
+                # [C] values: widened here, 1 / sqrt in float64 so that invstd is the correctly rounded fp32 value
+                mean = bn.running_mean.float()
+                invstd = (1.0 / torch.sqrt(bn.running_var.double() + bn.eps)).float()
+                _nat.call("fv2p_batchnorm_apply_h", x, n, c, mean, invstd, weight, bias, int(relu), residual, y, dt, pd, _nat.stream())
+        mask_y = y if (residual is not None and relu) else None
+        ctx.save_for_backward(x, mean, invstd, weight, bias, mask_y)
+        ctx.relu, ctx.batch_stats, ctx.dt, ctx.pd, ctx.has_res = bool(relu), bool(batch_stats), dt, pd, residual is not None
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, mean, invstd, weight, bias, mask_y = ctx.saved_tensors
+        n, c = x.shape
+        dev = x.device
+        dy = dy.contiguous()
+        dx = torch.empty_like(x)
+        # the identity branch's gradient: dy * [y > 0] with a ReLU, dy itself without
+        dres = torch.empty_like(x) if (ctx.has_res and ctx.relu and ctx.needs_input_grad[3]) else None
+        dpar = torch.empty((2, c), dtype=x.dtype if ctx.pd else torch.float32, device=dev)
+        dgamma, dbeta = dpar[0], dpar[1]
+        with _nat.device_guard(dev):
+            ws = _nat.workspace(_ws_bytes16(c), dev)
+            _nat.call("fv2p_batchnorm_backward_h", x, dy, n, c, mean, invstd, weight, bias, int(ctx.relu), int(ctx.batch_stats), mask_y,
+                      dx, dres, dgamma, dbeta, ctx.dt, ctx.pd, ws, ws.numel(), _nat.stream())
+        if ctx.has_res and not ctx.relu and ctx.needs_input_grad[3]:
+            dres = dy
+        return (dx if ctx.needs_input_grad[0] else None, dgamma if (weight is not None and ctx.needs_input_grad[1]) else None,
+                dbeta if (bias is not None and ctx.needs_input_grad[2]) else None, dres, None, None)
+
+
 def _plain(module):
     return not (module._forward_hooks or module._forward_pre_hooks or module._backward_hooks)
+
+
+def _param_dtype(bn):
+    """The one dtype of bn's floating parameters and buffers, None when it has none, False when they are mixed or not on the GPU."""
+    ts = [t for t in (bn.weight, bn.bias, bn.running_mean, bn.running_var) if t is not None]
+    if any(not t.is_cuda for t in ts) or len({t.dtype for t in ts}) > 1:
+        return False
+    return ts[0].dtype if ts else None
+
+
+def fusable16(bn, relu_module, x, channels):
+    """The plain case of the (BatchNorm1d, ReLU) pair on float16 / bfloat16 features x [N, channels] the 16-bit op covers."""
+    if not _ENABLED or type(bn) is not nn.BatchNorm1d or not _plain(bn):
+        return False
+    if relu_module is not None and (type(relu_module) is not nn.ReLU or not _plain(relu_module)):
+        return False
+    if not (torch.is_tensor(x) and x.is_cuda and x.dtype in _DT16 and x.dim() == 2 and x.is_contiguous()):
+        return False
+    if torch.is_autocast_enabled() or channels != bn.num_features or x.shape[1] != channels:
+        return False
+    c = channels
+    if c > 256 and c % 8 != 0 or c > 1024:
+        return False
+    if (bn.weight is None) != (bn.bias is None):
+        return False
+    pdt = _param_dtype(bn)
+    if pdt is False or pdt not in (None, torch.float32, x.dtype):
+        return False
+    if bn.training and x.shape[0] < 2:
+        return False
+    return True
 
 
 def fusable(bn, relu_module, x, channels):
@@ -92,8 +191,19 @@ def fusable(bn, relu_module, x, channels):
     return True
 
 
-def batch_norm_relu(bn, x, relu_module=None):
-    """y = relu?(bn(x)) for x [N, C] fp32 on the GPU, or None when the fused path does not apply."""
+def batch_norm_relu(bn, x, relu_module=None, residual=None):
+    """y = relu?(bn(x)) for x [N, C] on the GPU, or None when the fused path does not apply.  float16 / bfloat16 x runs the 16-bit
+    kernels and may bring a `residual` of x's shape and dtype: y = relu?(bn(x) + residual).  (fp32 x with a residual: None.)"""
+    if torch.is_tensor(x) and x.dtype in _DT16:
+        if x.dim() != 2 or not fusable16(bn, relu_module, x, x.shape[1]) or x.shape[0] == 0:
+            return None
+        if residual is not None:
+            if not (torch.is_tensor(residual) and residual.is_cuda and residual.dtype == x.dtype and residual.shape == x.shape):
+                return None
+            residual = residual.contiguous()
+        return _BatchNormReLU16.apply(x, bn.weight, bn.bias, residual, bn, relu_module is not None)
+    if residual is not None:
+        return None
     if not (torch.is_tensor(x) and x.dim() == 2 and x.is_contiguous() and fusable(bn, relu_module, x, x.shape[1])):
         return None
     if x.shape[0] < 2:

@@ -472,8 +472,28 @@ def indice_maxpool_backward(features, out_features, out_bp, indice_pairs, indice
     return _table_maxpool_backward(features, out_features, out_bp, table)
 
 
+def _pool_dtype(*tensors):
+    """The one dtype of a max-pool call's tensors: float32 (the fp32 kernels) or a key of _DT16 (the *_h kernels of
+    csrc/sparse_aux.hip).  Nothing is converted on the way, so every tensor has to have it."""
+    dts = {t.dtype for t in tensors}
+    if len(dts) > 1:
+        raise TypeError("sparse max-pool: features, outputs and gradients must share one dtype, got "
+                        + ", ".join(sorted(str(d) for d in dts)) + " (nothing is cast here)")
+    dt = dts.pop()
+    if dt != torch.float32 and dt not in _DT16:
+        raise NotImplementedError("sparse max-pool: float32, float16 and bfloat16 only, got %s" % dt)
+    return dt
+
+
 def _table_maxpool(features, table, flip, n_out):
     _nat.require_cuda(features)
+    dt = _pool_dtype(features)
+    if dt != torch.float32:   # 16-bit rows in, 16-bit rows out: compared on the widened values, the result is an input or 0
+        f = features.contiguous()
+        out = torch.empty((n_out, f.shape[1]), dtype=dt, device=f.device)
+        with _nat.device_guard(f.device):
+            _nat.call("fv2p_sparse_maxpool_fwd_h", f, f.shape[0], f.shape[1], table, table.shape[0], n_out, int(flip), out, _DT16[dt], _nat.stream())
+        return out
     half = features.dtype == torch.half
     f = features.float().contiguous()
     out = torch.empty((n_out, f.shape[1]), dtype=torch.float32, device=f.device)
@@ -483,6 +503,13 @@ def _table_maxpool(features, table, flip, n_out):
 
 
 def _table_maxpool_backward(features, out_features, out_bp, tab_in):
+    dt = _pool_dtype(features, out_features, out_bp)
+    if dt != torch.float32:   # fp32 sum over ascending k, rounded once
+        f, o, g = features.contiguous(), out_features.contiguous(), out_bp.contiguous()
+        din = torch.empty_like(f)
+        with _nat.device_guard(f.device):
+            _nat.call("fv2p_sparse_maxpool_bwd_h", f, o, g, f.shape[0], f.shape[1], tab_in, tab_in.shape[0], din, _DT16[dt], _nat.stream())
+        return din
     half = features.dtype == torch.half
     f, o, g = features.float().contiguous(), out_features.float().contiguous(), out_bp.float().contiguous()
     din = torch.empty_like(f)

@@ -70,6 +70,8 @@ def indice_maxpool_backward_fp32(features, outFeatures, outGrad, indicePairs, in
     return _ops.indice_maxpool_backward(features, outFeatures, outGrad, indicePairs, indiceNum)
 
 
+# Same dispatch for the max-pool: float16 / bfloat16 tensors run fv2p_sparse_maxpool_fwd_h / _bwd_h (csrc/sparse_aux.hip) and come back
+# in their own dtype, no fp32 copy in between; features, outputs and gradients of one call share one dtype (TypeError otherwise).
 indice_maxpool_half = indice_maxpool_fp32
 indice_maxpool_backward_half = indice_maxpool_backward_fp32
 

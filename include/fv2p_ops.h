@@ -339,6 +339,15 @@ int fv2p_sparse_maxpool_fwd(const float* in, int64_t n_in, int c, const int* tab
                             int flip_k, float* out, fv2p_stream_t stream);
 int fv2p_sparse_maxpool_bwd(const float* in, const float* out, const float* dout, int64_t n_in, int c,
                             const int* tab_in, int kvol, float* din, fv2p_stream_t stream);
+/* The two max-pool passes on 16-bit rows.  `dtype` (FV2P_DT_F16 / FV2P_DT_BF16) names the format of in, out, dout and din; any
+ * other value returns FV2P_EINVAL with "dtype" in the message and launches nothing.  Elements are compared on their widened
+ * values: the forward result is one of its inputs or 0, so it is exact; the backward sum runs in fp32 over ascending k and
+ * is rounded to nearest even once.  One thread takes 8 channels (one 16-byte access) when c % 8 == 0 and the pointers are
+ * 16-byte aligned, one channel otherwise.  n_out == 0 (fwd) / n_in == 0 (bwd) returns 0 and launches nothing. */
+int fv2p_sparse_maxpool_fwd_h(const void* in, int64_t n_in, int c, const int* tab, int kvol, int64_t n_out,
+                              int flip_k, void* out, int dtype, fv2p_stream_t stream);
+int fv2p_sparse_maxpool_bwd_h(const void* in, const void* out, const void* dout, int64_t n_in, int c,
+                              const int* tab_in, int kvol, void* din, int dtype, fv2p_stream_t stream);
 int fv2p_sparse_group_fwd(const float* in, int64_t n_in, int c, const int* tab, int kvol, int64_t n_out,
                           int flip_k, float* out, fv2p_stream_t stream);
 int fv2p_sparse_group_bwd(const float* grad, int64_t n_out, int c, const int* tab, int kvol, int64_t n_in,
@@ -811,6 +820,41 @@ int fv2p_batchnorm_backward(const float* x, const float* dy, int64_t n, int c, c
                             const float* invstd, const float* gamma, const float* beta, int relu, int batch_stats,
                             float* dx, float* dgamma, float* dbeta, void* ws, size_t ws_bytes,
                             fv2p_stream_t stream);
+
+/* ---- BatchNorm1d (+ residual, + ReLU) on 16-bit rows -------------------------------------------------------------
+ * The layers between two fv2p_sparse_conv_rows_h calls (csrc/batchnorm_h.hip).  `dtype` (FV2P_DT_F16 / FV2P_DT_BF16) names
+ * the format of x, y, dy, dx, residual, mask_y and dz_out; any other value returns FV2P_EINVAL with "dtype" in the message and
+ * launches nothing.  `param_dtype` names the format of gamma, beta, running_mean, running_var, dgamma and dbeta: 0 = fp32 (a
+ * module kept in fp32 under a 16-bit activation stream) or the call's dtype (module.half() / .bfloat16()); any other value
+ * returns FV2P_EINVAL and launches nothing.  mean and invstd are ALWAYS fp32.  No tensor is converted to fp32 in memory.
+ * Two launches per pass (reduce with one fp64 partial per workgroup, then apply: every workgroup folds the partials in the
+ * same fixed order), no float atomics, no grid barrier: results are bit-identical from run to run.  Per element, in fp32
+ * and in this order, (x - mean) * invstd * gamma + beta (+ residual), then the ReLU (NaN passes through), then ONE rounding to
+ * nearest even at the store.  16-bit parameters are widened on read; a new running value, dgamma and dbeta are computed in
+ * fp64 (from the widened old value) and rounded once on write.
+ * Rows travel as 16-byte accesses of 8 elements when c % 8 == 0 and every tensor is 16-byte aligned (c <= 1024), element by
+ * element otherwise (c <= 256); a larger c returns FV2P_ELIMIT.  Every entry point returns 0 and launches nothing for n == 0.
+ *   fv2p_batchnorm_forward_h  : the contract of fv2p_batchnorm_forward (batch statistics, running statistics moved with
+ *                               `momentum`, < 0 = cumulative average over num_batches_tracked, which is advanced), with the
+ *                               optional residual of fv2p_batchnorm_apply_res.  Workspace: fv2p_batchnorm_h_ws_bytes.
+ *   fv2p_batchnorm_apply_h    : the same normalisation with given mean / invstd (eval mode).  One launch.
+ *   fv2p_batchnorm_backward_h : dz = dy * [y > 0], the mask recomputed from x, or read from mask_y > 0 when given (the residual
+ *                               form relu(bn(x) + identity): mask_y is that block's output); dz_out (NULL = not wanted) receives
+ *                               dz, the identity branch's gradient; dx = gamma * invstd * (dz - c1 - xhat * c2) in fp32, rounded
+ *                               once, c1 = mean dz and c2 = mean dz * xhat (both 0 when batch_stats == 0); dgamma = sum dz * xhat
+ *                               and dbeta = sum dz, folded in fixed order. */
+size_t fv2p_batchnorm_h_ws_bytes(int64_t n, int c);
+int fv2p_batchnorm_forward_h(const void* x, int64_t n, int c, float eps, float momentum, const void* gamma, const void* beta,
+                             int relu, const void* residual, void* running_mean, void* running_var,
+                             int64_t* num_batches_tracked, float* mean, float* invstd, void* y, int dtype, int param_dtype,
+                             void* ws, size_t ws_bytes, fv2p_stream_t stream);
+int fv2p_batchnorm_apply_h(const void* x, int64_t n, int c, const float* mean, const float* invstd, const void* gamma,
+                           const void* beta, int relu, const void* residual, void* y, int dtype, int param_dtype,
+                           fv2p_stream_t stream);
+int fv2p_batchnorm_backward_h(const void* x, const void* dy, int64_t n, int c, const float* mean, const float* invstd,
+                              const void* gamma, const void* beta, int relu, int batch_stats, const void* mask_y, void* dx,
+                              void* dz_out, void* dgamma, void* dbeta, int dtype, int param_dtype, void* ws, size_t ws_bytes,
+                              fv2p_stream_t stream);
 
 #ifdef __cplusplus
 }

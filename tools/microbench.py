@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Per-kernel timings on one GPU (events on the launch stream). Not part of the product or of bench.py; used to
-iterate on kernel variants:  python tools/microbench.py [conv|conv16|dcn|fps|voxel|nms|all]"""
+iterate on kernel variants:  python tools/microbench.py [conv|conv16|bn16|dcn|fps|voxel|nms|all]"""
 import os
 import sys
 import time
@@ -329,6 +329,55 @@ def conv16():
         name = f"{'subm' if mod.subm else 'conv'} {cin}->{cout} {mod.indice_key}"
         print(f"{name:30s} {f.shape[0]:6d} {n_out:6d} {p:8d} | {row[0]:8.1f} {row[1]:7.1f} {row[2]:7.1f} | {row[3]:12.1f} {row[4]:7.1f} |"
               f" {row[5]:8.1f} {row[6]:7.1f} {row[7]:7.1f} | {row[8]:8.1f} {row[9]:7.1f} {row[10]:7.1f}")
+
+
+def bn16(out_path=None):
+    """BatchNorm1d(eps=1e-3, momentum=0.01) + ReLU on [N, C] rows at the backbone's shapes, forward and forward + backward, three routes:
+      fp16 / bf16 op : the 16-bit op (csrc/batchnorm_h.hip) on float16 / bfloat16 tensors, module in the same dtype;
+      torch 16       : nn.BatchNorm1d then nn.ReLU, one by one, on the same 16-bit tensors - what ran before the 16-bit op existed;
+      fp32 op        : the fp32 fused op on fp32 tensors of the same shape.
+    Each figure: the median of ROUNDS windows of REPS calls (events on the stream, after a warm-up), the routes taken alternately
+    round by round in one process; +- is half the range of the windows.  The table also goes to `out_path` (profiles/bn_half.txt)."""
+    from torch import nn
+    from pcdet.ops.spconv import norm
+    dev = torch.device("cuda:0")
+    ROUNDS, REPS = 9, 200
+    lines = ["BatchNorm1d + ReLU, us per call: median of %d windows of %d calls, +- half the range; fwd | fwd + bwd" % (ROUNDS, REPS),
+             "%-14s %-22s %-22s %-22s %-22s" % ("shape", "fp16 op", "bf16 op", "torch 16 (fp16)", "fp32 op")]
+    for n, c in ((35000, 16), (100000, 32), (100000, 64), (100000, 128)):
+        torch.manual_seed(0)
+        x32 = torch.randn(n, c, device=dev) * 2 + 1
+        routes = []
+        for name, dt, fused in (("fp16 op", torch.float16, True), ("bf16 op", torch.bfloat16, True), ("torch 16", torch.float16, False), ("fp32 op", torch.float32, True)):
+            bn, relu = nn.BatchNorm1d(c, eps=1e-3, momentum=0.01).to(dev).to(dt), nn.ReLU()
+            x, g = x32.to(dt).requires_grad_(True), torch.randn(n, c, device=dev).to(dt)
+
+            def fwd(bn=bn, relu=relu, x=x, fused=fused):
+                y = norm.batch_norm_relu(bn, x, relu) if fused else relu(bn(x))
+                assert y is not None
+                return y
+
+            def both(fwd=fwd, g=g, x=x, bn=bn):
+                fwd().backward(g)
+                x.grad = None
+                bn.weight.grad = bn.bias.grad = None
+            with torch.no_grad():
+                fwd()
+            routes.append((name, fwd, both, [], []))
+        for _ in range(ROUNDS):
+            for _, fwd, both, tf, tb in routes:
+                with torch.no_grad():
+                    tf.append(timeit(fwd, reps=REPS, warm=20))
+                tb.append(timeit(both, reps=REPS, warm=20))
+        cell = lambda tf, tb: "%6.1f+-%4.1f |%6.1f+-%4.1f" % (np.median(tf), (max(tf) - min(tf)) / 2, np.median(tb), (max(tb) - min(tb)) / 2)
+        lines.append("%-14s " % ("[%d, %d]" % (n, c)) + " ".join("%-22s" % cell(tf, tb) for _, _, _, tf, tb in routes))
+        print(lines[-1], flush=True)
+    text = "\n".join(lines) + "\n"
+    print(text)
+    if out_path:
+        os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+        with open(out_path, "w") as fh:
+            fh.write(text)
 
 
 def dcn():
@@ -713,7 +762,10 @@ if __name__ == "__main__":
     if which == "voxelcount":
         voxelcount()
         sys.exit(0)
-    for name, fn in (("conv", conv), ("conv16", conv16), ("dcn", dcn), ("fps", fps), ("voxel", voxel), ("fpstrace", fpstrace), ("nn", nn), ("nms", nms), ("sa", sa), ("bn", bn), ("bev", bev), ("oproof", oproof)):
+    if which == "bn16" and len(sys.argv) > 2:   # python tools/microbench.py bn16 profiles/bn_half.txt
+        bn16(sys.argv[2])
+        sys.exit(0)
+    for name, fn in (("conv", conv), ("conv16", conv16), ("bn16", bn16), ("dcn", dcn), ("fps", fps), ("voxel", voxel), ("fpstrace", fpstrace), ("nn", nn), ("nms", nms), ("sa", sa), ("bn", bn), ("bev", bev), ("oproof", oproof)):
         if which in (name, "all"):
             print(f"==== {name}")
             fn()
