@@ -103,6 +103,10 @@ static inline DetLists det_lists(void* ws, size_t ws_bytes, int64_t entries, int
   return d;
 }
 
+// fv2p_scatter_add on float16 / bfloat16 rows (scatter_add.hip): out [n_dst, c] is zero-filled and WRITTEN, one rounding per row
+int scatter_add_h(int64_t entries, int c, int64_t n_dst, const int* dst_row, const int64_t* src_off, const float* coef, const void* src,
+                  int64_t src_cs, void* out, int dtype, void* ws, size_t ws_bytes, hipStream_t stream);
+
 // One launch that fills up to 8 regions with a 32-bit pattern each (replaces a run of hipMemsetAsync calls: every
 // memset is its own dispatch, ~3 us of queue time each).  Regions are 4-byte aligned, sizes multiples of 4 bytes.
 struct FillJobs {

@@ -10,6 +10,7 @@
 // thread's points and running distances in registers for the whole 16 k-round loop (the reference re-reads and
 // re-writes `temp` in global memory every round).
 #include "common.hpp"
+#include "dt16.hpp"
 #include <limits.h>
 #include <stdlib.h>
 #include <type_traits>
@@ -1821,6 +1822,73 @@ __global__ void det_group_stack_entries_k(int B, int M, int C, int nsample, int 
   off[e] = static_cast<int64_t>(pt) * C * nsample + sm;
 }
 
+
+// ---- grouping and interpolation of a stacked batch on 16-bit feature rows (float16 / bfloat16) --------------------------------------
+// grouping forward: a copy into (M, C, S), so one kernel for both formats.  thread = (point, V channels, sample), samples fastest:
+// V = 8 channels arrive as one 16-byte load of the feature row (C % 8 == 0, features 16-byte aligned) and leave as 8 element stores,
+// each of them next to the neighbouring lanes' (the lanes of a point's samples write S consecutive elements of a channel).
+// A row outside [0, N) gives zeros.
+template <int V>
+__global__ __launch_bounds__(256) void group_points_stack_h_k(int B, int M, int C, int N, int nsample, const u16* __restrict__ features,
+                                                              const int* __restrict__ feat_cnt, const int* __restrict__ idx,
+                                                              const int* __restrict__ idx_cnt, u16* __restrict__ out) {
+  const int cv = C / V;
+  const int64_t t = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
+  if (t >= static_cast<int64_t>(M) * cv * nsample) return;
+  const int s = static_cast<int>(t % nsample), ch = static_cast<int>((t / nsample) % cv) * V, pt = static_cast<int>(t / nsample / cv);
+  int bs, tmp;
+  stack_locate(pt, B, idx_cnt, &bs, &tmp);
+  const int64_t r = static_cast<int64_t>(stack_start(bs, feat_cnt)) + idx[static_cast<int64_t>(pt) * nsample + s];
+  const bool ok = r >= 0 && r < N;
+  u16* o = out + (static_cast<int64_t>(pt) * C + ch) * nsample + s;
+  if constexpr (V == 8) {
+    const uint4 q = ok ? *reinterpret_cast<const uint4*>(features + r * C + ch) : make_uint4(0, 0, 0, 0);
+    const unsigned w[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      o[static_cast<int64_t>(2 * j) * nsample] = static_cast<u16>(w[j] & 0xffffu);
+      o[static_cast<int64_t>(2 * j + 1) * nsample] = static_cast<u16>(w[j] >> 16);
+    }
+  } else {
+    *o = ok ? features[r * C + ch] : static_cast<u16>(0);
+  }
+}
+// interpolation forward: w0 * f0 + w1 * f1 + w2 * f2 on the widened rows in three_interp_stack_k's order (no contraction), one rounding.
+// A known row outside [0, m) counts as a row of zeros.
+template <class T, int V>
+__global__ __launch_bounds__(256) void three_interp_stack_h_k(int64_t n, int c, int m, const u16* __restrict__ features, const int* __restrict__ idx,
+                                                              const float* __restrict__ weight, u16* __restrict__ out) {
+  const int cv = c / V;
+  const int64_t t = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
+  if (t >= n * cv) return;
+  const int64_t pt = t / cv;
+  const int ch = static_cast<int>(t % cv) * V;
+  Row16<T, V> f[3];
+  float w[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const int r = idx[pt * 3 + k];
+    w[k] = weight[pt * 3 + k];
+    if (r >= 0 && r < m) f[k].load(features + static_cast<int64_t>(r) * c + ch);
+    else {
+#pragma unroll
+      for (int j = 0; j < V; ++j) f[k].v[j] = 0.f;
+    }
+  }
+  Row16<T, V> o;
+#pragma unroll
+  for (int j = 0; j < V; ++j) o.v[j] = w[0] * f[0].v[j] + w[1] * f[1].v[j] + w[2] * f[2].v[j];
+  o.store(out + pt * c + ch);
+}
+// entries of the 16-bit interpolation gradient (scatter_add_h): e = 3 * query + slot -> known row idx[e], source row `query` of grad_out
+__global__ void interp_entries_k(int64_t entries, int c, int m, const int* __restrict__ idx, int* __restrict__ dst, int64_t* __restrict__ off) {
+  const int64_t e = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (e >= entries) return;
+  const int r = idx[e];
+  dst[e] = r >= 0 && r < m ? r : -1;
+  off[e] = e / 3 * c;
+}
+
 }  // namespace fv2p
 using namespace fv2p;
 
@@ -2343,4 +2411,77 @@ extern "C" int fv2p_group_points_stack_grad_gather(int b, int m, int c, int n, i
   const DetLists d = det_lists(ws, ws_bytes, entries, c, false, 0);
   hipLaunchKernelGGL(det_group_stack_entries_k, G1D(entries), 0, st, b, m, c, nsample, n, idx, idx_batch_cnt, features_batch_cnt, d.dst, d.off);
   return fv2p_scatter_add(entries, c, n, d.dst, d.off, nullptr, grad_out, nsample, grad_features, d.sws, d.sws_bytes, st);
+}
+
+// ---- 16-bit forms (float16 / bfloat16 feature rows): forward kernels above, gradients through scatter_add_h -------------------------
+#define FV2P_DT16_OK(who, dtype) FV2P_REQUIRE((dtype) == FV2P_DT_F16 || (dtype) == FV2P_DT_BF16, FV2P_EINVAL, who ": dtype %d is neither fp16 (1) nor bf16 (2)", (dtype))
+extern "C" int fv2p_group_points_stack_h(int b, int m, int c, int n, int nsample, const void* features, const int* features_batch_cnt, const int* idx,
+                                         const int* idx_batch_cnt, void* out, int dtype, fv2p_stream_t s) {
+  FV2P_DT16_OK("group_points_stack_h", dtype);
+  FV2P_REQUIRE(b >= 1 && m >= 0 && c >= 1 && n >= 0 && nsample >= 0, FV2P_EINVAL, "group_points_stack_h: bad sizes");
+  if (static_cast<int64_t>(m) * nsample == 0) return 0;
+  FV2P_REQUIRE((features || n == 0) && features_batch_cnt && idx && idx_batch_cnt && out, FV2P_EINVAL, "group_points_stack_h: null pointer");
+  if (c % 8 == 0 && aligned16(features))
+    hipLaunchKernelGGL((group_points_stack_h_k<8>), G1D(static_cast<int64_t>(m) * (c / 8) * nsample), 0, STREAM(s), b, m, c, n, nsample,
+                       static_cast<const u16*>(features), features_batch_cnt, idx, idx_batch_cnt, static_cast<u16*>(out));
+  else
+    hipLaunchKernelGGL((group_points_stack_h_k<1>), G1D(static_cast<int64_t>(m) * c * nsample), 0, STREAM(s), b, m, c, n, nsample,
+                       static_cast<const u16*>(features), features_batch_cnt, idx, idx_batch_cnt, static_cast<u16*>(out));
+  FV2P_LAUNCH_CHECK();
+  return 0;
+}
+extern "C" size_t fv2p_group_points_stack_grad_h_ws_bytes(int m, int c, int nsample) { return fv2p_group_points_stack_grad_ws_bytes(m, c, nsample); }
+extern "C" int fv2p_group_points_stack_grad_h(int b, int m, int c, int n, int nsample, const void* grad_out, const int* idx, const int* idx_batch_cnt,
+                                              const int* features_batch_cnt, void* grad_features, int dtype, void* ws, size_t ws_bytes, fv2p_stream_t s) {
+  hipStream_t st = STREAM(s);
+  FV2P_DT16_OK("group_points_stack_grad_h", dtype);
+  FV2P_REQUIRE(b >= 1 && m >= 0 && c >= 1 && n >= 0 && nsample >= 0, FV2P_EINVAL, "group_points_stack_grad_h: bad sizes");
+  if (n == 0) return 0;
+  FV2P_REQUIRE(grad_features, FV2P_EINVAL, "group_points_stack_grad_h: null pointer");
+  const int64_t entries = static_cast<int64_t>(m) * nsample;
+  FV2P_REQUIRE(entries == 0 || (grad_out && idx && idx_batch_cnt && features_batch_cnt), FV2P_EINVAL, "group_points_stack_grad_h: null pointer");
+  FV2P_REQUIRE(entries < (1ll << 31), FV2P_ELIMIT, "group_points_stack_grad_h: too many entries");
+  if (entries == 0) return scatter_add_h(0, c, n, nullptr, nullptr, nullptr, nullptr, 1, grad_features, dtype, nullptr, 0, st);
+  FV2P_REQUIRE(ws && ws_bytes >= fv2p_group_points_stack_grad_h_ws_bytes(m, c, nsample), FV2P_EWORKSPACE, "group_points_stack_grad_h: workspace too small");
+  const DetLists d = det_lists(ws, ws_bytes, entries, c, false, 0);
+  hipLaunchKernelGGL(det_group_stack_entries_k, G1D(entries), 0, st, b, m, c, nsample, n, idx, idx_batch_cnt, features_batch_cnt, d.dst, d.off);
+  return scatter_add_h(entries, c, n, d.dst, d.off, nullptr, grad_out, nsample, grad_features, dtype, d.sws, d.sws_bytes, st);
+}
+template <class T>
+static void launch_three_interp_h(bool vec, int n, int c, int m, const void* features, const int* idx, const float* weight, void* out, hipStream_t st) {
+  if (vec) hipLaunchKernelGGL((three_interp_stack_h_k<T, 8>), G1D(static_cast<int64_t>(n) * (c / 8)), 0, st, static_cast<int64_t>(n), c, m,
+                              static_cast<const u16*>(features), idx, weight, static_cast<u16*>(out));
+  else hipLaunchKernelGGL((three_interp_stack_h_k<T, 1>), G1D(static_cast<int64_t>(n) * c), 0, st, static_cast<int64_t>(n), c, m,
+                          static_cast<const u16*>(features), idx, weight, static_cast<u16*>(out));
+}
+extern "C" int fv2p_three_interpolate_stack_h(int n, int c, int m, const void* features, const int* idx, const float* weight, void* out, int dtype,
+                                              fv2p_stream_t s) {
+  FV2P_DT16_OK("three_interpolate_stack_h", dtype);
+  FV2P_REQUIRE(n >= 0 && c >= 1 && m >= 0, FV2P_EINVAL, "three_interpolate_stack_h: bad sizes");
+  if (n == 0) return 0;
+  FV2P_REQUIRE((features || m == 0) && idx && weight && out, FV2P_EINVAL, "three_interpolate_stack_h: null pointer");
+  const bool vec = c % 8 == 0 && aligned16(features) && aligned16(out);
+  if (dtype == FV2P_DT_F16) launch_three_interp_h<H16>(vec, n, c, m, features, idx, weight, out, STREAM(s));
+  else launch_three_interp_h<B16>(vec, n, c, m, features, idx, weight, out, STREAM(s));
+  FV2P_LAUNCH_CHECK();
+  return 0;
+}
+extern "C" size_t fv2p_three_interpolate_stack_grad_h_ws_bytes(int n, int c, int m) {
+  (void)m;
+  return det_lists_bytes(static_cast<int64_t>(n > 0 ? n : 0) * 3, c > 0 ? c : 1, false, 0);
+}
+extern "C" int fv2p_three_interpolate_stack_grad_h(int n, int c, int m, const void* grad_out, const int* idx, const float* weight, void* grad_features,
+                                                   int dtype, void* ws, size_t ws_bytes, fv2p_stream_t s) {
+  hipStream_t st = STREAM(s);
+  FV2P_DT16_OK("three_interpolate_stack_grad_h", dtype);
+  FV2P_REQUIRE(n >= 0 && c >= 1 && m >= 0, FV2P_EINVAL, "three_interpolate_stack_grad_h: bad sizes");
+  if (m == 0) return 0;
+  FV2P_REQUIRE(grad_features && (n == 0 || (grad_out && idx && weight)), FV2P_EINVAL, "three_interpolate_stack_grad_h: null pointer");
+  const int64_t entries = static_cast<int64_t>(n) * 3;
+  FV2P_REQUIRE(entries < (1ll << 31), FV2P_ELIMIT, "three_interpolate_stack_grad_h: too many queries");
+  if (entries == 0) return scatter_add_h(0, c, m, nullptr, nullptr, nullptr, nullptr, 1, grad_features, dtype, nullptr, 0, st);
+  FV2P_REQUIRE(ws && ws_bytes >= fv2p_three_interpolate_stack_grad_h_ws_bytes(n, c, m), FV2P_EWORKSPACE, "three_interpolate_stack_grad_h: workspace too small");
+  const DetLists d = det_lists(ws, ws_bytes, entries, c, false, 0);
+  hipLaunchKernelGGL(interp_entries_k, G1D(entries), 0, st, entries, c, m, idx, d.dst, d.off);
+  return scatter_add_h(entries, c, m, d.dst, d.off, weight, grad_out, 1, grad_features, dtype, d.sws, d.sws_bytes, st);
 }

@@ -9,9 +9,12 @@
 //      acc = acc + coef * value (two roundings, no contraction: the file is built with -ffp-contract=off);
 //   3. a run inside one segment: out = out + acc.  A run over several segments: the piece of the segment it starts in, then the pieces
 //      of the following segments added one by one in segment order, and out = out + that total.
+// The kernels are templated on the element type of src and out: fp32 (fv2p_scatter_add: the total is added to out) and float16 / bfloat16
+// (scatter_add_h, the *_h gradients of pointnet2.hip: widened on load, the same fp32 association, the row's total rounded once and written).
 // Nothing depends on the launch, the stream, timing or other work on the device.  tests/test_scatter_add_gpu.py restates the order on
 // the host and compares bit for bit.
 #include "common.hpp"
+#include "dt16.hpp"
 
 namespace fv2p {
 
@@ -24,44 +27,98 @@ __global__ void scatter_keys_k(int64_t entries, int64_t n_dst, const int* __rest
   keys[e] = (static_cast<uint64_t>(r >= 0 && r < n_dst ? r : n_dst) << 32) | static_cast<uint64_t>(e);
 }
 
-struct SVec4 { float v[4]; };
-// vec: 16-byte access allowed for this address (the caller checked the base pointers, the channel count and the offset)
-__device__ __forceinline__ SVec4 sc_load4(const float* p, int64_t cs, bool vec, int c0, int c) {
-  SVec4 r;
-  if (vec) { const float4 q = *reinterpret_cast<const float4*>(p); r.v[0] = q.x; r.v[1] = q.y; r.v[2] = q.z; r.v[3] = q.w; }
-  else {
+// W channels of one lane: W = 4 (fp32 rows, one float4) or 8 (16-bit rows, one uint4); `part` is fp32 in both forms
+template <int W> struct SVec { float v[W]; };
+template <int W> __device__ __forceinline__ SVec<W> sc_zero() {
+  SVec<W> r;
 #pragma unroll
-    for (int u = 0; u < 4; ++u) r.v[u] = c0 + u < c ? p[u * cs] : 0.f;
+  for (int u = 0; u < W; ++u) r.v[u] = 0.f;
+  return r;
+}
+// vec: 16-byte access allowed for this address (the caller checked the base pointers, the channel count and the offset)
+template <int W>
+__device__ __forceinline__ SVec<W> sc_loadf(const float* p, int64_t cs, bool vec, int c0, int c) {
+  SVec<W> r;
+  if (vec) {
+#pragma unroll
+    for (int h = 0; h < W / 4; ++h) {
+      const float4 q = reinterpret_cast<const float4*>(p)[h];
+      r.v[4 * h] = q.x; r.v[4 * h + 1] = q.y; r.v[4 * h + 2] = q.z; r.v[4 * h + 3] = q.w;
+    }
+  } else {
+#pragma unroll
+    for (int u = 0; u < W; ++u) r.v[u] = c0 + u < c ? p[u * cs] : 0.f;
   }
   return r;
 }
-__device__ __forceinline__ void sc_add_store4(float* p, const SVec4& a, bool vec, int c0, int c) {   // p[u] = p[u] + a[u]
+template <int W>
+__device__ __forceinline__ void sc_storef(float* p, const SVec<W>& a, bool vec, int c0, int c) {
   if (vec) {
-    float4 q = *reinterpret_cast<float4*>(p);
-    q.x = q.x + a.v[0]; q.y = q.y + a.v[1]; q.z = q.z + a.v[2]; q.w = q.w + a.v[3];
-    *reinterpret_cast<float4*>(p) = q;
+#pragma unroll
+    for (int h = 0; h < W / 4; ++h) reinterpret_cast<float4*>(p)[h] = make_float4(a.v[4 * h], a.v[4 * h + 1], a.v[4 * h + 2], a.v[4 * h + 3]);
   } else {
 #pragma unroll
-    for (int u = 0; u < 4; ++u) if (c0 + u < c) p[u] = p[u] + a.v[u];
-  }
-}
-__device__ __forceinline__ void sc_store4(float* p, const SVec4& a, bool vec, int c0, int c) {
-  if (vec) *reinterpret_cast<float4*>(p) = make_float4(a.v[0], a.v[1], a.v[2], a.v[3]);
-  else {
-#pragma unroll
-    for (int u = 0; u < 4; ++u) if (c0 + u < c) p[u] = a.v[u];
+    for (int u = 0; u < W; ++u) if (c0 + u < c) p[u] = a.v[u];
   }
 }
 
+// The element type of src and out.  RowF32: fv2p_scatter_add, a row's total is ADDED to out.  Row16T<H16 / B16>: scatter_add_h, 16-bit
+// source rows widened on load, a row's fp32 total rounded ONCE and WRITTEN (the caller zero-filled out, every row has one writer).
+struct RowF32 {
+  using T = float;
+  static constexpr int W = 4;
+  static __device__ __forceinline__ SVec<4> load(const float* p, int64_t cs, bool vec, int c0, int c) { return sc_loadf<4>(p, cs, vec, c0, c); }
+  static __device__ __forceinline__ void commit(float* p, const SVec<4>& a, bool vec, int c0, int c) {   // p[u] = p[u] + a[u]
+    if (vec) {
+      float4 q = *reinterpret_cast<float4*>(p);
+      q.x = q.x + a.v[0]; q.y = q.y + a.v[1]; q.z = q.z + a.v[2]; q.w = q.w + a.v[3];
+      *reinterpret_cast<float4*>(p) = q;
+    } else {
+#pragma unroll
+      for (int u = 0; u < 4; ++u) if (c0 + u < c) p[u] = p[u] + a.v[u];
+    }
+  }
+};
+template <class F>
+struct Row16T {
+  using T = u16;
+  static constexpr int W = 8;
+  static __device__ __forceinline__ SVec<8> load(const u16* p, int64_t cs, bool vec, int c0, int c) {
+    SVec<8> r;
+    if (vec) {
+      Row16<F, 8> q;
+      q.load(p);
+#pragma unroll
+      for (int u = 0; u < 8; ++u) r.v[u] = q.v[u];
+    } else {
+#pragma unroll
+      for (int u = 0; u < 8; ++u) r.v[u] = c0 + u < c ? F::widen(p[u * cs]) : 0.f;
+    }
+    return r;
+  }
+  static __device__ __forceinline__ void commit(u16* p, const SVec<8>& a, bool vec, int c0, int c) {
+    if (vec) {
+      Row16<F, 8> q;
+#pragma unroll
+      for (int u = 0; u < 8; ++u) q.v[u] = a.v[u];
+      q.store(p);
+    } else {
+#pragma unroll
+      for (int u = 0; u < 8; ++u) if (c0 + u < c) p[u] = F::round(a.v[u]);
+    }
+  }
+};
+
 // Segment flags as in interp_seg_k: bit 0 the segment's first run continues from the segment before (piece in part[s][0]); bit 1 that
 // run goes on into the next segment; bit 2 the segment's last run starts here and goes on (piece in part[s][1]).
-// TPR lanes per segment (power of two, <= 64), each lane four channels per pass.  vec: src_cs == 1, c % 4 == 0 and src / out / part
-// 16-byte aligned; an entry whose source offset is not a multiple of four then still takes scalar loads.
-template <int TPR>
+// TPR lanes per segment (power of two, <= 64), each lane W channels per pass.  vec: src_cs == 1, c % W == 0 and src / out / part
+// 16-byte aligned; an entry whose source offset is not a multiple of W then still takes scalar loads.
+template <int TPR, class R>
 __global__ __launch_bounds__(256) void scatter_seg_k(int64_t n_dst, int c, int64_t entries, const uint64_t* __restrict__ keys,
                                                      const int64_t* __restrict__ src_off, const float* __restrict__ coef,
-                                                     const float* __restrict__ src, int64_t src_cs, float* __restrict__ out,
+                                                     const typename R::T* __restrict__ src, int64_t src_cs, typename R::T* __restrict__ out,
                                                      float* __restrict__ part, int* __restrict__ flags, int vec_ok) {
+  constexpr int W = R::W;
   const int64_t t = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
   const int64_t s = t / TPR;
   const int sub = static_cast<int>(t % TPR);
@@ -72,17 +129,17 @@ __global__ __launch_bounds__(256) void scatter_seg_k(int64_t n_dst, int c, int64
   const uint32_t next = i1 < entries ? static_cast<uint32_t>(keys[i1] >> 32) : 0xfffffffeu;
   const uint64_t um = static_cast<uint64_t>(n_dst);
   int fl = 0;
-  for (int c0 = 4 * sub; c0 < c; c0 += 4 * TPR) {
-    const bool vec = vec_ok && c0 + 3 < c;
-    SVec4 acc = {{0.f, 0.f, 0.f, 0.f}};
+  for (int c0 = W * sub; c0 < c; c0 += W * TPR) {
+    const bool vec = vec_ok && c0 + W - 1 < c;
+    SVec<W> acc = sc_zero<W>();
     uint32_t cur = static_cast<uint32_t>(keys[i0] >> 32);
     bool at_start = true;
     auto flush = [&](bool at_end) {
       if (cur >= um) return;   // dropped entries
       const bool from_prev = at_start && cur == prev, to_next = at_end && cur == next;
-      if (!from_prev && !to_next) sc_add_store4(out + static_cast<int64_t>(cur) * c + c0, acc, vec, c0, c);
-      else if (from_prev) { sc_store4(part + (s * 2 + 0) * c + c0, acc, vec, c0, c); fl |= to_next ? 3 : 1; }
-      else { sc_store4(part + (s * 2 + 1) * c + c0, acc, vec, c0, c); fl |= 4; }
+      if (!from_prev && !to_next) R::commit(out + static_cast<int64_t>(cur) * c + c0, acc, vec, c0, c);
+      else if (from_prev) { sc_storef<W>(part + (s * 2 + 0) * c + c0, acc, vec, c0, c); fl |= to_next ? 3 : 1; }
+      else { sc_storef<W>(part + (s * 2 + 1) * c + c0, acc, vec, c0, c); fl |= 4; }
     };
     for (int64_t i = i0; i < i1; i += 4) {
       uint64_t k[4];
@@ -93,14 +150,14 @@ __global__ __launch_bounds__(256) void scatter_seg_k(int64_t n_dst, int c, int64
         k[u] = in[u] ? keys[i + u] : ~0ull;
         ok[u] = in[u] && (k[u] >> 32) < um;
       }
-      SVec4 v[4];
+      SVec<W> v[4];
       float w[4];
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         const uint32_t e = static_cast<uint32_t>(k[u]);
         w[u] = ok[u] ? (coef ? coef[e] : 1.f) : 0.f;
         const int64_t off = ok[u] ? (src_off ? src_off[e] : static_cast<int64_t>(e) * c) : 0;
-        v[u] = ok[u] ? sc_load4(src + off + c0 * src_cs, src_cs, vec && (off & 3) == 0, c0, c) : SVec4{{0.f, 0.f, 0.f, 0.f}};
+        v[u] = ok[u] ? R::load(src + off + c0 * src_cs, src_cs, vec && (off & (W - 1)) == 0, c0, c) : sc_zero<W>();
       }
 #pragma unroll
       for (int u = 0; u < 4; ++u)
@@ -109,11 +166,11 @@ __global__ __launch_bounds__(256) void scatter_seg_k(int64_t n_dst, int c, int64
           if (row != cur) {
             flush(false);
             cur = row; at_start = false;
-            acc = SVec4{{0.f, 0.f, 0.f, 0.f}};
+            acc = sc_zero<W>();
           }
           if (ok[u]) {
 #pragma unroll
-            for (int q = 0; q < 4; ++q) acc.v[q] = acc.v[q] + w[u] * v[u].v[q];
+            for (int q = 0; q < W; ++q) acc.v[q] = acc.v[q] + w[u] * v[u].v[q];
           }
         }
     }
@@ -123,10 +180,11 @@ __global__ __launch_bounds__(256) void scatter_seg_k(int64_t n_dst, int c, int64
 }
 
 // the runs that cross segment borders: the group of the segment a run starts in adds the following segments' pieces in segment order
-template <int TPR>
+template <int TPR, class R>
 __global__ __launch_bounds__(256) void scatter_fix_k(int c, int64_t entries, int64_t segments, const uint64_t* __restrict__ keys,
-                                                     const float* __restrict__ part, const int* __restrict__ flags, float* __restrict__ out,
-                                                     int vec_ok) {
+                                                     const float* __restrict__ part, const int* __restrict__ flags,
+                                                     typename R::T* __restrict__ out, int vec_ok) {
+  constexpr int W = R::W;
   const int64_t t = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
   const int64_t s = t / TPR;
   const int sub = static_cast<int>(t % TPR);
@@ -143,16 +201,69 @@ __global__ __launch_bounds__(256) void scatter_fix_k(int c, int64_t entries, int
       if (open) { ++len; open = (f[u] & 2) != 0; }
   }
   if (s + len >= segments) len = segments - 1 - s;   // (cannot happen on a consistent flag array)
-  for (int c0 = 4 * sub; c0 < c; c0 += 4 * TPR) {
-    const bool vec = vec_ok && c0 + 3 < c;
-    SVec4 acc = sc_load4(part + (s * 2 + 1) * c + c0, 1, vec, c0, c);
+  for (int c0 = W * sub; c0 < c; c0 += W * TPR) {
+    const bool vec = vec_ok && c0 + W - 1 < c;
+    SVec<W> acc = sc_loadf<W>(part + (s * 2 + 1) * c + c0, 1, vec, c0, c);
     for (int64_t j = 1; j <= len; ++j) {
-      const SVec4 p = sc_load4(part + ((s + j) * 2 + 0) * c + c0, 1, vec, c0, c);
+      const SVec<W> p = sc_loadf<W>(part + ((s + j) * 2 + 0) * c + c0, 1, vec, c0, c);
 #pragma unroll
-      for (int q = 0; q < 4; ++q) acc.v[q] = acc.v[q] + p.v[q];
+      for (int q = 0; q < W; ++q) acc.v[q] = acc.v[q] + p.v[q];
     }
-    sc_add_store4(out + row * c + c0, acc, vec, c0, c);
+    R::commit(out + row * c + c0, acc, vec, c0, c);
   }
+}
+
+// keys, sort and the two passes for one element type; out is accumulated into (RowF32) or written where a row has entries (Row16T)
+template <class R>
+static int scatter_run(int64_t entries, int c, int64_t n_dst, const int* dst_row, const int64_t* src_off, const float* coef,
+                       const typename R::T* src, int64_t src_cs, typename R::T* out, void* ws, size_t ws_bytes, hipStream_t st) {
+  constexpr int W = R::W;
+  const int64_t segments = ceil_div(entries, kScatterSeg);
+  Carver cv(ws, ws_bytes);
+  uint64_t* keys = cv.take<uint64_t>(static_cast<size_t>(entries));
+  uint64_t* tmp = cv.take<uint64_t>(static_cast<size_t>(entries));
+  const size_t rb = radix_sort_ws_bytes(entries);
+  void* rws = cv.take<char>(rb);
+  float* part = cv.take<float>(static_cast<size_t>(segments) * 2 * c);
+  int* flags = cv.take<int>(static_cast<size_t>(segments));
+  hipLaunchKernelGGL(scatter_keys_k, dim3(static_cast<unsigned>(ceil_div(entries, 256))), dim3(256), 0, st, entries, n_dst, dst_row, keys);
+  if (int rc = radix_sort_u64(keys, tmp, entries, 32, 32 + bits_for(static_cast<uint64_t>(n_dst)), rws, rb, st)) return rc;
+  int tpr = 1;
+  while (tpr < 64 && tpr * W < c) tpr *= 2;
+  const int64_t blocks = ceil_div(segments * tpr, 256);
+  const int vec_ok = src_cs == 1 && c % W == 0 &&
+                     ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(part)) & 15) == 0;
+#define FV2P_SC(T)                                                                                                                      \
+  {                                                                                                                                     \
+    hipLaunchKernelGGL((scatter_seg_k<T, R>), dim3(static_cast<unsigned>(blocks)), dim3(256), 0, st, n_dst, c, entries, keys, src_off, coef, \
+                       src, src_cs, out, part, flags, vec_ok);                                                                          \
+    hipLaunchKernelGGL((scatter_fix_k<T, R>), dim3(static_cast<unsigned>(blocks)), dim3(256), 0, st, c, entries, segments, keys, part, flags, \
+                       out, vec_ok);                                                                                                    \
+  }
+  switch (tpr) { case 1: FV2P_SC(1) break; case 2: FV2P_SC(2) break; case 4: FV2P_SC(4) break; case 8: FV2P_SC(8) break;
+                 case 16: FV2P_SC(16) break; case 32: FV2P_SC(32) break; default: FV2P_SC(64) }
+#undef FV2P_SC
+  FV2P_LAUNCH_CHECK();
+  return 0;
+}
+
+// The 16-bit form behind the *_h gradients (pointnet2.hip): src and out are float16 / bfloat16 rows, coef stays fp32.  out [n_dst, c] is
+// WRITTEN: zero-filled here, then every row that has entries receives its fp32 total (the association above) rounded to nearest even
+// once.  Only the pieces of rows that span segments are kept in fp32 (`part`, in the workspace of fv2p_scatter_add_ws_bytes).
+int scatter_add_h(int64_t entries, int c, int64_t n_dst, const int* dst_row, const int64_t* src_off, const float* coef, const void* src,
+                  int64_t src_cs, void* out, int dtype, void* ws, size_t ws_bytes, hipStream_t st) {
+  FV2P_REQUIRE(dtype == FV2P_DT_F16 || dtype == FV2P_DT_BF16, FV2P_EINVAL, "scatter_add_h: dtype %d is neither fp16 (1) nor bf16 (2)", dtype);
+  FV2P_REQUIRE(entries >= 0 && c >= 1 && n_dst >= 0 && src_cs >= 1, FV2P_EINVAL, "scatter_add_h: bad sizes");
+  if (n_dst == 0) return 0;
+  FV2P_REQUIRE(out, FV2P_EINVAL, "scatter_add_h: null pointer");
+  FV2P_REQUIRE(entries < (1ll << 31) && n_dst < (1ll << 31) - 1, FV2P_ELIMIT, "scatter_add_h: more than 2^31 entries or rows");
+  FV2P_HIP(hipMemsetAsync(out, 0, static_cast<size_t>(n_dst) * c * sizeof(u16), st));   // rows without entries
+  if (entries == 0) return 0;
+  FV2P_REQUIRE(dst_row && src, FV2P_EINVAL, "scatter_add_h: null pointer");
+  FV2P_REQUIRE(ws && ws_bytes >= fv2p_scatter_add_ws_bytes(entries, c), FV2P_EWORKSPACE, "scatter_add_h: workspace too small");
+  if (dtype == FV2P_DT_F16)
+    return scatter_run<Row16T<H16>>(entries, c, n_dst, dst_row, src_off, coef, static_cast<const u16*>(src), src_cs, static_cast<u16*>(out), ws, ws_bytes, st);
+  return scatter_run<Row16T<B16>>(entries, c, n_dst, dst_row, src_off, coef, static_cast<const u16*>(src), src_cs, static_cast<u16*>(out), ws, ws_bytes, st);
 }
 
 }  // namespace fv2p
@@ -177,32 +288,5 @@ extern "C" int fv2p_scatter_add(int64_t entries, int c, int64_t n_dst, const int
   FV2P_REQUIRE(dst_row && src && out, FV2P_EINVAL, "scatter_add: null pointer");
   FV2P_REQUIRE(entries < (1ll << 31) && n_dst < (1ll << 31) - 1, FV2P_ELIMIT, "scatter_add: more than 2^31 entries or rows");
   FV2P_REQUIRE(ws && ws_bytes >= fv2p_scatter_add_ws_bytes(entries, c), FV2P_EWORKSPACE, "scatter_add: workspace too small");
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const int64_t segments = ceil_div(entries, kScatterSeg);
-  Carver cv(ws, ws_bytes);
-  uint64_t* keys = cv.take<uint64_t>(static_cast<size_t>(entries));
-  uint64_t* tmp = cv.take<uint64_t>(static_cast<size_t>(entries));
-  const size_t rb = radix_sort_ws_bytes(entries);
-  void* rws = cv.take<char>(rb);
-  float* part = cv.take<float>(static_cast<size_t>(segments) * 2 * c);
-  int* flags = cv.take<int>(static_cast<size_t>(segments));
-  hipLaunchKernelGGL(scatter_keys_k, dim3(static_cast<unsigned>(ceil_div(entries, 256))), dim3(256), 0, st, entries, n_dst, dst_row, keys);
-  if (int rc = radix_sort_u64(keys, tmp, entries, 32, 32 + bits_for(static_cast<uint64_t>(n_dst)), rws, rb, st)) return rc;
-  int tpr = 1;
-  while (tpr < 64 && tpr * 4 < c) tpr *= 2;
-  const int64_t blocks = ceil_div(segments * tpr, 256);
-  const int vec_ok = src_cs == 1 && (c & 3) == 0 &&
-                     ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(part)) & 15) == 0;
-#define FV2P_SC(T)                                                                                                                      \
-  {                                                                                                                                     \
-    hipLaunchKernelGGL((scatter_seg_k<T>), dim3(static_cast<unsigned>(blocks)), dim3(256), 0, st, n_dst, c, entries, keys, src_off, coef, \
-                       src, src_cs, out, part, flags, vec_ok);                                                                          \
-    hipLaunchKernelGGL((scatter_fix_k<T>), dim3(static_cast<unsigned>(blocks)), dim3(256), 0, st, c, entries, segments, keys, part, flags, \
-                       out, vec_ok);                                                                                                    \
-  }
-  switch (tpr) { case 1: FV2P_SC(1) break; case 2: FV2P_SC(2) break; case 4: FV2P_SC(4) break; case 8: FV2P_SC(8) break;
-                 case 16: FV2P_SC(16) break; case 32: FV2P_SC(32) break; default: FV2P_SC(64) }
-#undef FV2P_SC
-  FV2P_LAUNCH_CHECK();
-  return 0;
+  return scatter_run<RowF32>(entries, c, n_dst, dst_row, src_off, coef, src, src_cs, out, ws, ws_bytes, static_cast<hipStream_t>(stream));
 }

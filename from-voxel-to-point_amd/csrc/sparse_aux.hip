@@ -118,6 +118,45 @@ __global__ void group_bwd(const float* __restrict__ g, int n_out, int c, const i
   din[t] = s;
 }
 
+// The group pair on 16-bit rows.  The forward is a copy (no value is looked at: one kernel for both formats), V = 8 channels as one
+// 16-byte access when c % 8 == 0; the backward widens, sums in fp32 over ascending k and rounds once.
+template <int V>
+__global__ __launch_bounds__(256) void group_fwd_h(const u16* __restrict__ in, int c, const int* __restrict__ tab, int kvol, int n_out, int flip,
+                                                   u16* __restrict__ out) {
+  const int cv = c / V;
+  const int64_t t = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
+  const int64_t per_k = static_cast<int64_t>(n_out) * cv;
+  if (t >= per_k * kvol) return;
+  const int k = static_cast<int>(t / per_k);
+  const int64_t r = t % per_k;
+  const int o = static_cast<int>(r / cv), ch = static_cast<int>(r % cv) * V;
+  const int i = tab[static_cast<int64_t>(flip ? kvol - 1 - k : k) * n_out + o];
+  u16* dst = out + (static_cast<int64_t>(k) * n_out + o) * c + ch;
+  if constexpr (V == 8) *reinterpret_cast<uint4*>(dst) = i >= 0 ? *reinterpret_cast<const uint4*>(in + static_cast<int64_t>(i) * c + ch) : make_uint4(0, 0, 0, 0);
+  else *dst = i >= 0 ? in[static_cast<int64_t>(i) * c + ch] : static_cast<u16>(0);
+}
+template <class T, int V>
+__global__ __launch_bounds__(256) void group_bwd_h(const u16* __restrict__ g, int n_out, int c, const int* __restrict__ tab, int kvol, int n_in, int flip,
+                                                   u16* __restrict__ din) {
+  const int cv = c / V;
+  const int64_t t = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
+  if (t >= static_cast<int64_t>(n_in) * cv) return;
+  const int i = static_cast<int>(t / cv), ch = static_cast<int>(t % cv) * V;
+  Row16<T, V> s;
+#pragma unroll
+  for (int j = 0; j < V; ++j) s.v[j] = 0.f;
+  for (int k = 0; k < kvol; ++k) {
+    const int o = tab[static_cast<int64_t>(flip ? kvol - 1 - k : k) * n_in + i];
+    if (o >= 0 && o < n_out) {
+      Row16<T, V> v;
+      v.load(g + (static_cast<int64_t>(k) * n_out + o) * c + ch);
+#pragma unroll
+      for (int j = 0; j < V; ++j) s.v[j] += v.v[j];
+    }
+  }
+  s.store(din + static_cast<int64_t>(i) * c + ch);
+}
+
 // ---- SparseConvTensor.dense() --------------------------------------------------------------------
 // The reference builds the dense tensor as zeros [B, *spatial, C] -> index scatter -> permute(0, C, ...).contiguous()
 // (structure.py:57-66, used by HeightCompression, height_compression.py:10-26): three passes over the dense volume.
@@ -148,6 +187,32 @@ __global__ __launch_bounds__(256) void dense_gather(const float* __restrict__ de
   const int64_t cell = ndim == 3 ? (static_cast<int64_t>(p[1]) * d1 + p[2]) * d2 + p[3] : static_cast<int64_t>(p[1]) * d2 + p[2];
   const int64_t b = p[0];
   rows[static_cast<int64_t>(row) * c + ch] = channels_first ? dense[(b * c + ch) * vol + cell] : dense[(b * vol + cell) * c + ch];
+}
+
+// dense() and its gradient on 16-bit rows: copies, so one kernel serves float16 and bfloat16.
+//   channels_last, V = 8: thread = (row, 8 channels), one 16-byte load and one 16-byte store (c % 8 == 0, both bases 16-byte aligned)
+//   channels_last, V = 1: thread = (row, ch)
+//   channels_first      : thread = (ch, row) as in dense_scatter: rows sorted by cell -> neighbouring lanes hit neighbouring cells
+template <int V, bool kGather>
+__global__ __launch_bounds__(256) void dense_move_h(const int* __restrict__ ind, int n, int c, int ndim, int d1, int d2, int64_t vol, int channels_first,
+                                                    u16* __restrict__ rows, u16* __restrict__ dense) {
+  const int cv = c / V;
+  const int64_t t = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
+  if (t >= static_cast<int64_t>(n) * cv) return;
+  const int row = channels_first ? static_cast<int>(t % n) : static_cast<int>(t / cv);
+  const int ch = (channels_first ? static_cast<int>(t / n) : static_cast<int>(t % cv)) * V;
+  const int* p = ind + static_cast<int64_t>(row) * (ndim + 1);
+  const int64_t cell = ndim == 3 ? (static_cast<int64_t>(p[1]) * d1 + p[2]) * d2 + p[3] : static_cast<int64_t>(p[1]) * d2 + p[2];
+  const int64_t b = p[0];
+  u16* r = rows + static_cast<int64_t>(row) * c + ch;
+  u16* d = dense + (channels_first ? (b * c + ch) * vol + cell : (b * vol + cell) * c + ch);
+  if constexpr (V == 8) {
+    if (kGather) *reinterpret_cast<uint4*>(r) = *reinterpret_cast<const uint4*>(d);
+    else *reinterpret_cast<uint4*>(d) = *reinterpret_cast<const uint4*>(r);
+  } else {
+    if (kGather) *r = *d;
+    else *d = *r;
+  }
 }
 
 // ---- MeanVFE + collate of one voxelised cloud -------------------------------------------------------
@@ -249,6 +314,41 @@ extern "C" int fv2p_sparse_group_bwd(const float* grad, int64_t n_out, int c, co
   return 0;
 }
 
+template <class T>
+static void launch_group_bwd_h(bool vec, const void* g, int64_t n_out, int c, const int* tab, int kvol, int64_t n_in, int flip, void* din, hipStream_t s) {
+  if (vec) hipLaunchKernelGGL((group_bwd_h<T, 8>), FV2P_GRID1D(n_in * (c / 8)), 0, s, static_cast<const u16*>(g), (int)n_out, c, tab, kvol, (int)n_in, flip, static_cast<u16*>(din));
+  else hipLaunchKernelGGL((group_bwd_h<T, 1>), FV2P_GRID1D(n_in * c), 0, s, static_cast<const u16*>(g), (int)n_out, c, tab, kvol, (int)n_in, flip, static_cast<u16*>(din));
+}
+extern "C" int fv2p_sparse_group_fwd_h(const void* in, int64_t n_in, int c, const int* tab, int kvol, int64_t n_out, int flip_k, void* out, int dtype,
+                                       fv2p_stream_t s) {
+  FV2P_REQUIRE(dtype == FV2P_DT_F16 || dtype == FV2P_DT_BF16, FV2P_EINVAL, "group_fwd_h: dtype %d is neither fp16 (1) nor bf16 (2)", dtype);
+  FV2P_REQUIRE(c >= 1 && kvol >= 1 && n_out >= 0 && n_in >= 0, FV2P_EINVAL, "group_fwd_h: bad sizes");
+  FV2P_REQUIRE(n_out * kvol * c < (1ll << 40) && n_out < (1ll << 31) && n_in < (1ll << 31), FV2P_ELIMIT, "group_fwd_h: too many rows");
+  if (n_out == 0) return 0;
+  FV2P_REQUIRE(tab && out && (in || n_in == 0), FV2P_EINVAL, "group_fwd_h: null pointer");
+  if ((c % 8 == 0) && aligned16(in) && aligned16(out))
+    hipLaunchKernelGGL((group_fwd_h<8>), FV2P_GRID1D(n_out * (c / 8) * kvol), 0, static_cast<hipStream_t>(s), static_cast<const u16*>(in), c, tab, kvol, (int)n_out,
+                       flip_k & 1, static_cast<u16*>(out));
+  else
+    hipLaunchKernelGGL((group_fwd_h<1>), FV2P_GRID1D(n_out * c * kvol), 0, static_cast<hipStream_t>(s), static_cast<const u16*>(in), c, tab, kvol, (int)n_out,
+                       flip_k & 1, static_cast<u16*>(out));
+  FV2P_LAUNCH_CHECK();
+  return 0;
+}
+extern "C" int fv2p_sparse_group_bwd_h(const void* grad, int64_t n_out, int c, const int* tab, int kvol, int64_t n_in, int flip_k, void* din, int dtype,
+                                       fv2p_stream_t s) {
+  FV2P_REQUIRE(dtype == FV2P_DT_F16 || dtype == FV2P_DT_BF16, FV2P_EINVAL, "group_bwd_h: dtype %d is neither fp16 (1) nor bf16 (2)", dtype);
+  FV2P_REQUIRE(c >= 1 && kvol >= 1 && n_in >= 0 && n_out >= 0, FV2P_EINVAL, "group_bwd_h: bad sizes");
+  FV2P_REQUIRE(n_out < (1ll << 31) && n_in < (1ll << 31), FV2P_ELIMIT, "group_bwd_h: too many rows");
+  if (n_in == 0) return 0;
+  FV2P_REQUIRE(tab && din && (grad || n_out == 0), FV2P_EINVAL, "group_bwd_h: null pointer");
+  const bool vec = (c % 8 == 0) && aligned16(grad) && aligned16(din);
+  if (dtype == FV2P_DT_F16) launch_group_bwd_h<H16>(vec, grad, n_out, c, tab, kvol, n_in, flip_k & 1, din, static_cast<hipStream_t>(s));
+  else launch_group_bwd_h<B16>(vec, grad, n_out, c, tab, kvol, n_in, flip_k & 1, din, static_cast<hipStream_t>(s));
+  FV2P_LAUNCH_CHECK();
+  return 0;
+}
+
 extern "C" int fv2p_sparse_to_dense(const float* features, const int* indices, int64_t n, int c, int ndim, int batch,
                                     const int spatial[3], int channels_first, float* dense, fv2p_stream_t s_) {
   hipStream_t s = static_cast<hipStream_t>(s_);
@@ -274,6 +374,44 @@ extern "C" int fv2p_dense_to_sparse(const float* dense, const int* indices, int6
   const int64_t vol = ndim == 3 ? static_cast<int64_t>(spatial[0]) * spatial[1] * spatial[2] : static_cast<int64_t>(spatial[0]) * spatial[1];
   hipLaunchKernelGGL(dense_gather, FV2P_GRID1D(n * c), 0, s, dense, indices, (int)n, c, ndim, ndim == 3 ? spatial[1] : 0,
                      ndim == 3 ? spatial[2] : spatial[1], vol, channels_first, rows);
+  FV2P_LAUNCH_CHECK();
+  return 0;
+}
+// the 16-bit pair: the same arguments plus dtype; the values are moved, never looked at
+template <bool kGather>
+static void launch_dense_move_h(const int* ind, int64_t n, int c, int ndim, const int spatial[3], int64_t vol, int channels_first, void* rows, void* dense,
+                                hipStream_t s) {
+  const int d1 = ndim == 3 ? spatial[1] : 0, d2 = ndim == 3 ? spatial[2] : spatial[1];
+  if (!channels_first && c % 8 == 0 && aligned16(rows) && aligned16(dense))
+    hipLaunchKernelGGL((dense_move_h<8, kGather>), FV2P_GRID1D(n * (c / 8)), 0, s, ind, (int)n, c, ndim, d1, d2, vol, 0, static_cast<u16*>(rows), static_cast<u16*>(dense));
+  else
+    hipLaunchKernelGGL((dense_move_h<1, kGather>), FV2P_GRID1D(n * c), 0, s, ind, (int)n, c, ndim, d1, d2, vol, channels_first ? 1 : 0, static_cast<u16*>(rows),
+                       static_cast<u16*>(dense));
+}
+extern "C" int fv2p_sparse_to_dense_h(const void* features, const int* indices, int64_t n, int c, int ndim, int batch, const int spatial[3],
+                                      int channels_first, void* dense, int dtype, fv2p_stream_t s_) {
+  hipStream_t s = static_cast<hipStream_t>(s_);
+  FV2P_REQUIRE(dtype == FV2P_DT_F16 || dtype == FV2P_DT_BF16, FV2P_EINVAL, "sparse_to_dense_h: dtype %d is neither fp16 (1) nor bf16 (2)", dtype);
+  FV2P_REQUIRE(c >= 1 && n >= 0 && n < (1ll << 31) && batch >= 1 && (ndim == 2 || ndim == 3), FV2P_EINVAL, "sparse_to_dense_h: bad sizes");
+  FV2P_REQUIRE(dense && spatial, FV2P_EINVAL, "sparse_to_dense_h: null pointer");
+  FV2P_REQUIRE(n == 0 || (features && indices), FV2P_EINVAL, "sparse_to_dense_h: null pointer");
+  const int64_t vol = ndim == 3 ? static_cast<int64_t>(spatial[0]) * spatial[1] * spatial[2] : static_cast<int64_t>(spatial[0]) * spatial[1];
+  FV2P_REQUIRE(vol >= 0, FV2P_EINVAL, "sparse_to_dense_h: bad sizes");
+  if (vol > 0) FV2P_HIP(hipMemsetAsync(dense, 0, sizeof(u16) * static_cast<size_t>(batch) * c * vol, s));   // (an odd element count is no multiple of multi_fill's 4 bytes)
+  if (n == 0) return 0;
+  launch_dense_move_h<false>(indices, n, c, ndim, spatial, vol, channels_first, const_cast<void*>(features), dense, s);
+  FV2P_LAUNCH_CHECK();
+  return 0;
+}
+extern "C" int fv2p_dense_to_sparse_h(const void* dense, const int* indices, int64_t n, int c, int ndim, int batch, const int spatial[3],
+                                      int channels_first, void* rows, int dtype, fv2p_stream_t s_) {
+  hipStream_t s = static_cast<hipStream_t>(s_);
+  FV2P_REQUIRE(dtype == FV2P_DT_F16 || dtype == FV2P_DT_BF16, FV2P_EINVAL, "dense_to_sparse_h: dtype %d is neither fp16 (1) nor bf16 (2)", dtype);
+  FV2P_REQUIRE(c >= 1 && n >= 0 && n < (1ll << 31) && batch >= 1 && (ndim == 2 || ndim == 3), FV2P_EINVAL, "dense_to_sparse_h: bad sizes");
+  FV2P_REQUIRE(n == 0 || (dense && indices && rows && spatial), FV2P_EINVAL, "dense_to_sparse_h: null pointer");
+  if (n == 0) return 0;
+  const int64_t vol = ndim == 3 ? static_cast<int64_t>(spatial[0]) * spatial[1] * spatial[2] : static_cast<int64_t>(spatial[0]) * spatial[1];
+  launch_dense_move_h<true>(indices, n, c, ndim, spatial, vol, channels_first, rows, const_cast<void*>(dense), s);
   FV2P_LAUNCH_CHECK();
   return 0;
 }

@@ -518,27 +518,48 @@ def _table_maxpool_backward(features, out_features, out_bp, tab_in):
     return din.half() if half else din
 
 
+def _group_dtype(*tensors):
+    """The one dtype of a group call's tensors: float32 (the fp32 kernels) or a key of _DT16 (the *_h kernels of csrc/sparse_aux.hip).
+    Nothing is converted on the way, so every tensor has to have it."""
+    dts = {t.dtype for t in tensors}
+    if len(dts) > 1:
+        raise TypeError("sparse group: features and gradients must share one dtype, got "
+                        + ", ".join(sorted(str(d) for d in dts)) + " (nothing is cast here)")
+    dt = dts.pop()
+    if dt != torch.float32 and dt not in _DT16:
+        raise NotImplementedError("sparse group: float32, float16 and bfloat16 only, got %s" % dt)
+    return dt
+
+
 def indice_group(features, indice_pairs, indice_pair_num, num_activate_out, inverse=False, subm=False):
-    """[K, n_out, C] gather of neighbour features, zeros where no neighbour (reference ops.py:196-211)."""
-    if features.dtype != torch.float32:
-        raise NotImplementedError
+    """[K, n_out, C] gather of neighbour features, zeros where no neighbour (reference ops.py:196-211).  16-bit rows are copied as
+    they are."""
+    dt = _group_dtype(features)
     rb = _rulebook_of(indice_pairs, indice_pair_num, features.shape[0], num_activate_out, inverse)
     table, flip = rb.in_table() if inverse else rb.out_table()
     f = features.contiguous()
-    out = torch.empty((table.shape[0], num_activate_out, f.shape[1]), dtype=torch.float32, device=f.device)
+    out = torch.empty((table.shape[0], num_activate_out, f.shape[1]), dtype=dt, device=f.device)
     with _nat.device_guard(f.device):
-        _nat.call("fv2p_sparse_group_fwd", f, f.shape[0], f.shape[1], table, table.shape[0], num_activate_out, int(flip), out, _nat.stream())
+        if dt == torch.float32:
+            _nat.call("fv2p_sparse_group_fwd", f, f.shape[0], f.shape[1], table, table.shape[0], num_activate_out, int(flip), out, _nat.stream())
+        else:
+            _nat.call("fv2p_sparse_group_fwd_h", f, f.shape[0], f.shape[1], table, table.shape[0], num_activate_out, int(flip), out, _DT16[dt],
+                      _nat.stream())
     return out
 
 
 def indice_group_backward(features, out_bp, indice_pairs, indice_pair_num, inverse=False, subm=False):
-    """d_features[i] = sum_k out_bp[k, tab_in[k][i]] (reference ops.py:214-230)."""
-    if features.dtype != torch.float32:
-        raise NotImplementedError
+    """d_features[i] = sum_k out_bp[k, tab_in[k][i]] (reference ops.py:214-230); on 16-bit rows an fp32 sum over ascending k, rounded
+    once."""
+    dt = _group_dtype(features, out_bp)
     rb = _rulebook_of(indice_pairs, indice_pair_num, features.shape[0], out_bp.shape[1], inverse)
     table, flip = rb.out_table() if inverse else rb.in_table()
     g = out_bp.contiguous()
-    din = torch.empty((features.shape[0], features.shape[1]), dtype=torch.float32, device=g.device)
+    din = torch.empty((features.shape[0], features.shape[1]), dtype=dt, device=g.device)
     with _nat.device_guard(g.device):
-        _nat.call("fv2p_sparse_group_bwd", g, g.shape[1], g.shape[2], table, table.shape[0], features.shape[0], int(flip), din, _nat.stream())
+        if dt == torch.float32:
+            _nat.call("fv2p_sparse_group_bwd", g, g.shape[1], g.shape[2], table, table.shape[0], features.shape[0], int(flip), din, _nat.stream())
+        else:
+            _nat.call("fv2p_sparse_group_bwd_h", g, g.shape[1], g.shape[2], table, table.shape[0], features.shape[0], int(flip), din, _DT16[dt],
+                      _nat.stream())
     return din

@@ -5,6 +5,10 @@ import numpy as np
 import torch
 
 
+# 16-bit storage formats of the *_h entry points (FV2P_DT_F16 / FV2P_DT_BF16 of include/fv2p_ops.h)
+_DT16 = {torch.float16: 1, torch.bfloat16: 2}
+
+
 def scatter_nd(indices, updates, shape):
     """Dense tensor of `shape` with `updates` written at `indices` (no duplicate handling),
     cf. reference structure.py:5-18."""
@@ -17,7 +21,9 @@ def scatter_nd(indices, updates, shape):
 
 
 class _Dense(torch.autograd.Function):
-    """features [N, C] -> dense [B, C, *spatial] (or [B, *spatial, C]); gradient = gather at the active cells."""
+    """features [N, C] -> dense [B, C, *spatial] (or [B, *spatial, C]); gradient = gather at the active cells.
+    float32, float16 and bfloat16: the output has the dtype of `features`, the gradient rows that of the incoming gradient
+    (16-bit elements are moved as they are, fv2p_sparse_to_dense_h / fv2p_dense_to_sparse_h)."""
 
     @staticmethod
     def forward(ctx, features, indices, spatial, batch, channels_first):
@@ -25,11 +31,15 @@ class _Dense(torch.autograd.Function):
         n, c = features.shape
         ndim = len(spatial)
         shape = [batch, c] + list(spatial) if channels_first else [batch] + list(spatial) + [c]
-        out = torch.empty(shape, dtype=torch.float32, device=features.device)
+        dt = features.dtype
+        out = torch.empty(shape, dtype=dt, device=features.device)
         sp3 = list(spatial) + [1] * (3 - ndim)
         ind = indices.contiguous()
         with _nat.device_guard(features.device):
-            _nat.call("fv2p_sparse_to_dense", features.contiguous(), ind, n, c, ndim, batch, sp3, int(channels_first), out, _nat.stream())
+            if dt == torch.float32:
+                _nat.call("fv2p_sparse_to_dense", features.contiguous(), ind, n, c, ndim, batch, sp3, int(channels_first), out, _nat.stream())
+            else:
+                _nat.call("fv2p_sparse_to_dense_h", features.contiguous(), ind, n, c, ndim, batch, sp3, int(channels_first), out, _DT16[dt], _nat.stream())
         ctx.save_for_backward(ind)
         ctx.meta = (n, c, ndim, batch, sp3, channels_first)
         return out
@@ -39,9 +49,15 @@ class _Dense(torch.autograd.Function):
         import fv2p_native as _nat
         (ind,) = ctx.saved_tensors
         n, c, ndim, batch, sp3, channels_first = ctx.meta
-        rows = torch.empty((n, c), dtype=torch.float32, device=grad.device)
+        dt = grad.dtype
+        if dt != torch.float32 and dt not in _DT16:
+            raise TypeError("SparseConvTensor.dense(): the gradient must be float32, float16 or bfloat16, got %s" % dt)
+        rows = torch.empty((n, c), dtype=dt, device=grad.device)
         with _nat.device_guard(grad.device):
-            _nat.call("fv2p_dense_to_sparse", grad.contiguous(), ind, n, c, ndim, batch, sp3, int(channels_first), rows, _nat.stream())
+            if dt == torch.float32:
+                _nat.call("fv2p_dense_to_sparse", grad.contiguous(), ind, n, c, ndim, batch, sp3, int(channels_first), rows, _nat.stream())
+            else:
+                _nat.call("fv2p_dense_to_sparse_h", grad.contiguous(), ind, n, c, ndim, batch, sp3, int(channels_first), rows, _DT16[dt], _nat.stream())
         return rows, None, None, None, None
 
 
@@ -74,7 +90,7 @@ class SparseConvTensor(object):
     def dense(self, channels_first=True):
         ndim = len(self.spatial_shape)
         f = self.features
-        if f.is_cuda and f.dtype == torch.float32 and f.dim() == 2 and ndim in (2, 3) and not torch.is_autocast_enabled():
+        if f.is_cuda and (f.dtype == torch.float32 or f.dtype in _DT16) and f.dim() == 2 and ndim in (2, 3) and not torch.is_autocast_enabled():
             # one fill + one scatter straight into the requested layout (csrc/sparse_aux.hip), instead of
             # zeros -> index scatter -> permute -> contiguous over the whole dense volume
             return _Dense.apply(f, self.indices, tuple(int(v) for v in self.spatial_shape), int(self.batch_size), bool(channels_first))

@@ -352,6 +352,15 @@ int fv2p_sparse_group_fwd(const float* in, int64_t n_in, int c, const int* tab, 
                           int flip_k, float* out, fv2p_stream_t stream);
 int fv2p_sparse_group_bwd(const float* grad, int64_t n_out, int c, const int* tab, int kvol, int64_t n_in,
                           int flip_k, float* din, fv2p_stream_t stream);
+/* The group pair on 16-bit rows (the reference has indice_group_fp32 only, all.cc:64-71; these carry the features of a 16-bit
+ * backbone).  `dtype` (FV2P_DT_F16 / FV2P_DT_BF16) names the format of in / out (fwd) and grad / din (bwd); any other value returns
+ * FV2P_EINVAL with "dtype" in the message and launches nothing.  The forward copies 16-bit elements (zeros where the table holds
+ * -1); the backward sums in fp32 over ascending k and rounds to nearest even once.  8 channels per 16-byte access when c % 8 == 0
+ * and the pointers are 16-byte aligned, one channel otherwise.  n_out == 0 (fwd) / n_in == 0 (bwd) returns 0 and launches nothing. */
+int fv2p_sparse_group_fwd_h(const void* in, int64_t n_in, int c, const int* tab, int kvol, int64_t n_out,
+                            int flip_k, void* out, int dtype, fv2p_stream_t stream);
+int fv2p_sparse_group_bwd_h(const void* grad, int64_t n_out, int c, const int* tab, int kvol, int64_t n_in,
+                            int flip_k, void* din, int dtype, fv2p_stream_t stream);
 
 /* ---- (f).2: bilinear gather of BEV features at key points --------------------------------------------------------
  * Replaces bilinear_interpolate_torch and BEVGridPooling.interpolate_from_bev_features
@@ -379,6 +388,16 @@ int fv2p_sparse_to_dense(const float* features, const int* indices, int64_t n, i
                          const int spatial[3], int channels_first, float* dense, fv2p_stream_t stream);
 int fv2p_dense_to_sparse(const float* dense, const int* indices, int64_t n, int c, int ndim, int batch,
                          const int spatial[3], int channels_first, float* rows, fv2p_stream_t stream);
+/* The same pair on 16-bit features (SparseConvTensor.dense() of a .half() / .bfloat16() backbone, which the reference sends through
+ * scatter_nd + permute + contiguous as well, structure.py:57-66).  `dtype` (FV2P_DT_F16 / FV2P_DT_BF16) names the format of features /
+ * rows and dense; any other value returns FV2P_EINVAL and launches nothing.  Elements are moved, never converted: the result is bit
+ * for bit the reference's.  The forward zero-fills dense itself (also when n == 0).  channels_last with c % 8 == 0 and 16-byte
+ * aligned pointers moves 16-byte pieces of a row; every other case moves single elements, channels_first with neighbouring lanes on
+ * neighbouring cells. */
+int fv2p_sparse_to_dense_h(const void* features, const int* indices, int64_t n, int c, int ndim, int batch,
+                           const int spatial[3], int channels_first, void* dense, int dtype, fv2p_stream_t stream);
+int fv2p_dense_to_sparse_h(const void* dense, const int* indices, int64_t n, int c, int ndim, int batch,
+                           const int spatial[3], int channels_first, void* rows, int dtype, fv2p_stream_t stream);
 
 /* ---- (f).1: MeanVFE + collate of one voxelised cloud -------------------------------------------------------------
  * feats[v, :] = sum of the zero-padded point slots of voxel v / max(num_points[v], 1)   (vfe/mean_vfe.py:14-31),
@@ -613,6 +632,35 @@ int fv2p_group_points_stack_grad_gather(int b, int m, int c, int n, int nsample,
 size_t fv2p_three_interpolate_batch_grad_ws_bytes(int b, int c, int n, int m);
 int fv2p_three_interpolate_batch_grad_gather(int b, int c, int n, int m, const float* grad_out, const int* idx, const float* weight,
                                              float* grad_points, void* ws, size_t ws_bytes, fv2p_stream_t stream);
+
+/* ---- Stack grouping and interpolation on 16-bit feature rows ----------------------------------------------------------------
+ * What GroupingOperation and ThreeInterpolate of pointnet2_stack/pointnet2_utils.py:95-262 (group_points_gpu.cu, interpolate_gpu.cu:
+ * float only in the reference) do when the features come from a float16 / bfloat16 backbone.  `dtype` (FV2P_DT_F16 / FV2P_DT_BF16)
+ * names the format of the feature, output and gradient rows; idx, the batch counts and the interpolation weight stay int32 / float.
+ * Any other dtype, a null pointer or a bad size returns FV2P_EINVAL before anything is launched.  Nothing is converted to fp32 in
+ * memory; 8 channels per 16-byte access when c % 8 == 0 and the feature pointers are 16-byte aligned, one element otherwise.
+ *   fv2p_group_points_stack_h : features (n, c), idx (m, nsample) sample-local -> out (m, c, nsample), a copy of 16-bit elements;
+ *     a row outside [0, n) gives zeros.  m * nsample == 0 returns 0 and launches nothing.
+ *   fv2p_three_interpolate_stack_h : features (m, c), idx / weight (n, 3) -> out (n, c) = w0 * f0 + w1 * f1 + w2 * f2 in fp32 in the
+ *     order of fv2p_three_interpolate_stack (no contraction), rounded to nearest even once; a row outside [0, m) counts as zeros.
+ *   The two gradients exist in the fixed-order form only (the siblings of fv2p_group_points_stack_grad_gather and
+ *     fv2p_three_interpolate_stack_grad_gather; there is no atomic form): the 16-bit gradient rows are widened on load and summed in
+ *     fp32 in exactly the association of fv2p_scatter_add (entries of a row in ascending e, segments of 32 sorted positions, the
+ *     pieces of a row that spans segments added in segment order, products weight * value rounded before they are added), and every
+ *     row of grad_features is rounded ONCE.  grad_features is written: rows without entries are zero, entries outside the range are
+ *     dropped.  Only the fp32 pieces of rows that span segments live in the workspace (*_ws_bytes), never an fp32 image of a
+ *     gradient.  No float atomics; bit-identical from run to run.  Zero feature rows return 0 and launch nothing. */
+int fv2p_group_points_stack_h(int b, int m, int c, int n, int nsample, const void* features, const int* features_batch_cnt,
+                              const int* idx, const int* idx_batch_cnt, void* out, int dtype, fv2p_stream_t stream);
+size_t fv2p_group_points_stack_grad_h_ws_bytes(int m, int c, int nsample);
+int fv2p_group_points_stack_grad_h(int b, int m, int c, int n, int nsample, const void* grad_out, const int* idx,
+                                   const int* idx_batch_cnt, const int* features_batch_cnt, void* grad_features, int dtype,
+                                   void* ws, size_t ws_bytes, fv2p_stream_t stream);
+int fv2p_three_interpolate_stack_h(int n, int c, int m, const void* features, const int* idx, const float* weight, void* out,
+                                   int dtype, fv2p_stream_t stream);
+size_t fv2p_three_interpolate_stack_grad_h_ws_bytes(int n, int c, int m);
+int fv2p_three_interpolate_stack_grad_h(int n, int c, int m, const void* grad_out, const int* idx, const float* weight,
+                                        void* grad_features, int dtype, void* ws, size_t ws_bytes, fv2p_stream_t stream);
 
 /* ---- A11 consumer: fused grid set-abstraction (gather -> shared-MLP layer -> max over the samples) ---------------------
  * The part of PointnetSAModuleMSG.forward (pointnet2_batch/pointnet2_modules.py:30-62) that follows the ball query, for the

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Per-kernel timings on one GPU (events on the launch stream). Not part of the product or of bench.py; used to
-iterate on kernel variants:  python tools/microbench.py [conv|conv16|bn16|dcn|fps|voxel|nms|all]"""
+iterate on kernel variants:  python tools/microbench.py [conv|conv16|bn16|exit16|dcn|fps|voxel|nms|all]"""
 import os
 import sys
 import time
@@ -371,6 +371,91 @@ def bn16(out_path=None):
                 tb.append(timeit(both, reps=REPS, warm=20))
         cell = lambda tf, tb: "%6.1f+-%4.1f |%6.1f+-%4.1f" % (np.median(tf), (max(tf) - min(tf)) / 2, np.median(tb), (max(tb) - min(tb)) / 2)
         lines.append("%-14s " % ("[%d, %d]" % (n, c)) + " ".join("%-22s" % cell(tf, tb) for _, _, _, tf, tb in routes))
+        print(lines[-1], flush=True)
+    text = "\n".join(lines) + "\n"
+    print(text)
+    if out_path:
+        os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+        with open(out_path, "w") as fh:
+            fh.write(text)
+
+
+def exit16(out_path=None):
+    """The ways out of a 16-bit backbone at the KITTI shapes: SparseConvTensor.dense(), stack grouping (S = 16) and the stack
+    three-point interpolation, forward and backward (the backward of a graph built once, retain_graph), four routes:
+      fp16 / bf16 op : the 16-bit op (csrc/sparse_aux.hip, csrc/pointnet2.hip) on float16 / bfloat16 tensors;
+      fp32 op        : the fp32 op on fp32 tensors of the same shape (for interpolation the fixed-order gather gradient, the form the
+                       16-bit op has; 49 152 queries select it anyway);
+      former (fp16)  : what ran before the 16-bit op existed: the torch fallback of dense() (zeros, index scatter, permute, contiguous),
+                       and .float() -> fp32 op -> .to(float16) for the point ops.
+    Each figure: the median of ROUNDS windows of REPS calls (events on the stream, after a warm-up), the routes taken alternately round by
+    round in one process; +- is half the range of the windows.  The table also goes to `out_path` (profiles/exit_half.txt)."""
+    import pcdet.ops.spconv as spconv
+    from pcdet.ops.spconv.structure import scatter_nd
+    from pcdet.ops.pointnet2.pointnet2_stack import pointnet2_utils as pu
+    dev = torch.device("cuda:0")
+    ROUNDS, REPS = 7, 50
+    rng = np.random.default_rng(0)
+    lines = ["16-bit exits of the backbone, us per call: median of %d windows of %d calls, +- half the range; fwd | bwd" % (ROUNDS, REPS),
+             "%-34s %-22s %-22s %-22s %-22s" % ("op", "fp16 op", "bf16 op", "fp32 op", "former (fp16)")]
+
+    def dense_case():
+        batch, grid, c, n = 3, [2, 200, 176], 128, 30000
+        flat = np.sort(rng.choice(batch * int(np.prod(grid)), size=n, replace=False))
+        ind = torch.from_numpy(np.stack(np.unravel_index(flat, [batch] + grid), 1).astype(np.int32)).to(dev)
+
+        def make(dt, former):
+            x = torch.randn(n, c, device=dev).to(dt).requires_grad_(True)
+            if former:
+                return x, lambda: scatter_nd(ind.long(), x, [batch] + grid + [c]).permute(0, 4, 1, 2, 3).contiguous()
+            return x, lambda: spconv.SparseConvTensor(x, ind, grid, batch).dense()
+        return "dense() [2,200,176]x128 b3 n=30000", make
+
+    def group_case(name, n, c):
+        b, m, s = 4, 8192, 16
+        fc = torch.full((b,), n // b, dtype=torch.int32, device=dev)
+        ic = torch.full((b,), m // b, dtype=torch.int32, device=dev)
+        idx = torch.from_numpy(rng.integers(0, n // b, size=(m, s)).astype(np.int32)).to(dev)
+
+        def make(dt, former):
+            x = torch.randn(n, c, device=dev).to(dt).requires_grad_(True)
+            if former:
+                return x, lambda: pu.grouping_operation(x.float(), fc, idx, ic).to(dt)
+            return x, lambda: pu.grouping_operation(x, fc, idx, ic)
+        return "grouping %s [%d, %d] M=8192 S=16" % (name, n, c), make
+
+    def interp_case(c):
+        n, m = 49152, 20000
+        idx = torch.from_numpy(rng.integers(0, m, size=(n, 3)).astype(np.int32)).to(dev)
+        w = torch.rand(n, 3, device=dev)
+        w = (w / w.sum(1, keepdim=True)).contiguous()
+
+        def make(dt, former):
+            x = torch.randn(m, c, device=dev).to(dt).requires_grad_(True)
+            if former:
+                return x, lambda: pu.three_interpolate(x.float(), idx, w).to(dt)
+            return x, lambda: pu.three_interpolate(x, idx, w)
+        return "interpolation n=49152 m=20000 C=%d" % c, make
+
+    for title, make in (dense_case(), group_case("conv3", 60000, 64), group_case("conv4", 20000, 64), interp_case(16), interp_case(64), interp_case(128)):
+        routes = []
+        for name, dt, former in (("fp16 op", torch.float16, False), ("bf16 op", torch.bfloat16, False), ("fp32 op", torch.float32, False),
+                                 ("former", torch.float16, True)):
+            x, fwd = make(dt, former)
+            y = fwd()
+            g = torch.randn(y.shape, device=dev).to(y.dtype)
+
+            def bwd(y=y, g=g, x=x):
+                y.backward(g, retain_graph=True)
+                x.grad = None
+            routes.append((name, fwd, bwd, [], []))
+        for _ in range(ROUNDS):
+            for _, fwd, bwd, tf, tb in routes:
+                with torch.no_grad():
+                    tf.append(timeit(fwd, reps=REPS, warm=10))
+                tb.append(timeit(bwd, reps=REPS, warm=10))
+        cell = lambda tf, tb: "%7.1f+-%5.1f |%7.1f+-%5.1f" % (np.median(tf), (max(tf) - min(tf)) / 2, np.median(tb), (max(tb) - min(tb)) / 2)
+        lines.append("%-34s " % title + " ".join("%-22s" % cell(tf, tb) for _, _, _, tf, tb in routes))
         print(lines[-1], flush=True)
     text = "\n".join(lines) + "\n"
     print(text)
@@ -764,6 +849,9 @@ if __name__ == "__main__":
         sys.exit(0)
     if which == "bn16" and len(sys.argv) > 2:   # python tools/microbench.py bn16 profiles/bn_half.txt
         bn16(sys.argv[2])
+        sys.exit(0)
+    if which == "exit16":   # python tools/microbench.py exit16 [profiles/exit_half.txt]
+        exit16(sys.argv[2] if len(sys.argv) > 2 else None)
         sys.exit(0)
     for name, fn in (("conv", conv), ("conv16", conv16), ("bn16", bn16), ("dcn", dcn), ("fps", fps), ("voxel", voxel), ("fpstrace", fpstrace), ("nn", nn), ("nms", nms), ("sa", sa), ("bn", bn), ("bev", bev), ("oproof", oproof)):
         if which in (name, "all"):
