@@ -476,6 +476,74 @@ at::Tensor batch_norm_relu(const at::Tensor& x, const c10::optional<at::Tensor>&
                          c10::optional<at::Tensor>(), 0);
 }
 
+// ---- BatchNorm2d (+ReLU) on contiguous NCHW maps (csrc/batchnorm2d.hip) ---------------------------------------------------------------
+// Saves x, mean, invstd and the parameters; the backward pass recomputes the ReLU mask from x, so neither the pre-activation nor y is kept.
+struct BnRelu2dFn : public torch::autograd::Function<BnRelu2dFn> {
+  static at::Tensor forward(AutogradContext* ctx, const at::Tensor& x, const c10::optional<at::Tensor>& weight, const c10::optional<at::Tensor>& bias,
+                            const c10::optional<at::Tensor>& running_mean, const c10::optional<at::Tensor>& running_var,
+                            const c10::optional<at::Tensor>& num_batches_tracked, bool training, double momentum, double eps, bool relu) {
+    require_f32_cuda(x, "input");
+    TORCH_CHECK(x.dim() == 4 && x.is_contiguous(), "batch_norm2d_relu: a contiguous [N, C, H, W] map expected");
+    const int64_t n = x.size(0), c = x.size(1), hw = x.size(2) * x.size(3);
+    const bool has_running = running_mean.has_value() && running_mean->defined();
+    const bool batch_stats = training || !has_running;
+    c10::DeviceGuard guard(x.device());
+    void* stream = cur_stream(x);
+    at::Tensor y = at::empty_like(x);
+    at::Tensor mean, invstd;
+    const float* gamma = (weight.has_value() && weight->defined()) ? weight->data_ptr<float>() : nullptr;
+    const float* beta = (bias.has_value() && bias->defined()) ? bias->data_ptr<float>() : nullptr;
+    if (batch_stats) {
+      at::Tensor saved = at::empty({2, c}, x.options());
+      mean = saved[0];
+      invstd = saved[1];
+      const bool track = training && has_running;
+      int64_t* nbt = (track && num_batches_tracked.has_value() && num_batches_tracked->defined()) ? num_batches_tracked->data_ptr<int64_t>() : nullptr;
+      at::Tensor ws = workspace(fv2p_batchnorm2d_ws_bytes(n, static_cast<int>(c), hw), x, stream);
+      check(fv2p_batchnorm2d_forward(x.data_ptr<float>(), n, static_cast<int>(c), hw, static_cast<float>(eps), static_cast<float>(momentum), gamma, beta,
+                                     relu ? 1 : 0, track ? running_mean->data_ptr<float>() : nullptr, track ? running_var->data_ptr<float>() : nullptr,
+                                     nbt, mean.data_ptr<float>(), invstd.data_ptr<float>(), y.data_ptr<float>(), ws.data_ptr(),
+                                     static_cast<size_t>(ws.numel()), stream),
+            "fv2p_batchnorm2d_forward");
+    } else {
+      mean = running_mean->clone();   // a copy: the buffer may move (train() + another forward) before this call's backward runs
+      invstd = at::rsqrt(*running_var + eps);
+      check(fv2p_batchnorm2d_apply(x.data_ptr<float>(), n, static_cast<int>(c), hw, mean.data_ptr<float>(), invstd.data_ptr<float>(), gamma, beta,
+                                   relu ? 1 : 0, y.data_ptr<float>(), stream),
+            "fv2p_batchnorm2d_apply");
+    }
+    ctx->save_for_backward({x, mean, invstd, weight.has_value() ? *weight : at::Tensor(), bias.has_value() ? *bias : at::Tensor()});
+    ctx->saved_data["relu"] = relu;
+    ctx->saved_data["batch_stats"] = batch_stats;
+    return y;
+  }
+
+  static variable_list backward(AutogradContext* ctx, variable_list grads) {
+    const auto saved = ctx->get_saved_variables();
+    const at::Tensor &x = saved[0], &mean = saved[1], &invstd = saved[2], &weight = saved[3], &bias = saved[4];
+    const at::Tensor dz = grads[0].contiguous();   // (a channels_last or expanded gradient: made NCHW-contiguous)
+    const int64_t n = x.size(0), c = x.size(1), hw = x.size(2) * x.size(3);
+    c10::DeviceGuard guard(x.device());
+    void* stream = cur_stream(x);
+    at::Tensor dx = at::empty_like(x);
+    at::Tensor dpar = at::empty({2, c}, x.options());
+    at::Tensor ws = workspace(fv2p_batchnorm2d_ws_bytes(n, static_cast<int>(c), hw), x, stream);
+    check(fv2p_batchnorm2d_backward(x.data_ptr<float>(), dz.data_ptr<float>(), n, static_cast<int>(c), hw, mean.data_ptr<float>(), invstd.data_ptr<float>(),
+                                    weight.defined() ? weight.data_ptr<float>() : nullptr, bias.defined() ? bias.data_ptr<float>() : nullptr,
+                                    ctx->saved_data["relu"].toBool() ? 1 : 0, ctx->saved_data["batch_stats"].toBool() ? 1 : 0, dx.data_ptr<float>(),
+                                    dpar[0].data_ptr<float>(), dpar[1].data_ptr<float>(), ws.data_ptr(), static_cast<size_t>(ws.numel()), stream),
+          "fv2p_batchnorm2d_backward");
+    return {dx, weight.defined() ? dpar[0] : at::Tensor(), bias.defined() ? dpar[1] : at::Tensor(), at::Tensor(), at::Tensor(), at::Tensor(),
+            at::Tensor(), at::Tensor(), at::Tensor(), at::Tensor()};
+  }
+};
+
+at::Tensor batch_norm2d_relu(const at::Tensor& x, const c10::optional<at::Tensor>& weight, const c10::optional<at::Tensor>& bias,
+                             const c10::optional<at::Tensor>& running_mean, const c10::optional<at::Tensor>& running_var,
+                             const c10::optional<at::Tensor>& num_batches_tracked, bool training, double momentum, double eps, bool relu) {
+  return BnRelu2dFn::apply(x, weight, bias, running_mean, running_var, num_batches_tracked, training, momentum, eps, relu);
+}
+
 // conv -> BatchNorm1d (-> ReLU) of one backbone block in one crossing from Python (post_act_block, spconv_backbone.py:8-27)
 at::Tensor sparse_conv_bn_relu(const at::Tensor& features, const at::Tensor& weight, const at::Tensor& tab_f, int64_t flip_f, const at::Tensor& tab_b,
                                int64_t flip_b, int64_t n_out, int64_t centre, const c10::optional<at::Tensor>& pairs,
@@ -1050,6 +1118,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gate_weights", &gate_weights, "aliases of the conv weights whose gradients are joined from the side stream at the end of backward");
   m.def("sparse_conv", &sparse_conv, "fused sparse convolution with autograd (tables from a Rulebook)");
   m.def("batch_norm_relu", &batch_norm_relu, "BatchNorm1d (+ReLU) on [N, C] with autograd");
+  m.def("batch_norm2d_relu", &batch_norm2d_relu, "BatchNorm2d (+ReLU) on a contiguous [N, C, H, W] map with autograd");
   m.def("voxelize_batch_mean", &voxelize_batch_mean, py::arg("clouds"), py::arg("voxel_size"), py::arg("range_lo"), py::arg("grid"),
         py::arg("max_points"), py::arg("max_voxels"), py::arg("cloud_streams") = true, py::call_guard<py::gil_scoped_release>(),
         "voxelise a batch of clouds + MeanVFE + collate, without the GIL");

@@ -27,7 +27,7 @@ from pcdet.ops.DeformableConvolutionV2PyTorch.modules.modulated_deform_conv impo
 from pcdet.ops.iou3d_nms import iou3d_nms_utils
 
 from .backbone import VoxelResBackBone8x
-from .fv2p_model import box_corners, sigmoid_focal
+from .fv2p_model import box_corners, run_maps, sigmoid_focal
 
 
 class MGAFConfig:
@@ -68,7 +68,7 @@ class DCNBEVBackbone(nn.Module):
         from .fv2p_model import BEVBackbone
         for blk, de in zip(self.blocks, self.deblocks):
             x = BEVBackbone._block(blk, x)   # the leading ZeroPad2d + Conv2d pair as one zero-padded convolution (same sums, no padded copy)
-            ups.append(de(x))
+            ups.append(run_maps(de, x))
         return torch.cat(ups, dim=1)
 
 
@@ -99,13 +99,13 @@ class CenterAFHead(nn.Module):
                                                         nn.Conv2d(cfg.head_conv, out, 1, bias=True)) for name, out in cfg.heads})
 
     def forward(self, x):
-        x = self.feature_adapt(self.shared_conv_layer(x))
-        segm = self.heads["segm"](x)
+        x = self.feature_adapt(run_maps(self.shared_conv_layer, x))
+        segm = run_maps(self.heads["segm"], x)
         att = x + torch.sigmoid(segm.detach()).expand_as(x) * x       # mask-guided attention (center_af_head_single.py:84-92)
         preds = {"segm": segm}
         for name, head in self.heads.items():
             if name != "segm":
-                preds[name] = head(att)
+                preds[name] = run_maps(head, att)
         return preds
 
 

@@ -176,7 +176,7 @@ def reference_dcn_structure():
 def reference_call_structure():
     saved = [(_fsp, "indice_conv", _fsp.indice_conv), (_fsp, "indice_subm_conv", _fsp.indice_subm_conv),
              (_fsp, "indice_inverse_conv", _fsp.indice_inverse_conv),
-             (_norm, "fusable", _norm.fusable),
+             (_norm, "fusable", _norm.fusable), (_norm, "fusable2d", _norm.fusable2d),
              (_structure.SparseConvTensor, "dense", _structure.SparseConvTensor.dense),
              (_pn2_fused, "supported", _pn2_fused.supported),
              (_pn2_stack, "furthest_point_sample", _pn2_stack.furthest_point_sample),
@@ -188,6 +188,7 @@ def reference_call_structure():
         _fsp.indice_subm_conv = _make_conv(False, True)
         _fsp.indice_inverse_conv = _make_conv(True, False)
         _norm.fusable = lambda *a, **k: False        # every BatchNorm1d / ReLU as its own torch module, no conv-epilogue statistics
+        _norm.fusable2d = lambda *a, **k: False      # and every BatchNorm2d / ReLU of the dense maps
         _structure.SparseConvTensor.dense = _dense_torch
         _pn2_fused.supported = lambda *a, **k: False
         _pn2_stack.furthest_point_sample = plain_fps.apply

@@ -12,6 +12,9 @@ float16 / bfloat16 features take a route of their own (`fusable16`, `_BatchNormR
 the gradients stay in 16 bits, the arithmetic is fp32 with one rounding at the store, and the module's parameters and buffers are
 either all fp32 or all of x's dtype.  Nothing is cast on the way.  That route also takes the `residual` of a residual block's tail,
 y = relu(bn(x) + residual).
+
+Dense maps [N, C, H, W] have the same op for `nn.BatchNorm2d` (`fusable2d`, `batch_norm2d_relu`, `run_maps`; kernels in
+csrc/batchnorm2d.hip): at the end of this file.
 """
 import os
 
@@ -213,3 +216,118 @@ def batch_norm_relu(bn, x, relu_module=None, residual=None):
         return ext.batch_norm_relu(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked, bn.training,
                                    -1.0 if bn.momentum is None else float(bn.momentum), float(bn.eps), relu_module is not None)
     return _BatchNormReLU.apply(x, bn.weight, bn.bias, bn, relu_module is not None)
+
+
+# ---- BatchNorm2d (+ReLU) on contiguous NCHW maps (csrc/batchnorm2d.hip) ---------------------------------------------------------------
+# The pair behind every Conv2d / ConvTranspose2d of the BEV backbones (base_bev_backbone.py:35-46, :53-70).  Same contract as the row op
+# above: the module's parameters and running statistics, torch's result within fp32 rounding, None whenever the situation is not the
+# plain one - and the caller then runs the torch modules one by one.
+BN2D_CHUNK = 4096   # plane elements per workgroup (kBn2dChunk in csrc/batchnorm2d.hip); tests place shapes on either side of it
+
+
+class _BatchNorm2dReLU(Function):
+    """The ctypes form of the compiled binding's BnRelu2dFn (used when lib/fv2p_torch.so is absent)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, bn, relu):
+        n, c, h, w = x.shape
+        hw = h * w
+        dev = x.device
+        batch_stats = bn.training or bn.running_mean is None
+        y = torch.empty_like(x)
+        with _nat.device_guard(dev):
+            if batch_stats:
+                stats = torch.empty((2, c), dtype=torch.float32, device=dev)
+                mean, invstd = stats[0], stats[1]
+                track = bn.training and bn.running_mean is not None
+                ws = _nat.workspace(_nat.call("fv2p_batchnorm2d_ws_bytes", n, c, hw), dev)
+                _nat.call("fv2p_batchnorm2d_forward", x, n, c, hw, float(bn.eps), -1.0 if bn.momentum is None else float(bn.momentum),
+                          weight, bias, int(relu), bn.running_mean if track else None, bn.running_var if track else None,
+                          bn.num_batches_tracked if track else None, mean, invstd, y, ws, ws.numel(), _nat.stream())
+            else:
+                mean = bn.running_mean.clone()   # a copy: the buffer may move before this call's backward runs
+                invstd = torch.rsqrt(bn.running_var + bn.eps)
+                _nat.call("fv2p_batchnorm2d_apply", x, n, c, hw, mean, invstd, weight, bias, int(relu), y, _nat.stream())
+        ctx.save_for_backward(x, mean, invstd, weight, bias)
+        ctx.relu, ctx.batch_stats = bool(relu), bool(batch_stats)
+        return y
+
+    @staticmethod
+    def backward(ctx, dz):
+        x, mean, invstd, weight, bias = ctx.saved_tensors
+        n, c, h, w = x.shape
+        hw = h * w
+        dev = x.device
+        dz = dz.contiguous()
+        dx = torch.empty_like(x)
+        dpar = torch.empty((2, c), dtype=torch.float32, device=dev)
+        dgamma, dbeta = dpar[0], dpar[1]
+        with _nat.device_guard(dev):
+            ws = _nat.workspace(_nat.call("fv2p_batchnorm2d_ws_bytes", n, c, hw), dev)
+            _nat.call("fv2p_batchnorm2d_backward", x, dz, n, c, hw, mean, invstd, weight, bias, int(ctx.relu), int(ctx.batch_stats),
+                      dx, dgamma, dbeta, ws, ws.numel(), _nat.stream())
+        return (dx if ctx.needs_input_grad[0] else None, dgamma if (weight is not None and ctx.needs_input_grad[1]) else None,
+                dbeta if (bias is not None and ctx.needs_input_grad[2]) else None, None, None)
+
+
+def _plain_forward(module):
+    """No hooks, and `forward` is the class's own (not replaced on the instance)."""
+    return _plain(module) and "forward" not in module.__dict__
+
+
+def fusable2d(bn, relu_module, x):
+    """The plain case of the (BatchNorm2d, ReLU) pair on a map x [N, C, H, W] the fused op covers."""
+    if not _ENABLED or type(bn) is not nn.BatchNorm2d or not _plain_forward(bn):
+        return False
+    if relu_module is not None and (type(relu_module) is not nn.ReLU or not _plain_forward(relu_module)):
+        return False
+    if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4):
+        return False
+    if not x.is_contiguous() or x.shape[1] != bn.num_features:   # (channels_last maps are not NCHW-contiguous: torch's modules run)
+        return False
+    if torch.is_autocast_enabled():
+        return False
+    n, _, h, w = x.shape
+    if n * h * w < (2 if bn.training else 1):   # torch raises for a single value per channel in training mode: let it
+        return False
+    if (bn.weight is None) != (bn.bias is None):
+        return False
+    for t in (bn.weight, bn.bias, bn.running_mean, bn.running_var):
+        if t is not None and (t.dtype != torch.float32 or t.device != x.device):
+            return False
+    if bn.num_batches_tracked is not None and bn.num_batches_tracked.device != x.device:
+        return False
+    return True
+
+
+def batch_norm2d_relu(bn, x, relu_module=None):
+    """y = relu?(bn(x)) for a contiguous fp32 map x [N, C, H, W] on the GPU, or None when the fused path does not apply."""
+    if not fusable2d(bn, relu_module, x):
+        return None
+    ext = _nat.torch_ext()
+    if ext is not None:
+        return ext.batch_norm2d_relu(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked, bn.training,
+                                     -1.0 if bn.momentum is None else float(bn.momentum), float(bn.eps), relu_module is not None)
+    return _BatchNorm2dReLU.apply(x, bn.weight, bn.bias, bn, relu_module is not None)
+
+
+def run_maps(mods, x):
+    """The modules `mods` (a Sequential of Conv2d / ConvTranspose2d / BatchNorm2d / ReLU / ...) applied to the map x in order, with every
+    (BatchNorm2d, ReLU) pair - or a BatchNorm2d alone - the fused op covers as one call.  Anything else runs as the module itself."""
+    mods = list(mods)
+    i = 0
+    while i < len(mods):
+        m = mods[i]
+        if type(m) is nn.BatchNorm2d:
+            relu = mods[i + 1] if i + 1 < len(mods) and type(mods[i + 1]) is nn.ReLU else None
+            y = batch_norm2d_relu(m, x, relu)
+            if y is None and relu is not None:   # the ReLU module is not a plain one: the BatchNorm alone, then the module
+                relu = None
+                y = batch_norm2d_relu(m, x, None)
+            if y is not None:
+                x = y
+                i += 1 + (relu is not None)
+                continue
+        x = m(x)
+        i += 1
+    return x

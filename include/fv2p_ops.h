@@ -904,6 +904,34 @@ int fv2p_batchnorm_backward_h(const void* x, const void* dy, int64_t n, int c, c
                               void* dz_out, void* dgamma, void* dbeta, int dtype, int param_dtype, void* ws, size_t ws_bytes,
                               fv2p_stream_t stream);
 
+/* ---- BatchNorm2d (+ReLU) on contiguous fp32 NCHW maps [n, c, hw] ---------------------------------------------------------
+ * The pair behind every Conv2d / ConvTranspose2d of the reference's BEV backbones: nn.BatchNorm2d(eps=1e-3, momentum=0.01) +
+ * nn.ReLU() (pcdet/models/backbones_2d/base_bev_backbone.py:35-46, :53-70; dcn_bev_backbone.py:40-83), which torch runs as a
+ * spatial BatchNorm and an elementwise clamp (5 passes over the map forward, 8 backward).  Here (csrc/batchnorm2d.hip) each
+ * direction is two launches: a reduce over (sample, channel, chunk of the plane) that writes one pair of fp64 partial sums per
+ * workgroup, and an apply on the same grid in which every workgroup folds the partials of its channel in one fixed order - 3
+ * passes forward, 5 backward, no atomics, no counters, results bit-identical from run to run.  torch semantics as for
+ * fv2p_batchnorm_forward (biased variance for the normalisation, unbiased for running_var, momentum < 0 = cumulative average
+ * over num_batches_tracked, which is read before it is advanced).  hw = H * W; planes are read with 16-byte accesses when
+ * hw % 4 == 0 and the tensors are 16-byte aligned, element by element otherwise.  gamma / beta may be NULL.
+ *   fv2p_batchnorm2d_forward  : training-mode layer: mean / invstd [c] of the batch (returned for the backward pass), running
+ *                               statistics moved in place when running_mean != NULL, y = relu?((x - mean) * invstd * gamma + beta).
+ *   fv2p_batchnorm2d_apply    : the same expression with given mean / invstd (eval mode).  One launch; n == 0 launches nothing.
+ *   fv2p_batchnorm2d_backward : dy = dz * [y > 0] with y recomputed from x by the forward's own expression (y is not read);
+ *                               dgamma = sum dy * xhat, dbeta = sum dy, dx = gamma * invstd * (dy - mean(dy) - xhat * mean(dy * xhat))
+ *                               when batch_stats != 0, dx = gamma * invstd * dy otherwise.
+ * Workspace for _forward and _backward: fv2p_batchnorm2d_ws_bytes(n, c, hw) (0 for a shape that cannot be launched: FV2P_ELIMIT). */
+size_t fv2p_batchnorm2d_ws_bytes(int64_t n, int c, int64_t hw);
+int fv2p_batchnorm2d_forward(const float* x, int64_t n, int c, int64_t hw, float eps, float momentum, const float* gamma,
+                             const float* beta, int relu, float* running_mean, float* running_var,
+                             int64_t* num_batches_tracked, float* mean, float* invstd, float* y, void* ws, size_t ws_bytes,
+                             fv2p_stream_t stream);
+int fv2p_batchnorm2d_apply(const float* x, int64_t n, int c, int64_t hw, const float* mean, const float* invstd,
+                           const float* gamma, const float* beta, int relu, float* y, fv2p_stream_t stream);
+int fv2p_batchnorm2d_backward(const float* x, const float* dz, int64_t n, int c, int64_t hw, const float* mean,
+                              const float* invstd, const float* gamma, const float* beta, int relu, int batch_stats,
+                              float* dx, float* dgamma, float* dbeta, void* ws, size_t ws_bytes, fv2p_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Per-kernel timings on one GPU (events on the launch stream). Not part of the product or of bench.py; used to
-iterate on kernel variants:  python tools/microbench.py [conv|conv16|bn16|exit16|dcn|fps|voxel|nms|all]"""
+iterate on kernel variants:  python tools/microbench.py [conv|conv16|bn16|bn2d|exit16|dcn|fps|voxel|nms|all]"""
 import os
 import sys
 import time
@@ -698,6 +698,56 @@ def bn():
               f"fwd {3 * 4 * n * c / tf / 1e6:5.2f} TB/s")
 
 
+def bn2d(out_path=None):
+    """BatchNorm2d(eps=1e-3, momentum=0.01) + ReLU on the BEV branch's maps, forward and backward alone: the fused op
+    (csrc/batchnorm2d.hip, two launches per direction) against nn.BatchNorm2d then nn.ReLU.  The fraction is the algorithmic traffic
+    (3 passes over the map forward, 5 backward) per second against the 6.3 TB/s a streaming copy reaches on this part.  Each figure:
+    the median of ROUNDS windows of REPS calls, the two routes taken alternately in one process; +- is half the range of the windows."""
+    from torch import nn
+    from pcdet.ops.spconv import norm
+    dev = torch.device("cuda:0")
+    ROUNDS, REPS, COPY = 7, 20, 6.3e12
+    lines = ["BatchNorm2d + ReLU, us per call: median of %d windows of %d calls, +- half the range; fraction of %.1f TB/s at 3 (fwd) / 5 (bwd) passes"
+             % (ROUNDS, REPS, COPY / 1e12),
+             "%-20s %-32s %-32s %-18s %-18s" % ("map", "fused fwd (fraction)", "fused bwd (fraction)", "torch fwd", "torch bwd")]
+    for shape in ((3, 128, 200, 176), (3, 256, 100, 88), (3, 256, 200, 176)):
+        torch.manual_seed(0)
+        x = (torch.randn(shape, device=dev) * 2 + 1).requires_grad_(True)
+        g = torch.randn(shape, device=dev)
+        routes = []
+        for fused in (True, False):
+            bn, relu = nn.BatchNorm2d(shape[1], eps=1e-3, momentum=0.01).to(dev), nn.ReLU()
+
+            def fwd(bn=bn, relu=relu, fused=fused):
+                y = norm.batch_norm2d_relu(bn, x, relu) if fused else relu(bn(x))
+                assert y is not None
+                return y
+            y = fwd()
+
+            def bwd(y=y, bn=bn):
+                y.backward(g, retain_graph=True)
+                x.grad = None
+                bn.weight.grad = bn.bias.grad = None
+            routes.append((fwd, bwd, [], []))
+        for _ in range(ROUNDS):
+            for fwd, bwd, tf, tb in routes:
+                with torch.no_grad():
+                    tf.append(timeit(fwd, reps=REPS, warm=3))
+                tb.append(timeit(bwd, reps=REPS, warm=3))
+        nbytes = 4.0 * x.numel()
+        cell = lambda t: "%7.1f+-%5.1f" % (np.median(t), (max(t) - min(t)) / 2)
+        frac = lambda t, passes: "(%.2f)" % (passes * nbytes / (np.median(t) * 1e-6) / COPY)
+        (_, _, ff, fb), (_, _, rf, rb) = routes
+        lines.append("%-20s %-32s %-32s %-18s %-18s" % (list(shape), cell(ff) + " " + frac(ff, 3), cell(fb) + " " + frac(fb, 5), cell(rf), cell(rb)))
+        print(lines[-1], flush=True)
+    text = "\n".join(lines) + "\n"
+    print(text)
+    if out_path:
+        os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+        with open(out_path, "w") as fh:
+            fh.write(text)
+
+
 def bev():
     """Bilinear BEV gather at the FV2P size vs the reference's torch composition (permute + 4 index gathers + weights)."""
     from pcdet.models.backbones_3d.pfe import bev_grid_pooling as bgp
@@ -849,6 +899,9 @@ if __name__ == "__main__":
         sys.exit(0)
     if which == "bn16" and len(sys.argv) > 2:   # python tools/microbench.py bn16 profiles/bn_half.txt
         bn16(sys.argv[2])
+        sys.exit(0)
+    if which == "bn2d":   # python tools/microbench.py bn2d [profiles/bn2d.txt]
+        bn2d(sys.argv[2] if len(sys.argv) > 2 else None)
         sys.exit(0)
     if which == "exit16":   # python tools/microbench.py exit16 [profiles/exit_half.txt]
         exit16(sys.argv[2] if len(sys.argv) > 2 else None)
