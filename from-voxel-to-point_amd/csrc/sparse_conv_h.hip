@@ -12,6 +12,11 @@
 //              their 32 gradient rows are staged through LDS transposed ([channel][pair]) with the same 4 x 8 register transpose.
 // Channel counts that are not a multiple of 8 break the 16-byte alignment of rows: they take the element-wise, zero-filled fetch
 // of the same kernels (template parameter AL = false).  No tensor is converted to fp32 anywhere.
+//
+// fv2p_sparse_conv_rows_hw32 / fv2p_sparse_conv_wgrad_hw32 are the same kernels for fp32 MASTER weights beside 16-bit rows (template
+// parameter W32): the weight slice is read as fp32 and rounded to nearest even on its way into LDS - from LDS onward nothing differs,
+// so the result has the bits of the 16-bit entry point on weight.to(dtype) - the fp32 bias joins the fp32 accumulator unrounded, and
+// the reduce pass of the weight gradient stores its fp32 sum instead of rounding it.  These entry points make no 16-bit copy of the weights in memory.
 #include <type_traits>
 
 #include "common.hpp"
@@ -45,6 +50,13 @@ struct BF16 {
 
 __device__ __forceinline__ uint4 zero4() { return make_uint4(0u, 0u, 0u, 0u); }
 __device__ __forceinline__ uint4 load16(const u16* p) { return *reinterpret_cast<const uint4*>(p); }
+// 8 consecutive fp32 values (two 16-byte loads) rounded to T: the 16-byte group load16 would have read from the rounded tensor
+template <class T>
+__device__ __forceinline__ uint4 load16_round(const float* p) {
+  const float4 lo = *reinterpret_cast<const float4*>(p), hi = *reinterpret_cast<const float4*>(p + 4);
+  const auto pack = [](float a, float b) { return static_cast<unsigned>(T::round(a)) | (static_cast<unsigned>(T::round(b)) << 16); };
+  return make_uint4(pack(lo.x, lo.y), pack(lo.z, lo.w), pack(hi.x, hi.y), pack(hi.z, hi.w));
+}
 __device__ __forceinline__ unsigned word_of(const uint4& v, int i) { return i == 0 ? v.x : i == 1 ? v.y : i == 2 ? v.z : v.w; }
 
 // r[i] = 8 consecutive 16-bit elements of row i (i = 0..3).  Column j of the 4 x 8 block, rows 0..3 packed into 8 bytes.
@@ -74,25 +86,30 @@ constexpr int kWld = kSlice + 8;                     // LDS row stride of a slic
 
 struct RowsArgs {
   const u16* src;
-  const u16* weight;
+  const void* weight;   // 16-bit elements, or fp32 ones for the W32 kernels
   const int* tab;
-  const u16* bias;
+  const void* bias;     // as weight
   u16* dst;
   int n_dst, c_src, c_dst, kvol, flip;
   int d0, cdn;   // this launch's destination columns [d0, d0 + cdn), cdn <= 128
 };
 
 // W_k[s0 .. s0 + 32 ksn)[d0 .. d0 + 16 NB) -> ws[c_dst][c_src] (zero outside the weight: an A fragment's zero fill must not meet
-// whatever bits LDS held).  WT: the parameter is read as W_k^T, i.e. stored [K][c_dst][c_src].
-template <int NB, bool WT, bool AL>
+// whatever bits LDS held).  WT: the parameter is read as W_k^T, i.e. stored [K][c_dst][c_src].  W32: the parameter is fp32 and is
+// rounded to T here, element by element, before the register transpose.
+template <class T, int NB, bool WT, bool AL, bool W32>
 __device__ __forceinline__ void stage_weight(u16* __restrict__ ws, const RowsArgs& a, int k, int s0, int ksn) {
   const int t = threadIdx.x;
-  const u16* __restrict__ wk = a.weight + static_cast<long long>(k) * a.c_src * a.c_dst;
+  using W = std::conditional_t<W32, float, u16>;
+  const W* __restrict__ wk = static_cast<const W*>(a.weight) + static_cast<long long>(k) * a.c_src * a.c_dst;
+  const auto load8 = [](const W* p) {
+    if constexpr (W32) return load16_round<T>(p); else return load16(p);
+  };
   if constexpr (AL && WT) {
     const int chunks = ksn * 4, total = NB * 16 * chunks;
     for (int c = t; c < total; c += 256) {
       const int cd = c / chunks, cs = s0 + (c % chunks) * 8;
-      const uint4 v = (cd < a.cdn && cs < a.c_src) ? load16(wk + static_cast<long long>(a.d0 + cd) * a.c_src + cs) : zero4();
+      const uint4 v = (cd < a.cdn && cs < a.c_src) ? load8(wk + static_cast<long long>(a.d0 + cd) * a.c_src + cs) : zero4();
       *reinterpret_cast<uint4*>(ws + cd * kWld + (cs - s0)) = v;
     }
   } else if constexpr (AL) {
@@ -103,7 +120,7 @@ __device__ __forceinline__ void stage_weight(u16* __restrict__ ws, const RowsArg
       uint4 r[4];
 #pragma unroll
       for (int i = 0; i < 4; ++i)
-        r[i] = (cs + i < a.c_src && cd < a.cdn) ? load16(wk + static_cast<long long>(cs + i) * a.c_dst + a.d0 + cd) : zero4();
+        r[i] = (cs + i < a.c_src && cd < a.cdn) ? load8(wk + static_cast<long long>(cs + i) * a.c_dst + a.d0 + cd) : zero4();
 #pragma unroll
       for (int j = 0; j < 8; ++j) *reinterpret_cast<uint2*>(ws + (cd + j) * kWld + q * 4) = column_of(r, j);
     }
@@ -113,14 +130,16 @@ __device__ __forceinline__ void stage_weight(u16* __restrict__ ws, const RowsArg
     for (int e = t; e < cdp * csp; e += 256) {
       const int cd = WT ? e / csp : e % cdp, cs = WT ? e % csp : e / cdp;
       u16 v = 0;
-      if (cd < a.cdn && s0 + cs < a.c_src)
-        v = WT ? wk[static_cast<long long>(a.d0 + cd) * a.c_src + s0 + cs] : wk[static_cast<long long>(s0 + cs) * a.c_dst + a.d0 + cd];
+      if (cd < a.cdn && s0 + cs < a.c_src) {
+        const W e1 = WT ? wk[static_cast<long long>(a.d0 + cd) * a.c_src + s0 + cs] : wk[static_cast<long long>(s0 + cs) * a.c_dst + a.d0 + cd];
+        if constexpr (W32) v = T::round(e1); else v = e1;
+      }
       ws[cd * kWld + cs] = v;
     }
   }
 }
 
-template <class T, int NB, bool WT, bool AL>
+template <class T, int NB, bool WT, bool AL, bool W32>
 __global__ __launch_bounds__(256) void conv_rows_h(RowsArgs a) {
   __shared__ __align__(16) u16 ws[2][NB * 16 * kWld];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -160,7 +179,7 @@ __global__ __launch_bounds__(256) void conv_rows_h(RowsArgs a) {
           }
         }
       // two slices in LDS: the barrier below also says that every wave is done with the slice before last, whose place this one takes
-      stage_weight<NB, WT, AL>(ws[buf], a, k, s0, ksn);
+      stage_weight<T, NB, WT, AL, W32>(ws[buf], a, k, s0, ksn);
       __syncthreads();
       bool wave_any = false;
 #pragma unroll
@@ -185,7 +204,11 @@ __global__ __launch_bounds__(256) void conv_rows_h(RowsArgs a) {
     for (int nb = 0; nb < NB; ++nb) {
       const int c = nb * 16 + lr;
       if (c >= a.cdn) continue;
-      const float b = a.bias ? T::widen(a.bias[a.d0 + c]) : 0.f;
+      float b = 0.f;
+      if (a.bias) {
+        if constexpr (W32) b = static_cast<const float*>(a.bias)[a.d0 + c];   // joins the fp32 sum as it is: one rounding, at the store
+        else b = T::widen(static_cast<const u16*>(a.bias)[a.d0 + c]);
+      }
 #pragma unroll
       for (int reg = 0; reg < 4; ++reg) {
         const long long r = row0 + g * 16 + lq * 4 + reg;
@@ -202,7 +225,7 @@ struct WgradArgs {
   const u16* src;
   const u16* grad;
   const int* tab;
-  u16* dw;
+  void* dw;   // 16-bit elements, or fp32 ones (F32 reduce pass)
   int n_dst, c_src, c_dst, kvol, flip;
   int s0, csn, d0, cdn;   // this launch's block of dW: source channels [s0, s0 + csn), gradient columns [d0, d0 + cdn), each <= 128
   int rpc;                // rows per chunk (a multiple of 256)
@@ -306,9 +329,9 @@ __global__ __launch_bounds__(256) void conv_wgrad_h(WgradArgs a, float* __restri
   }
 }
 
-// dW block = chunk partials summed in ascending chunk order, rounded once
-template <class T>
-__global__ __launch_bounds__(256) void wgrad_reduce_h(const float* __restrict__ partial, int chunks, int kvol, int csn, int cdn, u16* __restrict__ dw,
+// dW block = chunk partials summed in ascending chunk order, rounded once - or, F32, stored as the fp32 sum it is
+template <class T, bool F32>
+__global__ __launch_bounds__(256) void wgrad_reduce_h(const float* __restrict__ partial, int chunks, int kvol, int csn, int cdn, void* __restrict__ dw,
                                                       int c_src, int c_dst, int s0, int d0) {
   const long long per_chunk = static_cast<long long>(kvol) * csn * cdn;
   const long long e = static_cast<long long>(blockIdx.x) * 256 + threadIdx.x;
@@ -316,7 +339,8 @@ __global__ __launch_bounds__(256) void wgrad_reduce_h(const float* __restrict__ 
   float s = 0.f;
   for (int c = 0; c < chunks; ++c) s += partial[c * per_chunk + e];
   const int cd = static_cast<int>(e % cdn), cs = static_cast<int>((e / cdn) % csn), k = static_cast<int>(e / (static_cast<long long>(cdn) * csn));
-  dw[(static_cast<long long>(k) * c_src + s0 + cs) * c_dst + d0 + cd] = T::round(s);
+  const long long o = (static_cast<long long>(k) * c_src + s0 + cs) * c_dst + d0 + cd;
+  if constexpr (F32) static_cast<float*>(dw)[o] = s; else static_cast<u16*>(dw)[o] = T::round(s);
 }
 
 int pad_blocks(int blocks) { return blocks <= 1 ? 1 : blocks <= 2 ? 2 : blocks <= 4 ? 4 : 8; }
@@ -326,22 +350,22 @@ template <class F> void for_blocks(int padded, F&& f) {
 }
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
-template <class T, bool WT, bool AL>
+template <class T, bool WT, bool AL, bool W32>
 void launch_rows(const RowsArgs& a, hipStream_t stream) {
   const dim3 grid(static_cast<unsigned>(ceil_div(a.n_dst, kTileRows))), block(256);
   for_blocks(pad_blocks(static_cast<int>(ceil_div(a.cdn, 16))), [&](auto nb) {
-    hipLaunchKernelGGL((conv_rows_h<T, decltype(nb)::value, WT, AL>), grid, block, 0, stream, a);
+    hipLaunchKernelGGL((conv_rows_h<T, decltype(nb)::value, WT, AL, W32>), grid, block, 0, stream, a);
   });
 }
-template <class T>
+template <class T, bool W32>
 void launch_rows(const RowsArgs& a, bool wt, bool al, hipStream_t stream) {
-  if (wt) { if (al) launch_rows<T, true, true>(a, stream); else launch_rows<T, true, false>(a, stream); }
-  else    { if (al) launch_rows<T, false, true>(a, stream); else launch_rows<T, false, false>(a, stream); }
+  if (wt) { if (al) launch_rows<T, true, true, W32>(a, stream); else launch_rows<T, true, false, W32>(a, stream); }
+  else    { if (al) launch_rows<T, false, true, W32>(a, stream); else launch_rows<T, false, false, W32>(a, stream); }
 }
 
 int wgrad_rows_per_chunk(int64_t n_dst) { return n_dst <= 32768 ? 512 : n_dst <= 131072 ? 1024 : 2048; }
 
-template <class T, bool AL>
+template <class T, bool AL, bool F32>
 void launch_wgrad(const WgradArgs& a, float* partial, unsigned chunks, hipStream_t stream) {
   const dim3 grid(chunks, static_cast<unsigned>(a.kvol)), block(256);
   const size_t lds = static_cast<size_t>(a.rpc) * 2 * sizeof(int);
@@ -351,38 +375,35 @@ void launch_wgrad(const WgradArgs& a, float* partial, unsigned chunks, hipStream
     });
   });
   const long long per_chunk = static_cast<long long>(a.kvol) * a.csn * a.cdn;
-  hipLaunchKernelGGL(wgrad_reduce_h<T>, dim3(static_cast<unsigned>(ceil_div(per_chunk, 256))), block, 0, stream, partial, static_cast<int>(chunks),
+  hipLaunchKernelGGL((wgrad_reduce_h<T, F32>), dim3(static_cast<unsigned>(ceil_div(per_chunk, 256))), block, 0, stream, partial, static_cast<int>(chunks),
                      a.kvol, a.csn, a.cdn, a.dw, a.c_src, a.c_dst, a.s0, a.d0);
 }
 
-}  // namespace
-}  // namespace fv2p
-
-using namespace fv2p;
-
-extern "C" int fv2p_sparse_conv_rows_h(const void* src, int64_t n_src, int c_src, const void* weight, int kvol, const int* tab, int64_t n_dst,
-                                       int c_dst, int flip_k, int transpose_w, const void* bias, void* dst, int dtype, fv2p_stream_t stream_) {
-  FV2P_REQUIRE(dtype == FV2P_DT_F16 || dtype == FV2P_DT_BF16, FV2P_EINVAL, "sparse_conv_rows_h: dtype %d is neither fp16 (1) nor bf16 (2)", dtype);
-  FV2P_REQUIRE(c_src >= 1 && c_dst >= 1 && kvol >= 1 && n_dst >= 0 && n_src >= 0, FV2P_EINVAL, "sparse_conv_rows_h: bad sizes");
+// The two row-conv entry points: `name` is the one the caller used (it opens every message), W32 says that weight and bias are fp32.
+template <bool W32>
+int conv_rows_entry(const char* name, const void* src, int64_t n_src, int c_src, const void* weight, int kvol, const int* tab, int64_t n_dst, int c_dst,
+                    int flip_k, int transpose_w, const void* bias, void* dst, int dtype, fv2p_stream_t stream_) {
+  FV2P_REQUIRE(dtype == FV2P_DT_F16 || dtype == FV2P_DT_BF16, FV2P_EINVAL, "%s: dtype %d is neither fp16 (1) nor bf16 (2)", name, dtype);
+  FV2P_REQUIRE(c_src >= 1 && c_dst >= 1 && kvol >= 1 && n_dst >= 0 && n_src >= 0, FV2P_EINVAL, "%s: bad sizes", name);
   if (n_dst == 0) return 0;
-  FV2P_REQUIRE(weight && tab && dst && (src || n_src == 0), FV2P_EINVAL, "sparse_conv_rows_h: null pointer");
-  FV2P_REQUIRE(n_dst < (1ll << 31) - kTileRows, FV2P_ELIMIT, "sparse_conv_rows_h: too many rows");
+  FV2P_REQUIRE(weight && tab && dst && (src || n_src == 0), FV2P_EINVAL, "%s: null pointer", name);
+  FV2P_REQUIRE(n_dst < (1ll << 31) - kTileRows, FV2P_ELIMIT, "%s: too many rows", name);
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   RowsArgs a;
-  a.src = static_cast<const u16*>(src); a.weight = static_cast<const u16*>(weight); a.tab = tab;
-  a.bias = static_cast<const u16*>(bias); a.dst = static_cast<u16*>(dst);
+  a.src = static_cast<const u16*>(src); a.weight = weight; a.tab = tab;
+  a.bias = bias; a.dst = static_cast<u16*>(dst);
   a.n_dst = static_cast<int>(n_dst); a.c_src = c_src; a.c_dst = c_dst; a.kvol = kvol; a.flip = flip_k & FV2P_TAB_FLIP;
   const bool al = c_src % 8 == 0 && c_dst % 8 == 0 && aligned16(src) && aligned16(weight);
   for (int d0 = 0; d0 < c_dst; d0 += 128) {   // every launch sums over ALL source channels: one rounding per element whatever c_src
     a.d0 = d0; a.cdn = c_dst - d0 < 128 ? c_dst - d0 : 128;
-    if (dtype == FV2P_DT_F16) launch_rows<F16>(a, transpose_w != 0, al, stream);
-    else launch_rows<BF16>(a, transpose_w != 0, al, stream);
+    if (dtype == FV2P_DT_F16) launch_rows<F16, W32>(a, transpose_w != 0, al, stream);
+    else launch_rows<BF16, W32>(a, transpose_w != 0, al, stream);
   }
   FV2P_LAUNCH_CHECK();
   return 0;
 }
 
-extern "C" size_t fv2p_sparse_conv_wgrad_h_ws_bytes(int64_t n_dst, int c_src, int c_dst, int kvol) {
+size_t wgrad_ws_bytes(int64_t n_dst, int c_src, int c_dst, int kvol) {
   const int64_t n = n_dst > 0 ? n_dst : 1;
   const int cd = c_dst < 128 ? c_dst : 128, cs = c_src < 128 ? c_src : 128;
   Sizer s;
@@ -390,18 +411,19 @@ extern "C" size_t fv2p_sparse_conv_wgrad_h_ws_bytes(int64_t n_dst, int c_src, in
   return s.bytes();
 }
 
-extern "C" int fv2p_sparse_conv_wgrad_h(const void* src, int64_t n_src, int c_src, const void* grad, const int* tab, int64_t n_dst, int c_dst,
-                                        int kvol, int flip_k, void* dweight, int dtype, void* ws, size_t ws_bytes, fv2p_stream_t stream_) {
-  FV2P_REQUIRE(dtype == FV2P_DT_F16 || dtype == FV2P_DT_BF16, FV2P_EINVAL, "sparse_conv_wgrad_h: dtype %d is neither fp16 (1) nor bf16 (2)", dtype);
-  FV2P_REQUIRE(c_src >= 1 && c_dst >= 1 && kvol >= 1 && n_dst >= 0 && n_src >= 0, FV2P_EINVAL, "sparse_conv_wgrad_h: bad sizes");
+// The two weight-gradient entry points: F32 says that dweight is fp32 (the reduce pass then does not round).
+template <bool F32>
+int conv_wgrad_entry(const char* name, const void* src, int64_t n_src, int c_src, const void* grad, const int* tab, int64_t n_dst, int c_dst, int kvol,
+                     int flip_k, void* dweight, int dtype, void* ws, size_t ws_bytes, fv2p_stream_t stream_) {
+  FV2P_REQUIRE(dtype == FV2P_DT_F16 || dtype == FV2P_DT_BF16, FV2P_EINVAL, "%s: dtype %d is neither fp16 (1) nor bf16 (2)", name, dtype);
+  FV2P_REQUIRE(c_src >= 1 && c_dst >= 1 && kvol >= 1 && n_dst >= 0 && n_src >= 0, FV2P_EINVAL, "%s: bad sizes", name);
   if (n_dst == 0) return 0;
-  FV2P_REQUIRE(dweight && (src || n_src == 0) && grad && tab, FV2P_EINVAL, "sparse_conv_wgrad_h: null pointer");
-  FV2P_REQUIRE(n_dst < (1ll << 31) - 4096, FV2P_ELIMIT, "sparse_conv_wgrad_h: too many rows");
-  FV2P_REQUIRE(ws && ws_bytes >= fv2p_sparse_conv_wgrad_h_ws_bytes(n_dst, c_src, c_dst, kvol), FV2P_EWORKSPACE,
-               "sparse_conv_wgrad_h: workspace too small");
+  FV2P_REQUIRE(dweight && (src || n_src == 0) && grad && tab, FV2P_EINVAL, "%s: null pointer", name);
+  FV2P_REQUIRE(n_dst < (1ll << 31) - 4096, FV2P_ELIMIT, "%s: too many rows", name);
+  FV2P_REQUIRE(ws && ws_bytes >= wgrad_ws_bytes(n_dst, c_src, c_dst, kvol), FV2P_EWORKSPACE, "%s: workspace too small", name);
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   WgradArgs a;
-  a.src = static_cast<const u16*>(src); a.grad = static_cast<const u16*>(grad); a.tab = tab; a.dw = static_cast<u16*>(dweight);
+  a.src = static_cast<const u16*>(src); a.grad = static_cast<const u16*>(grad); a.tab = tab; a.dw = dweight;
   a.n_dst = static_cast<int>(n_dst); a.c_src = c_src; a.c_dst = c_dst; a.kvol = kvol; a.flip = flip_k & FV2P_TAB_FLIP;
   a.rpc = wgrad_rows_per_chunk(n_dst);
   const unsigned chunks = static_cast<unsigned>(ceil_div(n_dst, a.rpc));
@@ -411,9 +433,36 @@ extern "C" int fv2p_sparse_conv_wgrad_h(const void* src, int64_t n_src, int c_sr
     for (int s0 = 0; s0 < c_src; s0 += 128) {   // blocks of dW are disjoint: the workspace is reused, launches are ordered by the stream
       a.d0 = d0; a.cdn = c_dst - d0 < 128 ? c_dst - d0 : 128;
       a.s0 = s0; a.csn = c_src - s0 < 128 ? c_src - s0 : 128;
-      if (dtype == FV2P_DT_F16) { if (al) launch_wgrad<F16, true>(a, partial, chunks, stream); else launch_wgrad<F16, false>(a, partial, chunks, stream); }
-      else                      { if (al) launch_wgrad<BF16, true>(a, partial, chunks, stream); else launch_wgrad<BF16, false>(a, partial, chunks, stream); }
+      if (dtype == FV2P_DT_F16) { if (al) launch_wgrad<F16, true, F32>(a, partial, chunks, stream); else launch_wgrad<F16, false, F32>(a, partial, chunks, stream); }
+      else                      { if (al) launch_wgrad<BF16, true, F32>(a, partial, chunks, stream); else launch_wgrad<BF16, false, F32>(a, partial, chunks, stream); }
     }
   FV2P_LAUNCH_CHECK();
   return 0;
+}
+
+}  // namespace
+}  // namespace fv2p
+
+using namespace fv2p;
+
+extern "C" int fv2p_sparse_conv_rows_h(const void* src, int64_t n_src, int c_src, const void* weight, int kvol, const int* tab, int64_t n_dst,
+                                       int c_dst, int flip_k, int transpose_w, const void* bias, void* dst, int dtype, fv2p_stream_t stream) {
+  return conv_rows_entry<false>("sparse_conv_rows_h", src, n_src, c_src, weight, kvol, tab, n_dst, c_dst, flip_k, transpose_w, bias, dst, dtype, stream);
+}
+
+extern "C" int fv2p_sparse_conv_rows_hw32(const void* src, int64_t n_src, int c_src, const float* weight, int kvol, const int* tab, int64_t n_dst,
+                                          int c_dst, int flip_k, int transpose_w, const float* bias, void* dst, int dtype, fv2p_stream_t stream) {
+  return conv_rows_entry<true>("sparse_conv_rows_hw32", src, n_src, c_src, weight, kvol, tab, n_dst, c_dst, flip_k, transpose_w, bias, dst, dtype, stream);
+}
+
+extern "C" size_t fv2p_sparse_conv_wgrad_h_ws_bytes(int64_t n_dst, int c_src, int c_dst, int kvol) { return wgrad_ws_bytes(n_dst, c_src, c_dst, kvol); }
+
+extern "C" int fv2p_sparse_conv_wgrad_h(const void* src, int64_t n_src, int c_src, const void* grad, const int* tab, int64_t n_dst, int c_dst,
+                                        int kvol, int flip_k, void* dweight, int dtype, void* ws, size_t ws_bytes, fv2p_stream_t stream) {
+  return conv_wgrad_entry<false>("sparse_conv_wgrad_h", src, n_src, c_src, grad, tab, n_dst, c_dst, kvol, flip_k, dweight, dtype, ws, ws_bytes, stream);
+}
+
+extern "C" int fv2p_sparse_conv_wgrad_hw32(const void* src, int64_t n_src, int c_src, const void* grad, const int* tab, int64_t n_dst, int c_dst,
+                                           int kvol, int flip_k, float* dweight, int dtype, void* ws, size_t ws_bytes, fv2p_stream_t stream) {
+  return conv_wgrad_entry<true>("sparse_conv_wgrad_hw32", src, n_src, c_src, grad, tab, n_dst, c_dst, kvol, flip_k, dweight, dtype, ws, ws_bytes, stream);
 }

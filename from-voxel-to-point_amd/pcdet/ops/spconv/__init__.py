@@ -3,6 +3,7 @@ names, on the HIP kernels of libfv2p_ops.  Additions of this package sit at the 
 from . import conv as _conv
 from . import group as _group
 from . import modules as _modules
+from . import ops as _ops
 from . import pool as _pool
 from . import prefetch as _prefetch
 from . import structure as _structure
@@ -15,7 +16,8 @@ _REFERENCE_NAMES = {
     _structure: ("SparseConvTensor", "scatter_nd"),
     _group: ("SparseGroup3d", "SubMGroup3d"),
 }
-_OWN_NAMES = {_prefetch: ("rulebook_recipe", "build_rulebooks", "attach_rulebooks"), _conv: ("defer_weight_gradients", "conv_bn_fold", "materialise_pending", "set_bn_fold", "fold_enabled")}
+_OWN_NAMES = {_prefetch: ("rulebook_recipe", "build_rulebooks", "attach_rulebooks"), _conv: ("defer_weight_gradients", "conv_bn_fold", "materialise_pending", "set_bn_fold", "fold_enabled"),
+              _ops: ("set_mixed_precision", "mixed_precision")}
 
 __all__ = []
 for _table in (_REFERENCE_NAMES, _OWN_NAMES):

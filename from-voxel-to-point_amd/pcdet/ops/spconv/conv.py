@@ -91,6 +91,13 @@ class SparseConvolution(SparseModule):
         if weight is None or not torch.is_grad_enabled():
             weight = self.weight
         features = input.features
+        mixed = False
+        if ops.mixed_precision() and weight.dtype == torch.float32 and (self.bias is None or self.bias.dtype == torch.float32):
+            # mixed precision (ops.set_mixed_precision): fp32 master parameters beside 16-bit features.  A stack's first conv meets fp32
+            # features under autocast and casts them once, visibly to autograd; every conv after it already receives 16-bit rows
+            if features.dtype == torch.float32 and features.is_cuda and torch.is_autocast_enabled():
+                features = features.to(torch.get_autocast_dtype("cuda"))
+            mixed = ops.is_mixed(features, weight, self.bias)
         indices = input.indices
         spatial_shape = input.spatial_shape
         batch_size = input.batch_size
@@ -103,7 +110,8 @@ class SparseConvolution(SparseModule):
             out_spatial_shape = ops.get_conv_output_size(spatial_shape, self.kernel_size, self.stride, self.padding,
                                                          self.dilation)
         if self.conv1x1:  # reference conv.py:137-148: plain GEMM on the feature matrix
-            features = torch.mm(input.features, weight.view(self.in_channels, self.out_channels))
+            w2 = weight.view(self.in_channels, self.out_channels)
+            features = torch.mm(features, w2.to(features.dtype) if mixed else w2)
             if self.bias is not None:
                 features += self.bias
             out_tensor = SparseConvTensor(features, input.indices, input.spatial_shape, input.batch_size)
@@ -125,6 +133,13 @@ class SparseConvolution(SparseModule):
                 input.indice_dict[self.indice_key] = rb
             outids = rb.outids
         n_out = outids.shape[0]
+        if mixed:   # the bias goes through the kernel's epilogue: one rounding of the output
+            w16 = self._weight16(features.dtype) if ops.cached_copy_pays(self.in_channels, self.out_channels, self.bias) else None
+            out_features = Fsp.indice_mixed_conv(features, weight, self.bias, rb, n_out, self.inverse, self.subm, w16)
+            out_tensor = SparseConvTensor(out_features, outids, out_spatial_shape, batch_size)
+            out_tensor.indice_dict = input.indice_dict
+            out_tensor.grid = input.grid
+            return out_tensor
         if _post is not None and not self.fused_bn:
             fused = self._conv_bn_relu(features, rb, n_out, _post, weight)
             if fused is not None:
@@ -150,6 +165,20 @@ class SparseConvolution(SparseModule):
         out_tensor.indice_dict = input.indice_dict
         out_tensor.grid = input.grid
         return out_tensor
+
+
+def _weight16(self, dtype):
+    """The float32 master weight rounded to `dtype`, cast when the parameter has changed since the last call (its version counter moves
+    with every in-place update, i.e. once per optimiser step) - for the shapes of ops.cached_copy_pays.  Carries no gradient."""
+    w = self.weight
+    key = (w._version, w.data_ptr(), w.device, dtype)
+    ent = self.__dict__.get("_fv2p_w16")
+    if ent is None or ent[0] != key:
+        ent = self.__dict__["_fv2p_w16"] = (key, w.detach().to(dtype))
+    return ent[1]
+
+
+SparseConvolution._weight16 = _weight16
 
 
 def _conv_bn_relu(self, features, rb, n_out, post, weight=None):

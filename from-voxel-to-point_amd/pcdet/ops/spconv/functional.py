@@ -18,13 +18,14 @@ class _ConvBase(Function):
     def _fwd(cls, ctx, features, filters, indice_pairs, indice_pair_num, num_activate_out):
         ctx.rulebook = ops._rulebook_of(indice_pairs, indice_pair_num, features.shape[0], num_activate_out, cls.INVERSE)
         ctx.save_for_backward(features, filters)
+        ctx.mixed = ops.is_mixed(features, filters)   # decided here: backward runs outside any autocast region, maybe after the switch moved
         return ops.indice_conv(features, filters, ctx.rulebook, indice_pair_num, num_activate_out, cls.INVERSE, cls.SUBM)
 
     @classmethod
     def _bwd(cls, ctx, grad_output):
         features, filters = ctx.saved_tensors
         input_bp, filters_bp = ops.indice_conv_backward(features, filters, grad_output.contiguous(), ctx.rulebook, None,
-                                                        cls.INVERSE, cls.SUBM)
+                                                        cls.INVERSE, cls.SUBM, mixed=ctx.mixed)
         return input_bp, filters_bp, None, None, None
 
 
@@ -62,6 +63,36 @@ class SubMConvFunction(_ConvBase):
     @staticmethod
     def backward(ctx, grad_output):
         return SubMConvFunction._bwd(ctx, grad_output)
+
+
+class MixedConvFunction(Function):
+    """The conv modules' call in mixed precision (ops.set_mixed_precision): float16 / bfloat16 features, float32 filters and bias.
+    The bias goes through the kernel's epilogue, so the output is rounded once; d features has the features' dtype, d filters and
+    d bias are float32 (d bias: the float32 column sum of the 16-bit output gradient).  `filters16`: the module's cached copy of
+    `filters` in the features' dtype, or None (ops.cached_copy_pays): the two row convs then read it through the uniform 16-bit kernel -
+    the bits the `hw32` kernel gives - while the weight gradient stays on `hw32`."""
+
+    @staticmethod
+    def forward(ctx, features, filters, bias, rulebook, num_activate_out, inverse, subm, filters16=None):
+        if not ops.is_mixed(features, filters, bias):
+            raise TypeError("MixedConvFunction: float16 / bfloat16 features with float32 filters and bias, and set_mixed_precision(True)")
+        if filters16 is not None and (bias is not None or filters16.dtype != features.dtype or filters16.shape != filters.shape):
+            raise TypeError("MixedConvFunction: filters16 is the bias-free conv's filters in the features' dtype")
+        ctx.rulebook, ctx.inverse, ctx.subm = rulebook, bool(inverse), bool(subm)
+        ctx.save_for_backward(features, filters)
+        ctx.has_bias, ctx.filters16 = bias is not None, filters16
+        if filters16 is not None:
+            return ops.indice_conv(features, filters16, rulebook, None, num_activate_out, ctx.inverse, ctx.subm)
+        return ops.indice_conv(features, filters, rulebook, None, num_activate_out, ctx.inverse, ctx.subm, bias=bias)
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        features, filters = ctx.saved_tensors
+        g = grad_output.contiguous()
+        input_bp, filters_bp = ops.indice_conv_backward(features, filters, g, ctx.rulebook, None, ctx.inverse, ctx.subm, mixed=True,
+                                                        filters16=ctx.filters16)
+        bias_bp = g.sum(0, dtype=torch.float32) if (ctx.has_bias and ctx.needs_input_grad[2]) else None
+        return input_bp, filters_bp, bias_bp, None, None, None, None, None
 
 
 class SparseMaxPoolFunction(Function):
@@ -137,6 +168,7 @@ def _dispatch(fn_cls):
 indice_conv = _dispatch(SparseConvFunction)
 indice_inverse_conv = _dispatch(SparseInverseConvFunction)
 indice_subm_conv = _dispatch(SubMConvFunction)
+indice_mixed_conv = MixedConvFunction.apply
 indice_maxpool = SparseMaxPoolFunction.apply
 indice_group = SparseGroupFunction.apply
 indice_subm_group = SubMGroupFunction.apply

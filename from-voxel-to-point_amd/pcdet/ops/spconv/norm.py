@@ -6,7 +6,8 @@ torch modules to ``.features`` (pcdet/ops/spconv/modules.py:86-100).  ``batch_no
 ``SparseSequential`` calls for that pair instead: same parameters, same running-statistics update, same result within
 fp32 rounding, kernels in csrc/batchnorm.hip.  It returns None whenever the situation is not the plain one (hooks on
 the modules, autocast, CPU tensors, a single row in training mode ...) and the caller then runs the torch
-modules one by one, so error behaviour stays torch's.
+modules one by one, so error behaviour stays torch's.  (`spconv.set_mixed_precision(True)` lifts the autocast rule for the 16-bit
+route below, and for it alone.)
 
 float16 / bfloat16 features take a route of their own (`fusable16`, `_BatchNormReLU16`, kernels in csrc/batchnorm_h.hip): x, y and
 the gradients stay in 16 bits, the arithmetic is fp32 with one rounding at the store, and the module's parameters and buffers are
@@ -23,6 +24,8 @@ from torch import nn
 from torch.autograd import Function
 
 import fv2p_native as _nat
+
+from . import ops as _ops
 
 _ENABLED = os.environ.get("FV2P_FUSED_BN", "1") != "0"
 
@@ -161,7 +164,9 @@ def fusable16(bn, relu_module, x, channels):
         return False
     if not (torch.is_tensor(x) and x.is_cuda and x.dtype in _DT16 and x.dim() == 2 and x.is_contiguous()):
         return False
-    if torch.is_autocast_enabled() or channels != bn.num_features or x.shape[1] != channels:
+    if torch.is_autocast_enabled() and not _ops.mixed_precision():   # (mixed precision: 16-bit rows under autocast are this route's case)
+        return False
+    if channels != bn.num_features or x.shape[1] != channels:
         return False
     c = channels
     if c > 256 and c % 8 != 0 or c > 1024:

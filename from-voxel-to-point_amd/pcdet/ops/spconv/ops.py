@@ -383,8 +383,44 @@ def _conv_dtype(*tensors):
     return dt
 
 
-def _conv_rows(src, weight, table, flip, n_dst, c_dst, transpose_w, bias=None):
+_MIXED = False
+
+
+def set_mixed_precision(on):
+    """Process-wide opt-in (off by default) to the standard mixed-precision arrangement of the sparse convolution: float16 / bfloat16
+    features and gradients beside float32 master weights and bias, on the `hw32` kernels of csrc/sparse_conv_h.hip (the weights are
+    rounded on their way into LDS; d weight and d bias come back float32).  Under torch.autocast a conv module then casts float32
+    features to the autocast dtype, and the 16-bit BatchNorm route and the native dense() no longer step aside.  With it off a mix of
+    dtypes raises TypeError as before.  See INTEGRATION.md, "Dtypes of the sparse convolution"."""
+    global _MIXED
+    _MIXED = bool(on)
+
+
+def mixed_precision():
+    return _MIXED
+
+
+def is_mixed(features, weight, bias=None):
+    """16-bit features beside float32 weights (and bias), with the switch on: the call the `hw32` kernels take."""
+    return (_MIXED and features.dtype in _DT16 and weight.dtype == torch.float32 and (bias is None or bias.dtype == torch.float32))
+
+
+def _conv_rows(src, weight, table, flip, n_dst, c_dst, transpose_w, bias=None, mixed=None):
+    """`mixed`: None = as the switch and the dtypes say; True = the caller recorded a mixed call earlier (a backward pass)."""
     _nat.require_cuda(src, weight, table)
+    if mixed is None:
+        mixed = is_mixed(src, weight, bias)
+    if mixed:   # 16-bit rows, fp32 weight and bias: rounded inside the kernel, no 16-bit copy of the weights
+        if src.dtype not in _DT16 or weight.dtype != torch.float32 or (bias is not None and bias.dtype != torch.float32):
+            raise TypeError("sparse conv (mixed precision): float16 / bfloat16 rows with float32 weights and bias, got %s, %s, %s"
+                            % (src.dtype, weight.dtype, None if bias is None else bias.dtype))
+        src, w = src.contiguous(), weight.contiguous()
+        dst = torch.empty((n_dst, c_dst), dtype=src.dtype, device=src.device)
+        bias = bias.contiguous() if bias is not None else None
+        with _nat.device_guard(src.device):
+            _nat.call("fv2p_sparse_conv_rows_hw32", src, src.shape[0], src.shape[1], w, table.shape[0], table, n_dst, c_dst, int(flip),
+                      int(transpose_w), bias, dst, _DT16[src.dtype], _nat.stream())
+        return dst
     dt = _conv_dtype(src, weight, bias)
     src = src.contiguous()
     w = weight.contiguous()
@@ -402,7 +438,8 @@ def _conv_rows(src, weight, table, flip, n_dst, c_dst, transpose_w, bias=None):
 
 
 def indice_conv(features, filters, indice_pairs, indice_pair_num, num_activate_out, inverse=False, subm=False, bias=None):
-    """out[o] = sum_k feat[i] W_k over the rulebook (reference ops.py:108-126 -> spconv_ops.h:260-362)."""
+    """out[o] = sum_k feat[i] W_k over the rulebook (reference ops.py:108-126 -> spconv_ops.h:260-362).  16-bit features beside
+    float32 filters (and bias) run the `hw32` kernel when `set_mixed_precision(True)`, and raise TypeError otherwise."""
     rb = _rulebook_of(indice_pairs, indice_pair_num, features.shape[0], num_activate_out, inverse)
     cin, cout = filters.shape[-2], filters.shape[-1]
     w = filters.reshape(-1, cin, cout)
@@ -415,15 +452,44 @@ def fused_indice_conv(features, filters, bias, indice_pairs, indice_pair_num, nu
     return indice_conv(features, filters, indice_pairs, indice_pair_num, num_activate_out, inverse, subm, bias=bias)
 
 
-def indice_conv_backward(features, filters, out_bp, indice_pairs, indice_pair_num, inverse=False, subm=False):
-    """Returns [d_features, d_filters] (reference ops.py:142-157 -> spconv_ops.h:364-457)."""
+def cached_copy_pays(cin, cout, bias):
+    """Mixed precision: should a conv MODULE keep a 16-bit copy of its float32 weight (cast once per optimiser step) for the row
+    kernels instead of having `hw32` round it at every staging?  Measured (profiles/amp_conv.txt, plain VoxelBackBone8x, batch 4): on the
+    aligned staging forms - 16->16 up to 64->128 - `hw32` forward + backward data lose 3 - 16 us (float16) and 9 - 45 us (bfloat16) per
+    layer to casting the weight every call, let alone once per step, while its weight gradient is 1 - 3 us ahead; the element-wise form
+    (4->16) is level.  The bits are the same either way.  A bias rules the copy out: the 16-bit kernel would round it."""
+    return bias is None and cin % 8 == 0 and cout % 8 == 0
+
+
+def indice_conv_backward(features, filters, out_bp, indice_pairs, indice_pair_num, inverse=False, subm=False, mixed=None, filters16=None):
+    """Returns [d_features, d_filters] (reference ops.py:142-157 -> spconv_ops.h:364-457).  `mixed`: what the forward call was
+    (None: as the switch and the dtypes say now) - a mixed call returns d_features in the features' dtype and a float32 d_filters.
+    `filters16` (mixed calls): `filters` rounded to the features' dtype, which the backward-data conv then reads (same bits)."""
     rb = _rulebook_of(indice_pairs, indice_pair_num, features.shape[0], out_bp.shape[0], inverse)
     cin, cout = filters.shape[-2], filters.shape[-1]
-    dt = _conv_dtype(features, filters, out_bp)
+    if mixed is None:
+        mixed = is_mixed(features, filters)
+    if mixed and out_bp.dtype != features.dtype:
+        raise TypeError("sparse conv (mixed precision): the output gradient must have the features' dtype %s, got %s (nothing is cast here)"
+                        % (features.dtype, out_bp.dtype))
+    dt = features.dtype if mixed else _conv_dtype(features, filters, out_bp)
     feats, w, g = features.contiguous(), filters.reshape(-1, cin, cout).contiguous(), out_bp.contiguous()
     kvol = w.shape[0]
     # forward used table F (dst rows = outputs); its transpose-direction table B has dst rows = inputs
     (tab_f, flip_f), (tab_b, flip_b) = (rb.in_table(), rb.out_table(cout)) if inverse else (rb.out_table(), rb.in_table(cout))
+    if mixed:
+        if filters16 is not None:
+            din = _conv_rows(g, filters16.reshape(-1, cin, cout), tab_b, flip_b, features.shape[0], cin, True, mixed=False)
+        else:
+            din = _conv_rows(g, w, tab_b, flip_b, features.shape[0], cin, True, mixed=True)
+        if g.shape[0] == 0:
+            return [din, torch.zeros_like(filters)]
+        dw = torch.empty_like(w)   # float32: the sum of the chunk partials as it is
+        with _nat.device_guard(feats.device):
+            ws = _nat.workspace(_nat.lib().fv2p_sparse_conv_wgrad_h_ws_bytes(g.shape[0], cin, cout, kvol), feats.device)
+            _nat.call("fv2p_sparse_conv_wgrad_hw32", feats, feats.shape[0], cin, g, tab_f, g.shape[0], cout, kvol, int(flip_f), dw, _DT16[dt],
+                      ws, ws.numel(), _nat.stream())
+        return [din, dw.reshape(filters.shape)]
     if dt != torch.float32:
         din = _conv_rows(g, w, tab_b, flip_b, features.shape[0], cin, True)
         if g.shape[0] == 0:

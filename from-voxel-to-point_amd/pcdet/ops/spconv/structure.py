@@ -90,7 +90,9 @@ class SparseConvTensor(object):
     def dense(self, channels_first=True):
         ndim = len(self.spatial_shape)
         f = self.features
-        if f.is_cuda and (f.dtype == torch.float32 or f.dtype in _DT16) and f.dim() == 2 and ndim in (2, 3) and not torch.is_autocast_enabled():
+        from . import ops as _ops
+        native = not torch.is_autocast_enabled() or _ops.mixed_precision()   # (mixed precision: the rows under autocast are 16-bit already)
+        if f.is_cuda and (f.dtype == torch.float32 or f.dtype in _DT16) and f.dim() == 2 and ndim in (2, 3) and native:
             # one fill + one scatter straight into the requested layout (csrc/sparse_aux.hip), instead of
             # zeros -> index scatter -> permute -> contiguous over the whole dense volume
             return _Dense.apply(f, self.indices, tuple(int(v) for v in self.spatial_shape), int(self.batch_size), bool(channels_first))

@@ -326,6 +326,21 @@ size_t fv2p_sparse_conv_wgrad_h_ws_bytes(int64_t n_dst, int c_src, int c_dst, in
 int fv2p_sparse_conv_wgrad_h(const void* src, int64_t n_src, int c_src, const void* grad, const int* tab, int64_t n_dst,
                              int c_dst, int kvol, int flip_k, void* dweight, int dtype, void* ws, size_t ws_bytes,
                              fv2p_stream_t stream);
+/* The same two passes for fp32 MASTER weights beside 16-bit rows (mixed precision: pcdet.ops.spconv.set_mixed_precision).  `dtype`
+ * names the format of src / dst / grad only; the arguments, checks, coverage and summation orders are those of the entry points
+ * above, and there is no 16-bit copy of the weights in memory.
+ *   fv2p_sparse_conv_rows_hw32 : weight (same [K][c_src][c_dst] layout, [K][c_dst][c_src] with transpose_w = 1) and bias are fp32.
+ *     Every weight element is rounded to nearest even to `dtype` while its slice is staged into LDS; from there on the kernel is
+ *     that of fv2p_sparse_conv_rows_h, so with bias == NULL the result is bit for bit fv2p_sparse_conv_rows_h on weight rounded to
+ *     `dtype`.  The fp32 bias is added to the fp32 sum as it is (NOT rounded to 16 bits first); the sum is rounded once, at the store.
+ *   fv2p_sparse_conv_wgrad_hw32 : dweight [K][c_src][c_dst] is fp32: the sum of the chunk partials in ascending chunk order, without
+ *     the final rounding (rounding it to `dtype` gives the bits of fv2p_sparse_conv_wgrad_h).  Workspace: fv2p_sparse_conv_wgrad_h_ws_bytes. */
+int fv2p_sparse_conv_rows_hw32(const void* src, int64_t n_src, int c_src, const float* weight, int kvol, const int* tab,
+                               int64_t n_dst, int c_dst, int flip_k, int transpose_w, const float* bias, void* dst,
+                               int dtype, fv2p_stream_t stream);
+int fv2p_sparse_conv_wgrad_hw32(const void* src, int64_t n_src, int c_src, const void* grad, const int* tab, int64_t n_dst,
+                                int c_dst, int kvol, int flip_k, float* dweight, int dtype, void* ws, size_t ws_bytes,
+                                fv2p_stream_t stream);
 
 /* ---- A7: sparse max-pool / neighbour group over the same tables ------------------------------
  * Replace sparse_conv_ext.indice_maxpool_fp32(+backward) (all.cc:52-63 -> pool_ops.h:25-94; output starts

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Per-kernel timings on one GPU (events on the launch stream). Not part of the product or of bench.py; used to
-iterate on kernel variants:  python tools/microbench.py [conv|conv16|bn16|bn2d|exit16|dcn|fps|voxel|nms|all]"""
+iterate on kernel variants:  python tools/microbench.py [conv|conv16|amp16|bn16|bn2d|exit16|dcn|fps|voxel|nms|all]"""
 import os
 import sys
 import time
@@ -329,6 +329,112 @@ def conv16():
         name = f"{'subm' if mod.subm else 'conv'} {cin}->{cout} {mod.indice_key}"
         print(f"{name:30s} {f.shape[0]:6d} {n_out:6d} {p:8d} | {row[0]:8.1f} {row[1]:7.1f} {row[2]:7.1f} | {row[3]:12.1f} {row[4]:7.1f} |"
               f" {row[5]:8.1f} {row[6]:7.1f} {row[7]:7.1f} | {row[8]:8.1f} {row[9]:7.1f} {row[10]:7.1f}")
+
+
+def amp16(out_path=None):
+    """Mixed precision of the sparse conv (fp32 master weights beside 16-bit rows, csrc/sparse_conv_h.hip `hw32`), layer by layer at the
+    shapes `conv16` uses (plain VoxelBackBone8x, KITTI clouds, batch 4).  Per layer and 16-bit dtype, in us: forward, backward data (dX)
+    and weight gradient (dW, table-driven: backward minus dX, window by window) for
+      (a) fp32   : the fp32 kernels on fp32 tensors;
+      (b) 16     : the uniform 16-bit kernels on weights cast beforehand (outside the clock);
+      (c) cast+16: what autocast would otherwise do every step: weight.to(dt), then (b), then dW.float();
+      (d) hw32   : the `hw32` kernels on the fp32 weights (spconv.set_mixed_precision(True));
+      (e) copy   : what a conv module does where ops.cached_copy_pays says so: the row convs as (b), on a 16-bit copy cast once per
+                   optimiser step (outside the clock), the weight gradient as (d).
+    Each figure: the median of ROUNDS windows of REPS calls (events on the stream, after a warm-up), the routes taken alternately round by
+    round in one process; +- is half the range of the windows.  The last columns are (d) - (c) and (e) - (c) summed over fwd, dX and dW,
+    with the sum of the two routes' spreads.  The table also goes to `out_path` (profiles/amp_conv.txt holds it below the kernels'
+    resource table).  The routes call pcdet.ops.spconv.ops directly."""
+    from fv2p_harness import synth
+    from fv2p_harness.backbone import VoxelBackBone8x, mean_vfe
+    from pcdet.datasets.processor.voxel_generator import points_to_voxel_gpu
+    from pcdet.ops.spconv import ops
+    from pcdet.ops.spconv.conv import SparseConvolution
+    dev = torch.device("cuda:0")
+    ROUNDS, REPS = 7, 40
+    torch.manual_seed(0)
+    model = VoxelBackBone8x(4, [1408, 1600, 40]).to(dev)
+    feats, coords = [], []
+    for b in range(4):
+        v, c, n = points_to_voxel_gpu(torch.from_numpy(synth.lidar_cloud(b, 16384)).to(dev), synth.KITTI_VOXEL, synth.KITTI_RANGE, 5, True, 16000)
+        feats.append(mean_vfe(v, n))
+        coords.append(torch.nn.functional.pad(c, (1, 0), value=b))
+    recs = []
+
+    def hook(mod, inp, out):
+        if mod.indice_key is not None:
+            recs.append((mod, inp[0].features.detach(), inp[0].indice_dict[mod.indice_key], out.features.shape[0]))
+    hs = [m.register_forward_hook(hook) for m in model.modules() if isinstance(m, SparseConvolution)]
+    with torch.no_grad():
+        model(torch.cat(feats), torch.cat(coords), 4)
+    for h in hs:
+        h.remove()
+
+    def routes_of(mod, f, rb, n_out, dt):
+        cin, cout, subm = mod.in_channels, mod.out_channels, mod.subm
+        w = mod.weight.detach()
+        w3 = w.reshape(-1, cin, cout)
+        g = torch.randn((n_out, cout), device=dev)
+        tab_b, flip_b = rb.in_table(cout)
+        fd, gd, wd = f.to(dt), g.to(dt), w.to(dt)
+        w3d = wd.reshape(-1, cin, cout)
+
+        def c_all():
+            din, dw = ops.indice_conv_backward(fd, w.to(dt), gd, rb, None, False, subm)
+            return din, dw.float()
+        return [
+            ("fp32", lambda: ops.indice_conv(f, w, rb, None, n_out, False, subm), lambda: ops._conv_rows(g, w3, tab_b, flip_b, f.shape[0], cin, True),
+             lambda: ops.indice_conv_backward(f, w, g, rb, None, False, subm)),
+            ("16", lambda: ops.indice_conv(fd, wd, rb, None, n_out, False, subm), lambda: ops._conv_rows(gd, w3d, tab_b, flip_b, f.shape[0], cin, True),
+             lambda: ops.indice_conv_backward(fd, wd, gd, rb, None, False, subm)),
+            ("cast+16", lambda: ops.indice_conv(fd, w.to(dt), rb, None, n_out, False, subm),
+             lambda: ops._conv_rows(gd, w3.to(dt), tab_b, flip_b, f.shape[0], cin, True), c_all),
+            ("hw32", lambda: ops.indice_conv(fd, w, rb, None, n_out, False, subm), lambda: ops._conv_rows(gd, w3, tab_b, flip_b, f.shape[0], cin, True),
+             lambda: ops.indice_conv_backward(fd, w, gd, rb, None, False, subm)),
+            ("copy", lambda: ops.indice_conv(fd, wd, rb, None, n_out, False, subm), lambda: ops._conv_rows(gd, w3d, tab_b, flip_b, f.shape[0], cin, True),
+             lambda: ops.indice_conv_backward(fd, w, gd, rb, None, False, subm, filters16=wd)),
+        ]
+
+    med = lambda t: float(np.median(t))
+    spr = lambda t: (max(t) - min(t)) / 2
+    lines = ["sparse conv in mixed precision, us per call: median of %d windows of %d calls, +- half the range; fwd | dX | dW" % (ROUNDS, REPS),
+             "%-24s %6s %6s %-4s %-38s %-38s %-38s %-38s %-38s %-15s %s" % ("layer", "n_in", "n_out", "dt", "(a) fp32", "(b) 16-bit, weights pre-cast",
+                                                                         "(c) cast + 16-bit + dW.float()", "(d) hw32", "(e) cached copy, dW hw32", "(d) - (c)", "(e) - (c)")]
+    was = ops.mixed_precision()
+    ops.set_mixed_precision(True)
+    try:
+        seen = set()
+        for mod, f, rb, n_out in recs:
+            cin, cout = mod.in_channels, mod.out_channels
+            key = (mod.subm, cin, cout, f.shape[0], n_out)
+            if key in seen:
+                continue
+            seen.add(key)
+            pairs_saved, rb._wpairs = rb._wpairs, None     # table-driven weight gradient on every route
+            for dt, tag in ((torch.float16, "fp16"), (torch.bfloat16, "bf16")):
+                routes = [(name, fwd, dx, both, [], [], []) for name, fwd, dx, both in routes_of(mod, f, rb, n_out, dt)]
+                for _ in range(ROUNDS):
+                    for _, fwd, dx, both, tf, tx, tw in routes:
+                        tf.append(timeit(fwd, reps=REPS, warm=10))
+                        tx.append(timeit(dx, reps=REPS, warm=10))
+                        tw.append(timeit(both, reps=REPS, warm=10) - tx[-1])
+                cell = lambda tf, tx, tw: "%6.1f+-%4.1f |%6.1f+-%4.1f |%6.1f+-%4.1f" % (med(tf), spr(tf), med(tx), spr(tx), med(tw), spr(tw))
+                tot = lambda r: med(r[4]) + med(r[5]) + med(r[6])
+                sp = lambda r: spr(r[4]) + spr(r[5]) + spr(r[6])
+                name = "%s %d->%d %s" % ("subm" if mod.subm else "conv", cin, cout, mod.indice_key)
+                lines.append("%-24s %6d %6d %-4s " % (name, f.shape[0], n_out, tag) + " ".join("%-38s" % cell(*r[4:]) for r in routes)
+                             + " %+7.1f +-%5.1f" % (tot(routes[3]) - tot(routes[2]), sp(routes[3]) + sp(routes[2]))
+                             + " %+7.1f +-%5.1f" % (tot(routes[4]) - tot(routes[2]), sp(routes[4]) + sp(routes[2])))
+                print(lines[-1], flush=True)
+            rb._wpairs = pairs_saved
+    finally:
+        ops.set_mixed_precision(was)
+    text = "\n".join(lines) + "\n"
+    print(text)
+    if out_path:
+        os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+        with open(out_path, "w") as fh:
+            fh.write(text)
 
 
 def bn16(out_path=None):
@@ -899,6 +1005,9 @@ if __name__ == "__main__":
         sys.exit(0)
     if which == "bn16" and len(sys.argv) > 2:   # python tools/microbench.py bn16 profiles/bn_half.txt
         bn16(sys.argv[2])
+        sys.exit(0)
+    if which == "amp16":   # python tools/microbench.py amp16 [profiles/amp_conv.txt]
+        amp16(sys.argv[2] if len(sys.argv) > 2 else None)
         sys.exit(0)
     if which == "bn2d":   # python tools/microbench.py bn2d [profiles/bn2d.txt]
         bn2d(sys.argv[2] if len(sys.argv) > 2 else None)
