@@ -56,22 +56,19 @@ __global__ __launch_bounds__(256) void points_in_boxes_k(int boxes_num, int pts_
 // ---- RoI point pooling: one workgroup of 16 waves per (sample, box) -----------------------------------
 // (16 waves: at 384 boxes a 4-wave workgroup per box left six waves on a CU, and both phases wait on memory)
 constexpr int kRoiPoolWaves = 16;
-__global__ __launch_bounds__(kRoiPoolWaves * 64) void roipoint_pool_k(int pts_num, int boxes_num, int feat_len, int sampled, const float* __restrict__ xyz,
-                                                       const float* __restrict__ boxes3d, const float* __restrict__ feats,
-                                                       float* __restrict__ pooled, int* __restrict__ empty_flag) {
-  extern __shared__ int sidx[];  // [sampled]
-  __shared__ int wave_cnt[kRoiPoolWaves];
+// The selection both pool kernels share: the first `sampled` points of sample b inside `box`, in index order, into sidx[]; the box's
+// empty flag; zeros over its `sampled * row` outputs when it is empty.  Returns the number of selected points (0: nothing left to do).
+// Called by all threads of the workgroup (it synchronises).
+__device__ __forceinline__ int roi_pool_select(int pts_num, int sampled, int row, const float* __restrict__ xyz_b, const float* box, int* sidx,
+                                               int* wave_cnt, float* __restrict__ dst, int* __restrict__ empty_flag) {
   constexpr int T = kRoiPoolWaves * 64;
-  const int m = blockIdx.x, b = blockIdx.y;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  float box[7];
-  for (int j = 0; j < 7; ++j) box[j] = boxes3d[(static_cast<int64_t>(b) * boxes_num + m) * 7 + j];
   int total = 0;
   for (int base = 0; base < pts_num && total < sampled; base += T) {
     const int i = base + threadIdx.x;
     int in = 0;
     if (i < pts_num) {
-      const float* p = xyz + (static_cast<int64_t>(b) * pts_num + i) * 3;
+      const float* p = xyz_b + static_cast<int64_t>(i) * 3;
       const float pt[3] = {p[0], p[1], p[2]};
       float lx, ly;
       in = pt_in_box3d(pt, box, kMarginGpu, &lx, &ly);
@@ -87,13 +84,26 @@ __global__ __launch_bounds__(kRoiPoolWaves * 64) void roipoint_pool_k(int pts_nu
     __syncthreads();
   }
   const int cnt = total < sampled ? total : sampled;
-  if (threadIdx.x == 0) empty_flag[static_cast<int64_t>(b) * boxes_num + m] = (cnt == 0) ? 1 : 0;
+  if (threadIdx.x == 0) *empty_flag = (cnt == 0) ? 1 : 0;
+  if (cnt == 0)   // an empty box pools zeros (the reference pre-zeroes the whole output, roipoint_pool3d_utils.py:54; here only these rows)
+    for (int e = threadIdx.x; e < sampled * row; e += T) dst[e] = 0.f;
+  return cnt;
+}
+
+__global__ __launch_bounds__(kRoiPoolWaves * 64) void roipoint_pool_k(int pts_num, int boxes_num, int feat_len, int sampled, const float* __restrict__ xyz,
+                                                       const float* __restrict__ boxes3d, const float* __restrict__ feats,
+                                                       float* __restrict__ pooled, int* __restrict__ empty_flag) {
+  extern __shared__ int sidx[];  // [sampled]
+  __shared__ int wave_cnt[kRoiPoolWaves];
+  const int m = blockIdx.x, b = blockIdx.y;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  float box[7];
+  for (int j = 0; j < 7; ++j) box[j] = boxes3d[(static_cast<int64_t>(b) * boxes_num + m) * 7 + j];
   const int row = 3 + feat_len;
   float* dst = pooled + (static_cast<int64_t>(b) * boxes_num + m) * sampled * row;
-  if (cnt == 0) {   // an empty box pools zeros (the reference pre-zeroes the whole output, roipoint_pool3d_utils.py:54; here only these rows)
-    for (int e = threadIdx.x; e < sampled * row; e += T) dst[e] = 0.f;
-    return;
-  }
+  const int cnt = roi_pool_select(pts_num, sampled, row, xyz + static_cast<int64_t>(b) * pts_num * 3, box, sidx, wave_cnt, dst,
+                                  empty_flag + static_cast<int64_t>(b) * boxes_num + m);
+  if (cnt == 0) return;
   // wrap-around duplication (roipoint_pool3d_kernel.cu:90-98): slot k takes slot k % cnt.  A wave copies four slots at a time, a lane the
   // elements lane, lane + 64, ... of each row: the loads of the four rows are independent (one slot per iteration and thread-flat indexing,
   // the first form, left every 4-byte load waiting for the one before it: 170 us at 384 boxes x 512 slots x 133 floats).
@@ -111,6 +121,66 @@ __global__ __launch_bounds__(kRoiPoolWaves * 64) void roipoint_pool_k(int pts_nu
         for (int q = 0; q < 2; ++q) {
           const int j = j0 + 64 * q + lane;
           v[u][q] = j < 3 ? fx[static_cast<int64_t>(src[u]) * 3 + j] : (j < row ? ff[static_cast<int64_t>(src[u]) * feat_len + (j - 3)] : 0.f);
+        }
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+          const int j = j0 + 64 * q + lane;
+          if (j < row && s0 + u < sampled) dst[static_cast<int64_t>(s0 + u) * row + j] = v[u][q];
+        }
+    }
+  }
+}
+
+// ---- RoI point pooling with the rows written in the RoI's frame -----------------------------------------
+// IoUGuidedRoIHead.roipool3d_gpu (iouguided_roi_head.py:144-195) around the pool: the reference concatenates [score, depth, features]
+// per point, pools, and then subtracts the RoI centre, rotates by -ry and re-zeroes the empty boxes in passes over the pooled
+// (B, M, S, 3 + 2 + C) tensor.  Here the same selection (first S points inside the ENLARGED box in index order, wrapped when fewer)
+// writes rows [x', y', z', score, depth, features...] directly: (x', y', z') = the point minus the centre of the ORIGINAL roi
+// rotated by -ry, depth = |p| / depth_norm - 0.5.  Nothing is concatenated and the pooled tensor is written once.
+__global__ __launch_bounds__(kRoiPoolWaves * 64) void roipoint_pool_frame_k(int pts_num, int boxes_num, int feat_len, int sampled, float depth_norm,
+                                                       const float* __restrict__ xyz, const float* __restrict__ score,
+                                                       const float* __restrict__ feats, const float* __restrict__ boxes_big,
+                                                       const float* __restrict__ rois, float* __restrict__ pooled, int* __restrict__ empty_flag) {
+  extern __shared__ int sidx[];  // [sampled]
+  __shared__ int wave_cnt[kRoiPoolWaves];
+  const int m = blockIdx.x, b = blockIdx.y;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  float box[7], roi[7];
+  for (int j = 0; j < 7; ++j) {
+    box[j] = boxes_big[(static_cast<int64_t>(b) * boxes_num + m) * 7 + j];
+    roi[j] = rois[(static_cast<int64_t>(b) * boxes_num + m) * 7 + j];
+  }
+  const int row = 5 + feat_len;
+  float* dst = pooled + (static_cast<int64_t>(b) * boxes_num + m) * sampled * row;
+  const float* fx = xyz + static_cast<int64_t>(b) * pts_num * 3;
+  const int cnt = roi_pool_select(pts_num, sampled, row, fx, box, sidx, wave_cnt, dst, empty_flag + static_cast<int64_t>(b) * boxes_num + m);
+  if (cnt == 0) return;
+  const float ca = cosf(-roi[6]), sa = sinf(-roi[6]);
+  const float* fs = score + static_cast<int64_t>(b) * pts_num;
+  const float* ff = feats + static_cast<int64_t>(b) * pts_num * feat_len;
+  for (int s0 = 4 * w; s0 < sampled; s0 += 4 * kRoiPoolWaves) {
+    int src[4];
+    float head[4];   // this lane's value among the five leading ones of each slot's row (lanes 0 .. 4)
+#pragma unroll
+    for (int u = 0; u < 4; ++u) { const int sl = s0 + u < sampled ? s0 + u : sampled - 1; src[u] = sidx[sl < cnt ? sl : sl % cnt]; }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {   // every lane reads the slot's point and score (one address per wave) and keeps the value of its column
+      const float* p = fx + static_cast<int64_t>(src[u]) * 3;
+      const float x = p[0], y = p[1], z = p[2], sc = fs[src[u]];
+      const float dx = x - roi[0], dy = y - roi[1];
+      head[u] = lane == 0 ? dx * ca - dy * sa : (lane == 1 ? dx * sa + dy * ca : (lane == 2 ? z - roi[2] : (lane == 3 ? sc : sqrtf(x * x + y * y + z * z) / depth_norm - 0.5f)));
+    }
+    for (int j0 = 0; j0 < row; j0 += 128) {
+      float v[4][2];
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+          const int j = j0 + 64 * q + lane;
+          const float f = (j >= 5 && j < row) ? ff[static_cast<int64_t>(src[u]) * feat_len + (j - 5)] : 0.f;
+          v[u][q] = j < 5 ? head[u] : f;
         }
 #pragma unroll
       for (int u = 0; u < 4; ++u)
@@ -289,6 +359,25 @@ extern "C" int fv2p_roipoint_pool3d(const float* xyz, const float* boxes3d, cons
   FV2P_REQUIRE(static_cast<size_t>(sampled_pts_num) * 4 <= 60000, FV2P_ELIMIT, "roipoint_pool3d: sampled_pts_num > 15000");
   hipLaunchKernelGGL(roipoint_pool_k, dim3(boxes_num, batch), dim3(kRoiPoolWaves * 64), sampled_pts_num * sizeof(int), stream, pts_num, boxes_num,
                      feature_len, sampled_pts_num, xyz, boxes3d, pts_feature, pooled_features, pooled_empty_flag);
+  FV2P_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int fv2p_roipoint_pool3d_frame(const float* xyz, const float* pts_score, const float* pts_feature, const float* boxes3d,
+                                          const float* rois, int batch, int pts_num, int boxes_num, int feature_len, int sampled_pts_num,
+                                          float depth_normalizer, float* pooled_features, int* pooled_empty_flag, fv2p_stream_t stream_) {
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  FV2P_REQUIRE(batch >= 0 && pts_num >= 0 && boxes_num >= 0 && feature_len >= 0 && sampled_pts_num >= 1, FV2P_EINVAL,
+               "roipoint_pool3d_frame: bad sizes");
+  FV2P_REQUIRE(depth_normalizer > 0.f, FV2P_EINVAL, "roipoint_pool3d_frame: depth_normalizer must be positive");
+  if (batch == 0 || boxes_num == 0) return 0;
+  FV2P_REQUIRE(boxes3d && rois && pooled_features && pooled_empty_flag && ((xyz && pts_score) || pts_num == 0) &&
+               (pts_feature || feature_len == 0 || pts_num == 0), FV2P_EINVAL, "roipoint_pool3d_frame: null pointer");
+  FV2P_REQUIRE(static_cast<size_t>(sampled_pts_num) * 4 <= 60000, FV2P_ELIMIT, "roipoint_pool3d_frame: sampled_pts_num > 15000");
+  FV2P_REQUIRE(static_cast<int64_t>(sampled_pts_num) * (5 + feature_len) < (1ll << 31), FV2P_ELIMIT, "roipoint_pool3d_frame: a RoI's rows exceed 2^31 values");
+  hipLaunchKernelGGL(roipoint_pool_frame_k, dim3(boxes_num, batch), dim3(kRoiPoolWaves * 64), sampled_pts_num * sizeof(int), stream, pts_num,
+                     boxes_num, feature_len, sampled_pts_num, depth_normalizer, xyz, pts_score, pts_feature, boxes3d, rois, pooled_features,
+                     pooled_empty_flag);
   FV2P_LAUNCH_CHECK();
   return 0;
 }

@@ -358,3 +358,329 @@ extern "C" int fv2p_anchor_loss(const float* cls, const float* box, const float*
   FV2P_LAUNCH_CHECK();
   return 0;
 }
+
+// ---- second-stage losses in one pass ------------------------------------------------------------------------------------------------
+// RoIWithIoUHeadTemplate.get_box_cls_layer_loss / get_box_reg_layer_loss / get_box_iouscore_layer_loss
+// (pcdet/models/roi_heads/roi_withiou_head_template.py:133-265, CLS_SCORE_TYPE roi_iou) with the canonical targets of assign_targets
+// (:103-135) formed in place: the harness states the same in ~135 torch ops (IoUGuidedRoIHead.losses / reg_losses / canonical_targets,
+// corner_loss_lidar) and autograd in ~120 more.  One workgroup walks the R sampled RoIs (R is a few hundred): it counts the two
+// normalisers, then every thread forms its rows' four loss terms and the gradients with respect to the class logit and the
+// [iou, 7 residuals] row; the sums are taken in double in a fixed order (thread-strided rows, wave butterflies, waves in order).
+// Every float expression follows the tensor formulation, its corner cases included: the BCE logs clamped at -100 and its gradient
+// through max(p (1 - p), 1e-12) (0 once the sigmoid saturates), `n < beta` strictly in both smooth-L1s, sgn(0) = 0, the norm of a
+// zero corner offset with gradient 0, the first operand of torch.minimum on a tie.
+namespace fv2p {
+
+constexpr int kRoiLossThreads = 512;
+
+struct RoiLossArgs {
+  int r, gt_w;
+  const float *rois, *gt, *iou, *cls, *reg;   // (R,7) (R,gt_w) (R) (R) (R,8)
+  float cls_fg, cls_bg, soft_span, reg_fg, lab_thr, beta;
+  float *loss5, *dcls, *dreg, *canonical;   // canonical (R,7) or null
+};
+
+__device__ __forceinline__ float py_mod(float a, float b) {   // torch.remainder for b > 0
+  float m = fmodf(a, b);
+  if (m != 0.f && m < 0.f) m += b;
+  return m;
+}
+__device__ __forceinline__ float sgnf(float d) { return d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f); }
+
+__global__ __launch_bounds__(kRoiLossThreads) void roi_loss_k(RoiLossArgs p) {
+  constexpr int W = kRoiLossThreads / 64;
+  __shared__ int s_cnt[2];
+  __shared__ double s_red[4][W];
+  const int tid = threadIdx.x;
+  if (tid < 2) s_cnt[tid] = 0;
+  __syncthreads();
+  {   // normalisers: rois above REG_FG_THRESH, and rois whose renormalised IoU label reaches the same threshold
+    int c_fg = 0, c_val = 0;
+    for (int i = tid; i < p.r; i += kRoiLossThreads) {
+      const float iou = p.iou[i];
+      c_fg += iou > p.reg_fg ? 1 : 0;
+      c_val += (iou - 0.5f) * 2.f >= p.lab_thr ? 1 : 0;
+    }
+    if (c_fg) atomicAdd(&s_cnt[0], c_fg);      // integer sums: the order does not matter
+    if (c_val) atomicAdd(&s_cnt[1], c_val);
+  }
+  __syncthreads();
+  const float n_fg = fmaxf(static_cast<float>(s_cnt[0]), 1.f), n_val = fmaxf(static_cast<float>(s_cnt[1]), 1.f);
+  const float inv_r = 1.f / static_cast<float>(p.r);
+  const float two_pi = 6.283185307179586f, pi = 3.141592653589793f, half_pi = 1.5707963267948966f, three_half_pi = 4.71238898038469f;
+  double acc[4] = {0.0, 0.0, 0.0, 0.0};   // cls, reg, corner, iou
+  for (int i = tid; i < p.r; i += kRoiLossThreads) {
+    const float* roi = p.rois + static_cast<long long>(i) * 7;
+    const float* gt = p.gt + static_cast<long long>(i) * p.gt_w;
+    const float* rg = p.reg + static_cast<long long>(i) * 8;
+    const float iou = p.iou[i];
+    // -- class score: BCE of the sigmoid against the IoU-derived soft label, mean over all rois
+    float soft = fminf(fmaxf((iou - p.cls_bg) / p.soft_span, 0.f), 1.f);
+    soft = iou > p.cls_fg ? 1.f : (iou < p.cls_bg ? 0.f : soft);
+    const float x = p.cls[i];
+    const float pr = 1.f / (1.f + expf(-x));
+    const float l_cls = (soft - 1.f) * fmaxf(log1pf(-pr), -100.f) - soft * fmaxf(logf(pr), -100.f);
+    acc[0] += static_cast<double>(l_cls);
+    const float g_p = inv_r * (pr - soft) / fmaxf((1.f - pr) * pr, 1e-12f);
+    p.dcls[i] = g_p * (1.f - pr) * pr;
+    // -- IoU score: smooth-L1 (beta 1) against (iou - 0.5) * 2 on the rois whose label reaches the threshold
+    float dr[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    {
+      const float lab = (iou - 0.5f) * 2.f;
+      if (lab >= p.lab_thr) {
+        const float d = rg[0] - lab, n = fabsf(d);
+        acc[3] += static_cast<double>(n < 1.f ? 0.5f * d * d : n - 0.5f);
+        dr[0] = (n < 1.f ? d : sgnf(d)) / n_val;
+      }
+    }
+    const bool fg = iou > p.reg_fg;
+    float tx = 0.f, ty = 0.f, cz = 0.f, h = 0.f;
+    if (fg || p.canonical) {
+      // canonical target: gt in the roi's frame, heading folded to [-pi/2, pi/2] (assign_targets)
+      const float ry = py_mod(roi[6], two_pi);
+      const float cx = gt[0] - roi[0], cy = gt[1] - roi[1];
+      cz = gt[2] - roi[2];
+      const float cn = cosf(-ry), sn = sinf(-ry);
+      tx = cx * cn - cy * sn;
+      ty = cx * sn + cy * cn;
+      h = py_mod(gt[6] - ry, two_pi);
+      if (h > half_pi && h < three_half_pi) h = py_mod(h + pi, two_pi);
+      if (h > pi) h -= two_pi;
+      h = fminf(fmaxf(h, -half_pi), half_pi);
+      if (p.canonical) {
+        float* o = p.canonical + static_cast<long long>(i) * 7;
+        o[0] = tx; o[1] = ty; o[2] = cz; o[3] = gt[3]; o[4] = gt[4]; o[5] = gt[5]; o[6] = h;
+      }
+    }
+    if (fg) {
+      const float w = 1.f / n_fg;
+      // ResidualCoder target against the size-only anchor (0, 0, 0, dx, dy, dz, 0)
+      const float a0 = fmaxf(roi[3], 1e-5f), a1 = fmaxf(roi[4], 1e-5f), a2 = fmaxf(roi[5], 1e-5f);
+      const float diag_c = sqrtf(a0 * a0 + a1 * a1);
+      float t[7];
+      t[0] = tx / diag_c;
+      t[1] = ty / diag_c;
+      t[2] = cz / a2;
+      t[3] = logf(fmaxf(gt[3], 1e-5f) / a0);
+      t[4] = logf(fmaxf(gt[4], 1e-5f) / a1);
+      t[5] = logf(fmaxf(gt[5], 1e-5f) / a2);
+      t[6] = h;
+      float l_reg = 0.f;
+#pragma unroll
+      for (int j = 0; j < 7; ++j) {
+        const float d = rg[1 + j] - t[j], n = fabsf(d);
+        l_reg += n < p.beta ? 0.5f * n * n / p.beta : n - 0.5f * p.beta;
+        dr[1 + j] = (n < p.beta ? d / p.beta : sgnf(d)) * w;
+      }
+      acc[1] += static_cast<double>(l_reg);
+      // corner regularisation: the residuals decoded against the roi (ResidualCoder.decode_torch, sizes unclamped) into the LiDAR
+      // frame, its eight corners against those of the gt box or of its heading-flipped twin, whichever is nearer
+      const float s0 = roi[3], s1 = roi[4], s2 = roi[5];
+      const float diag = sqrtf(s0 * s0 + s1 * s1);
+      const float lx = rg[1] * diag, ly = rg[2] * diag, lz = rg[3] * s2;
+      const float px = expf(rg[4]) * s0, py = expf(rg[5]) * s1, pz = expf(rg[6]) * s2;
+      const float cr = cosf(roi[6]), sr = sinf(roi[6]);
+      const float bx = (lx * cr - ly * sr) + roi[0], by = (lx * sr + ly * cr) + roi[1], bz = lz + roi[2];
+      const float th = rg[7] + roi[6];
+      const float ct = cosf(th), st = sinf(th);
+      const float cg = cosf(gt[6]), sg = sinf(gt[6]);
+      const float gfh = gt[6] + pi;
+      const float cf = cosf(gfh), sf = sinf(gfh);
+      float vx = 0.f, vy = 0.f, vz = 0.f, d_sx = 0.f, d_sy = 0.f, d_sz = 0.f, d_th = 0.f, l_cor = 0.f;
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        // box_utils.boxes_to_corners_3d sign table
+        const float qx = (k == 0 || k == 1 || k == 4 || k == 5) ? 0.5f : -0.5f;
+        const float qy = (k == 0 || k == 3 || k == 4 || k == 7) ? 0.5f : -0.5f;
+        const float qz = k >= 4 ? 0.5f : -0.5f;
+        const float ox = px * qx, oy = py * qy, oz = pz * qz;
+        const float rx = ox * ct - oy * st, ryy = ox * st + oy * ct;         // rotated corner offset of the predicted box
+        const float pcx = rx + bx, pcy = ryy + by, pcz = oz + bz;
+        const float gx = gt[3] * qx, gy = gt[4] * qy, gz = gt[5] * qz + gt[2];
+        const float e1x = pcx - ((gx * cg - gy * sg) + gt[0]), e1y = pcy - ((gx * sg + gy * cg) + gt[1]), ez = pcz - gz;
+        const float e2x = pcx - ((gx * cf - gy * sf) + gt[0]), e2y = pcy - ((gx * sf + gy * cf) + gt[1]);
+        const float n1 = sqrtf(e1x * e1x + e1y * e1y + ez * ez), n2 = sqrtf(e2x * e2x + e2y * e2y + ez * ez);
+        const bool first = n1 <= n2;
+        const float dist = first ? n1 : n2, ex = first ? e1x : e2x, ey = first ? e1y : e2y;
+        l_cor += dist < 1.f ? 0.5f * dist * dist : dist - 0.5f;
+        // d smooth-L1 / d dist = dist or 1; d dist / d corner = offset / dist (0 at dist == 0)
+        const float sc = dist < 1.f ? 1.f : (dist > 0.f ? 1.f / dist : 0.f);
+        const float ux = ex * sc, uy = ey * sc, uz = ez * sc;
+        vx += ux; vy += uy; vz += uz;
+        d_sx += qx * (ux * ct + uy * st);
+        d_sy += qy * (uy * ct - ux * st);
+        d_sz += qz * uz;
+        d_th += uy * rx - ux * ryy;
+      }
+      acc[2] += static_cast<double>(l_cor * 0.125f);
+      const float wc = w * 0.125f;
+      dr[1] += (vx * cr + vy * sr) * diag * wc;
+      dr[2] += (vy * cr - vx * sr) * diag * wc;
+      dr[3] += vz * s2 * wc;
+      dr[4] += d_sx * px * wc;
+      dr[5] += d_sy * py * wc;
+      dr[6] += d_sz * pz * wc;
+      dr[7] += d_th * wc;
+    }
+    float* o = p.dreg + static_cast<long long>(i) * 8;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) o[j] = dr[j];
+  }
+  const int lane = tid & 63, wv = tid >> 6;
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    double v = acc[c];
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
+    if (lane == 0) s_red[c][wv] = v;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    double s[4];
+    for (int c = 0; c < 4; ++c) {
+      double v = 0.0;
+      for (int k = 0; k < W; ++k) v += s_red[c][k];
+      s[c] = v;
+    }
+    const float l_cls = static_cast<float>(s[0] / p.r), l_reg = static_cast<float>(s[1] / n_fg);
+    const float l_cor = static_cast<float>(s[2] / n_fg), l_iou = static_cast<float>(s[3] / n_val);
+    p.loss5[0] = l_cls + l_reg + l_cor + l_iou;
+    p.loss5[1] = l_cls;
+    p.loss5[2] = l_reg;
+    p.loss5[3] = l_cor;
+    p.loss5[4] = l_iou;
+  }
+}
+
+// ---- point-head loss ----------------------------------------------------------------------------------------------------------------
+// PointHeadSimple's foreground loss (point_head_template.py:47-142): sigmoid focal loss (alpha 0.25, gamma 2) of one logit per point
+// against labels in {-1 ignored, 0, 1}, every counted point weighted by 1 / max(#positive, 1); the score sigmoid(logit) the RoI head
+// pools comes out of the same pass.  Same three launches as the first-stage loss: positive count, loss + gradient, ordered reduce.
+__global__ __launch_bounds__(256) void point_pos_count_k(int n, const int64_t* __restrict__ labels, int* __restrict__ pos) {
+  const int a = blockIdx.x * blockDim.x + threadIdx.x;
+  const bool t = a < n && labels[a] > 0;
+  const int c = __popcll(__ballot(t));
+  if ((threadIdx.x & 63) == 0 && c) atomicAdd(pos, c);
+}
+
+__global__ __launch_bounds__(256) void point_loss_k(int n, const float* __restrict__ logits, const int64_t* __restrict__ labels,
+                                                    const int* __restrict__ pos, float alpha, float weight, float* __restrict__ dlogits,
+                                                    float* __restrict__ score, double* __restrict__ partial) {
+  const int a = blockIdx.x * blockDim.x + threadIdx.x;
+  const float norm = fmaxf(static_cast<float>(*pos), 1.f);
+  double l = 0.0;
+  if (a < n) {
+    const int64_t label = labels[a];
+    const bool t = label > 0;
+    const float x = logits[a];
+    const float w = (label == 0 || t) ? 1.f / norm : 0.f;
+    const float pr = 1.f / (1.f + expf(-x));
+    const float aw = t ? alpha : 1.f - alpha;
+    const float pt = t ? 1.f - pr : pr;
+    const float bce = fmaxf(x, 0.f) - (t ? x : 0.f) + log1pf(expf(-fabsf(x)));
+    l = static_cast<double>(aw * pt * pt * bce * w);
+    const float dpt = t ? -pr * (1.f - pr) : pr * (1.f - pr);
+    dlogits[a] = aw * w * (2.f * pt * dpt * bce + pt * pt * (pr - (t ? 1.f : 0.f))) * weight;
+    score[a] = pr;
+  }
+  __shared__ double s_red[4];
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) l += __shfl_xor(l, d, 64);
+  if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = l;
+  __syncthreads();
+  if (threadIdx.x == 0) partial[blockIdx.x] = s_red[0] + s_red[1] + s_red[2] + s_red[3];
+}
+
+__global__ __launch_bounds__(256) void point_loss_reduce_k(int rows, const double* __restrict__ partial, float weight, float* __restrict__ loss) {
+  __shared__ double s[256];
+  double acc = 0.0;
+  for (int r = threadIdx.x; r < rows; r += 256) acc += partial[r];
+  s[threadIdx.x] = acc;
+  __syncthreads();
+  for (int d = 128; d >= 1; d >>= 1) {
+    if (threadIdx.x < d) s[threadIdx.x] += s[threadIdx.x + d];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) loss[0] = static_cast<float>(s[0] * weight);
+}
+
+// ---- RoI grid geometry ----------------------------------------------------------------------------------------------------------------
+// get_dense_grid_points / get_global_grid_points_of_roi (iouguided_roi_head.py:195-220) and the corner-geometry input
+// (feature_adaptor/nn_modules.py:6-60) of every sampled RoI in one launch: local (R, g^3, 3) grid points in the roi's frame (x
+// slowest), column (R, g^2, 3) = the world position of the z = 0 grid point of every (x, y) column (the rotation is about z, so a
+// column shares its BEV position), corners (R, 8, 3) = the half extents with the corner sign table.
+__global__ __launch_bounds__(256) void roi_grid_k(int g, const float* __restrict__ rois, float* __restrict__ local, float* __restrict__ column,
+                                                  float* __restrict__ corners) {
+  const int r = blockIdx.x;
+  const float* roi = rois + static_cast<long long>(r) * 7;
+  const float sx = roi[3], sy = roi[4], sz = roi[5];
+  const float c = cosf(roi[6]), s = sinf(roi[6]);
+  const int g2 = g * g, g3 = g2 * g;
+  const float gf = static_cast<float>(g);
+  for (int e = threadIdx.x; e < g3; e += blockDim.x) {
+    const int ix = e / g2, iy = (e / g) % g, iz = e % g;
+    const float x = (static_cast<float>(ix) + 0.5f) / gf * sx - sx / 2.f;
+    const float y = (static_cast<float>(iy) + 0.5f) / gf * sy - sy / 2.f;
+    const float z = (static_cast<float>(iz) + 0.5f) / gf * sz - sz / 2.f;
+    float* o = local + (static_cast<long long>(r) * g3 + e) * 3;
+    o[0] = x; o[1] = y; o[2] = z;
+    if (iz == 0) {
+      float* w = column + (static_cast<long long>(r) * g2 + e / g) * 3;
+      w[0] = (x * c - y * s) + roi[0];
+      w[1] = (x * s + y * c) + roi[1];
+      w[2] = z + roi[2];
+    }
+  }
+  if (threadIdx.x < 8) {
+    const int k = threadIdx.x;
+    float* o = corners + (static_cast<long long>(r) * 8 + k) * 3;
+    o[0] = sx * ((k == 0 || k == 1 || k == 4 || k == 5) ? 0.5f : -0.5f);
+    o[1] = sy * ((k == 0 || k == 3 || k == 4 || k == 7) ? 0.5f : -0.5f);
+    o[2] = sz * (k >= 4 ? 0.5f : -0.5f);
+  }
+}
+
+}  // namespace fv2p
+
+extern "C" int fv2p_roi_loss(const float* rois, const float* gt, const float* iou, const float* cls, const float* reg, int r, int gt_w,
+                             float cls_fg, float cls_bg, float soft_span, float reg_fg, float iou_label_thr, float beta, float* loss5,
+                             float* dcls, float* dreg, float* canonical, fv2p_stream_t stream_) {
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  FV2P_REQUIRE(r >= 1 && gt_w >= 7, FV2P_EINVAL, "roi_loss: at least one roi, gt rows of at least 7 values");
+  FV2P_REQUIRE(rois && gt && iou && cls && reg && loss5 && dcls && dreg, FV2P_EINVAL, "roi_loss: null pointer");
+  fv2p::RoiLossArgs a{r, gt_w, rois, gt, iou, cls, reg, cls_fg, cls_bg, soft_span, reg_fg, iou_label_thr, beta, loss5, dcls, dreg, canonical};
+  hipLaunchKernelGGL(fv2p::roi_loss_k, dim3(1), dim3(fv2p::kRoiLossThreads), 0, stream, a);
+  FV2P_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" size_t fv2p_point_loss_ws_bytes(int n) {
+  return static_cast<size_t>((n > 0 ? n : 0) + 255) / 256 * sizeof(double) + 64;
+}
+
+extern "C" int fv2p_point_loss(const float* logits, const int64_t* labels, int n, float alpha, float weight, float* loss, float* dlogits,
+                               float* score, void* ws, size_t ws_bytes, fv2p_stream_t stream_) {
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  FV2P_REQUIRE(n >= 1, FV2P_EINVAL, "point_loss: at least one point");
+  FV2P_REQUIRE(logits && labels && loss && dlogits && score && ws, FV2P_EINVAL, "point_loss: null pointer");
+  FV2P_REQUIRE(ws_bytes >= fv2p_point_loss_ws_bytes(n), FV2P_EINVAL, "point_loss: workspace too small");
+  const unsigned bx = static_cast<unsigned>((n + 255) / 256);
+  int* pos = static_cast<int*>(ws);
+  double* partial = reinterpret_cast<double*>(static_cast<char*>(ws) + 64);
+  FV2P_HIP(hipMemsetAsync(pos, 0, 64, stream));
+  hipLaunchKernelGGL(fv2p::point_pos_count_k, dim3(bx), dim3(256), 0, stream, n, labels, pos);
+  hipLaunchKernelGGL(fv2p::point_loss_k, dim3(bx), dim3(256), 0, stream, n, logits, labels, pos, alpha, weight, dlogits, score, partial);
+  hipLaunchKernelGGL(fv2p::point_loss_reduce_k, dim3(1), dim3(256), 0, stream, static_cast<int>(bx), partial, weight, loss);
+  FV2P_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int fv2p_roi_grid(const float* rois, int r, int g, float* local, float* column, float* corners, fv2p_stream_t stream_) {
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  FV2P_REQUIRE(r >= 0 && g >= 1 && g <= 64, FV2P_EINVAL, "roi_grid: grid size in 1..64");
+  if (r == 0) return 0;
+  FV2P_REQUIRE(rois && local && column && corners, FV2P_EINVAL, "roi_grid: null pointer");
+  hipLaunchKernelGGL(fv2p::roi_grid_k, dim3(r), dim3(256), 0, stream, g, rois, local, column, corners);
+  FV2P_LAUNCH_CHECK();
+  return 0;
+}

@@ -312,6 +312,90 @@ class AnchorLossFn(torch.autograd.Function):
         return dcls * g, dbox * g, ddirs * g, None, None, None, None
 
 
+class RoiLossFn(torch.autograd.Function):
+    """fv2p_roi_loss: the second-stage losses (IoUGuidedRoIHead.losses / reg_losses / corner_loss_lidar, with canonical_targets formed
+    inside) of the sampled RoIs in one launch, which leaves the gradients with respect to the class logit and the [iou, 7 residuals] row."""
+
+    @staticmethod
+    def forward(ctx, rois, gt, iou, cls, reg8, cfg):
+        r = cls.shape[0]
+        rois, gt = rois.reshape(-1, 7).contiguous(), gt.reshape(-1, gt.shape[-1]).contiguous()
+        iou, cls, reg8 = iou.reshape(-1).contiguous(), cls.contiguous(), reg8.contiguous()
+        if not (rois.shape[0] == gt.shape[0] == iou.shape[0] == reg8.shape[0] == r and cls.numel() == r and reg8.shape[1] == 8):
+            raise ValueError("RoiLossFn: rois (R, 7), gt (R, >= 7), iou (R), cls (R, 1) and reg (R, 8) must agree in R")
+        out = cls.new_empty(5)
+        dcls, dreg = torch.empty_like(cls), torch.empty_like(reg8)
+        with _nat.device_guard(cls.device):
+            _nat.call("fv2p_roi_loss", rois, gt, iou, cls, reg8, r, gt.shape[1], float(cfg.cls_fg), float(cfg.cls_bg),
+                      cfg.cls_fg - cfg.cls_bg, float(cfg.reg_fg), (cfg.reg_fg - 0.5) * 2, 1.0 / 9.0, out, dcls, dreg, None, _nat.stream())
+        ctx.save_for_backward(dcls, dreg)
+        return out[0]   # out = {total, cls, reg, corner, iou}
+
+    @staticmethod
+    def backward(ctx, g):
+        dcls, dreg = ctx.saved_tensors
+        return None, None, None, dcls * g, dreg * g, None
+
+
+class PointLossFn(torch.autograd.Function):
+    """fv2p_point_loss: PointHead's focal loss over labels in {-1, 0, 1}, its logit gradient and the score sigmoid(logit) in one pass."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, weight):
+        logits, labels = logits.contiguous(), labels.contiguous()
+        n = logits.numel()
+        out = logits.new_empty(1)
+        dlogits, score = torch.empty_like(logits), logits.new_empty(n)
+        with _nat.device_guard(logits.device):
+            ws = _nat.workspace(int(_nat.lib().fv2p_point_loss_ws_bytes(n)), logits.device)
+            _nat.call("fv2p_point_loss", logits, labels, n, 0.25, float(weight), out, dlogits, score, ws, ws.numel(), _nat.stream())
+        ctx.save_for_backward(dlogits)
+        ctx.mark_non_differentiable(score)
+        return out[0], score
+
+    @staticmethod
+    def backward(ctx, g, _):
+        dlogits, = ctx.saved_tensors
+        return dlogits * g, None, None
+
+
+def roi_grid_geometry(rois, g):
+    """fv2p_roi_grid: what roi_streams reads of the RoI grids, from one launch.  rois (..., 7) float32 on the GPU, no gradient ->
+    (local (R, g^3, 3) grid points in the roi's frame, x slowest; column (R, g^2, 3) world position of the lowest grid point of every
+    (x, y) column; corners (R, 8, 3) half-extent corner offsets)."""
+    if not (rois.is_cuda and rois.dtype == torch.float32) or rois.requires_grad:
+        raise ValueError("roi_grid_geometry: float32 CUDA rois without gradient (IoUGuidedRoIHead.grid_points is the tensor form)")
+    r = rois.reshape(-1, 7).contiguous()
+    local, column, corners = r.new_empty(r.shape[0], g ** 3, 3), r.new_empty(r.shape[0], g * g, 3), r.new_empty(r.shape[0], 8, 3)
+    with _nat.device_guard(r.device):
+        _nat.call("fv2p_roi_grid", r, r.shape[0], g, local, column, corners, _nat.stream())
+    return local, column, corners
+
+
+def pool_points_in_frame(layer, depth_normalizer, key, feats, scores, rois):
+    """fv2p_roipoint_pool3d_frame: RoIPointPool3d's selection on the enlarged boxes with the rows [x', y', z', score, depth, features]
+    written in the roi's frame by the pool kernel itself.  key (B, N, 3), feats (B * N, C), scores (B * N), rois (B, M, 7) ->
+    (B * M, S, 5 + C), no gradient (the reference pools under no_grad)."""
+    with torch.no_grad():
+        b, n, _ = key.shape
+        m, c, s = rois.shape[1], feats.shape[1], layer.num_sampled_points
+        rois = rois.contiguous()
+        big, extra = rois.clone(), layer.pool_extra_width   # the boxes of the inside test: every side widened (a list) or scaled (a scalar)
+        if isinstance(extra, (list, tuple)) and len(set(extra)) == 1:
+            big[..., 3:6] += extra[0]   # a Python scalar becomes a kernel argument: no host-to-device copy
+        elif isinstance(extra, (list, tuple)):
+            for axis, e in enumerate(extra):
+                big[..., 3 + axis] += e
+        else:
+            big[..., 3:6] += rois[..., 3:6] * extra
+        pooled = feats.new_empty((b * m, s, 5 + c))
+        empty = torch.empty((b, m), dtype=torch.int32, device=feats.device)
+        with _nat.device_guard(feats.device):
+            _nat.call("fv2p_roipoint_pool3d_frame", key.contiguous(), scores.detach().contiguous(), feats.detach().contiguous(), big, rois,
+                      b, n, m, c, s, float(depth_normalizer), pooled, empty, _nat.stream())
+    return pooled
+
+
 class AnchorHead(nn.Module):
     """AnchorHeadSingle + AxisAlignedTargetAssigner for one class (anchor_head_single.py, anchor_head_template.py,
     axis_aligned_target_assigner.py:132-212), targets assigned for the whole batch at once."""
@@ -598,6 +682,9 @@ class PointHead(nn.Module):
     def forward(self, key, feats, gt):
         logits = run_rows(self.cls_layers, feats)                                # (B*M, 1)
         labels = self.assign(key, gt)
+        if KERNEL_GLUE and logits.is_cuda and logits.dtype == torch.float32 and logits.shape[1] == 1:
+            # loss, logit gradient and score in one pass (csrc/targets.hip); the lines below state the same in tensor ops
+            return PointLossFn.apply(logits, labels, self.cfg.point_cls_weight)
         pos = labels > 0
         w = ((labels == 0) | pos).float() / pos.sum().float().clamp_min(1.0)
         loss = sigmoid_focal(logits, pos.float().unsqueeze(-1), w).sum() * self.cfg.point_cls_weight
@@ -812,6 +899,9 @@ class IoUGuidedRoIHead(nn.Module):
 
     def pool_points(self, key, feats, scores, rois):
         """roipool3d_gpu (:144-195): 512 points per enlarged roi with [score, depth, features], in the roi's frame."""
+        if KERNEL_GLUE and key.is_cuda and feats.dtype == torch.float32:
+            # the pool kernel writes the rows in the roi's frame itself (csrc/roi_pool.hip); the lines below state the same in tensor ops
+            return pool_points_in_frame(self.roipoint_pool3d_layer, self.cfg.depth_normalizer, key, feats, scores, rois)
         b = key.shape[0]
         depth = key.view(-1, 3).norm(dim=1) / self.cfg.depth_normalizer - 0.5
         allf = torch.cat((scores.detach()[:, None], depth[:, None], feats), dim=1).view(b, -1, feats.shape[1] + 2)
@@ -840,14 +930,22 @@ class IoUGuidedRoIHead(nn.Module):
         b = bev.shape[0]
         rois, _ = self.proposals(prop_scores, prop_boxes)
         s_rois, s_gt, s_iou = self.sample_targets(rois, gt, uniforms)
-        gt_ct = self.canonical_targets(s_rois, s_gt)
+        # fv2p_roi_loss forms the canonical targets itself: on that route nothing reads gt_ct (see losses)
+        gt_ct = None if (KERNEL_GLUE and s_rois.is_cuda) else self.canonical_targets(s_rois, s_gt)
         return dict(rois=rois, s_rois=s_rois, s_gt=s_gt, s_iou=s_iou, gt_ct=gt_ct, **self.roi_streams(bev, s_rois))
 
     def roi_streams(self, bev, s_rois, bev_stride=8):
         """The two streams of forward_single_loop (iouguided_roi_head.py:223-304) that need no key points: the RoI grids with the BEV
         features gathered at them, and the corner-geometry embedding."""
         b = bev.shape[0]
-        world, local = self.grid_points(s_rois)
+        g = self.cfg.grid_size_roi
+        kernel = KERNEL_GLUE and s_rois.is_cuda and s_rois.dtype == torch.float32 and not s_rois.requires_grad
+        if kernel:   # local grid, world column points and corner offsets from one launch (csrc/targets.hip: fv2p_roi_grid)
+            local, column, corners = roi_grid_geometry(s_rois, g)
+        else:
+            world, local = self.grid_points(s_rois)
+            column = world.view(world.shape[0], g * g, g, 3)[:, :, 0] if KERNEL_GLUE and world.shape[1] == g ** 3 else None
+        n_roi = local.shape[0]
         # BEV stream: bilinear gather at the grid points + channel compression (:243-255).  The g grid points of a column (same x
         # and y index, z fastest: grid_points) share their BEV position — the rotation is about z — so the reference's g^3 gathers
         # per RoI are g^2 different ones: gathered and compressed once per column and broadcast over z (autograd sums the g
@@ -855,24 +953,26 @@ class IoUGuidedRoIHead(nn.Module):
         # BatchNorm1d of the compression — whose batch statistics are those of the repeated rows; only the n / (n - 1) factor of its
         # running variance sees 13 824 instead of 82 944 rows).  Values equal the per-point form to rounding (tested).
         batch_dict = {"batch_size": b, "spatial_features_before_head": bev, "spatial_features_stride": bev_stride}
-        g = self.cfg.grid_size_roi
-        if KERNEL_GLUE and world.shape[1] == g ** 3:
-            column = world.view(world.shape[0], g * g, g, 3)[:, :, 0]
+        if column is not None:
             g_bev = self.bev_grid_pool_layer(batch_dict, column.reshape(b, -1, 3))
-            g_bev = g_bev.view(world.shape[0], g * g, 1, -1).expand(-1, -1, g, -1).reshape(world.shape[0], g ** 3, -1)
+            g_bev = g_bev.view(n_roi, g * g, 1, -1).expand(-1, -1, g, -1).reshape(n_roi, g ** 3, -1)
         else:
             g_bev = self.bev_grid_pool_layer(batch_dict, world.view(b, -1, 3)).view(world.shape[0], world.shape[1], -1)
         g_bev = g_bev.permute(0, 2, 1).contiguous()
         # corner geometry stream (feature_adaptor/nn_modules.py:6-60): roi-frame corners without rotation or centre
-        t = dconst(s_rois, _CORNER_SIGNS, s_rois.dtype) / 2
-        corners = s_rois.reshape(-1, 7)[:, None, 3:6] * t[None]
+        if not kernel:
+            t = dconst(s_rois, _CORNER_SIGNS, s_rois.dtype) / 2
+            corners = s_rois.reshape(-1, 7)[:, None, 3:6] * t[None]
         cge = self.cge_inter(self.cge_up(corners.transpose(1, 2).unsqueeze(3).contiguous()).squeeze(-1))
         return dict(local=local, g_bev=g_bev, cge=cge)
 
     def finish(self, key, feats, scores, prep):
         rois = prep["s_rois"]
         cls, reg = self.predict(key, feats, scores, rois, prep)
-        loss = self.losses(rois, prep["s_gt"], prep["gt_ct"], prep["s_iou"], cls, reg[:, 1:], reg[:, :1])
+        if KERNEL_GLUE and cls.is_cuda:   # the whole [iou, 7 residuals] row: one gradient tensor back, no slices to re-assemble
+            loss = self.losses(rois, prep["s_gt"], prep["gt_ct"], prep["s_iou"], cls, reg, None)
+        else:
+            loss = self.losses(rois, prep["s_gt"], prep["gt_ct"], prep["s_iou"], cls, reg[:, 1:], reg[:, :1])
         return loss, {"rois": prep["rois"], "sampled_rois": rois, "roi_iou": prep["s_iou"]}
 
     def predict(self, key, feats, scores, rois, prep):
@@ -914,8 +1014,16 @@ class IoUGuidedRoIHead(nn.Module):
         return loss_reg, loss_corner
 
     def losses(self, rois, gt_src, gt_ct, iou, cls, reg, iou_pred):
-        """get_box_cls_layer_loss / get_box_reg_layer_loss / get_box_iouscore_layer_loss (:137-265), CLS_SCORE_TYPE roi_iou."""
+        """get_box_cls_layer_loss / get_box_reg_layer_loss / get_box_iouscore_layer_loss (:137-265), CLS_SCORE_TYPE roi_iou.
+        iou_pred None: reg holds the whole (R, 8) row [iou, 7 residuals].  gt_ct None: the canonical targets are formed here."""
         cfg = self.cfg
+        if KERNEL_GLUE and cls.is_cuda and cls.dtype == torch.float32:
+            # losses and logit gradients in one launch (csrc/targets.hip: fv2p_roi_loss); the lines below state the same in tensor ops
+            return RoiLossFn.apply(rois, gt_src, iou, cls, reg if iou_pred is None else torch.cat((iou_pred, reg), dim=1), cfg)
+        if iou_pred is None:
+            reg, iou_pred = reg[:, 1:], reg[:, :1]
+        if gt_ct is None:
+            gt_ct = self.canonical_targets(rois.reshape(1, -1, 7), gt_src.reshape(1, -1, gt_src.shape[-1]))
         iou = iou.view(-1)
         soft = ((iou - cfg.cls_bg) / (cfg.cls_fg - cfg.cls_bg)).clamp(0, 1)     # 1 above fg, 0 below bg, linear in between
         soft = torch.where(iou > cfg.cls_fg, torch.ones_like(soft), torch.where(iou < cfg.cls_bg, torch.zeros_like(soft), soft))

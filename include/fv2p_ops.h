@@ -488,6 +488,30 @@ int fv2p_anchor_loss(const float* cls, const float* box, const float* dirs, cons
                      int batch, int n_anchor, float alpha, float beta, float dir_offset, float w_cls, float w_loc, float w_dir, float* loss4,
                      float* dcls, float* dbox, float* ddirs, void* ws, size_t ws_bytes, fv2p_stream_t stream);
 
+/* Second-stage losses in one launch (RoIWithIoUHeadTemplate.get_box_cls_layer_loss / get_box_reg_layer_loss /
+ * get_box_iouscore_layer_loss, pcdet/models/roi_heads/roi_withiou_head_template.py:133-265, CLS_SCORE_TYPE roi_iou), the canonical
+ * targets of assign_targets (:103-135) formed inside: rois [R,7] and gt [R,gt_w] (gt_w >= 7) are the sampled RoIs and their boxes,
+ * iou [R], cls [R] logits, reg [R,8] = [iou score, 7 residuals].  soft_span = cls_fg - cls_bg; iou_label_thr =
+ * (reg_fg - 0.5) * 2, the threshold of the IoU-score head on the label (iou - 0.5) * 2; beta of the regression smooth-L1.
+ * loss5 = {total, cls, reg, corner, iou}; dcls [R] and dreg [R,8] = d total / d logits; canonical [R,7] (may be null) = the
+ * canonical box of every roi.  One workgroup, sums in double in a
+ * fixed order; no workspace. */
+int fv2p_roi_loss(const float* rois, const float* gt, const float* iou, const float* cls, const float* reg, int r, int gt_w, float cls_fg,
+                  float cls_bg, float soft_span, float reg_fg, float iou_label_thr, float beta, float* loss5, float* dcls, float* dreg,
+                  float* canonical, fv2p_stream_t stream);
+
+/* Point-head foreground loss (PointHeadSimple, point_head_template.py:47-142): sigmoid focal loss (gamma 2) of logits [N] against
+ * labels [N] i64 in {-1 ignored, 0, 1}, weight 1 / max(#positive, 1) per counted point, times `weight`.  loss [1], dlogits [N] =
+ * d loss / d logits, score [N] = sigmoid(logits). */
+size_t fv2p_point_loss_ws_bytes(int n);
+int fv2p_point_loss(const float* logits, const int64_t* labels, int n, float alpha, float weight, float* loss, float* dlogits, float* score,
+                    void* ws, size_t ws_bytes, fv2p_stream_t stream);
+
+/* RoI grid geometry in one launch (iouguided_roi_head.py:195-220, feature_adaptor/nn_modules.py:6-60): rois [R,7] -> local [R,g^3,3]
+ * grid points in the roi's frame (x slowest), column [R,g^2,3] world position of the lowest grid point of every (x, y) column,
+ * corners [R,8,3] half extents in boxes_to_corners_3d order. */
+int fv2p_roi_grid(const float* rois, int r, int g, float* local, float* column, float* corners, fv2p_stream_t stream);
+
 /* ---- A15 / A18: point-in-box, RoI-aware voxel pooling, RoI point pooling ------------------------
  * Replace roiaware_pool3d_cuda.{points_in_boxes_gpu, points_in_boxes_cpu, forward, backward}
  * (pcdet/ops/roiaware_pool3d/src/roiaware_pool3d.cpp:29-177, kernels roiaware_pool3d_kernel.cu:16-359) and
@@ -508,6 +532,13 @@ int fv2p_points_in_boxes_cpu(const float* boxes, const float* pts, int boxes_num
 int fv2p_roipoint_pool3d(const float* xyz, const float* boxes3d, const float* pts_feature, int batch, int pts_num,
                          int boxes_num, int feature_len, int sampled_pts_num, float* pooled_features,
                          int* pooled_empty_flag, fv2p_stream_t stream);
+/* roipoint_pool3d with the rows already in the RoI's frame (IoUGuidedRoIHead.roipool3d_gpu, iouguided_roi_head.py:144-195): the
+ * same selection on boxes3d (B,M,7, the enlarged boxes), rows [x', y', z', score, depth, features...] (B,M,S,5+C) with
+ * (x', y', z') = the point minus the centre of rois (B,M,7, the original boxes) rotated by -heading, score from pts_score (B,N),
+ * depth = |point| / depth_normalizer - 0.5.  Empty boxes pool zeros. */
+int fv2p_roipoint_pool3d_frame(const float* xyz, const float* pts_score, const float* pts_feature, const float* boxes3d,
+                               const float* rois, int batch, int pts_num, int boxes_num, int feature_len, int sampled_pts_num,
+                               float depth_normalizer, float* pooled_features, int* pooled_empty_flag, fv2p_stream_t stream);
 int fv2p_roiaware_pool3d_fwd(const float* rois, const float* pts, const float* pts_feature, int boxes_num,
                              int pts_num, int channels, int max_pts_each_voxel, int out_x, int out_y, int out_z,
                              int pool_method, int* argmax, int* pts_idx_of_voxels, float* pooled_features,
