@@ -23,18 +23,6 @@ namespace {
 constexpr int kBnMaxC = 1024;
 constexpr int kBnPartials = 64;
 
-// parameter vectors: fp32 (pd == 0) or T
-template <class T>
-__device__ __forceinline__ float par_load(const void* p, int e, int pd, float dflt) {
-  if (!p) return dflt;
-  return pd ? T::widen(static_cast<const u16*>(p)[e]) : static_cast<const float*>(p)[e];
-}
-template <class T>
-__device__ __forceinline__ void par_store(void* p, int e, int pd, double v) {
-  if (pd) static_cast<u16*>(p)[e] = T::round(to_odd(v));
-  else static_cast<float*>(p)[e] = static_cast<float>(v);
-}
-
 // partial: [nblk][2][c] doubles, as bn_reduce_k
 template <class T, int V, bool BWD>
 __global__ __launch_bounds__(256) void bn_reduce_h_k(const u16* __restrict__ x, const u16* __restrict__ dy, BnGeom g,

@@ -11,6 +11,7 @@
 // Backward (gradient of the map): the transposed scatter with float atomics (torch's index backward is an unordered
 // accumulation as well), then the transpose back.
 #include "common.hpp"
+#include "dt16.hpp"
 
 namespace fv2p {
 
@@ -178,6 +179,89 @@ static int launch_transpose(const float* in, int batch, int rows, long long cols
   return 0;
 }
 
+// ---- float16 / bfloat16 maps ---------------------------------------------------------------------------------------------------------
+// The gather on 16-bit rows: the four corner rows widened, ((a wa + b wb) + c wc) + d wd in fp32 in that order, ONE rounding at the
+// store - bit for bit the fp32 kernel's result on the widened map, rounded.  x / y stay fp32.  8 channels per 16-byte access or one.
+template <class T, int V>
+__global__ __launch_bounds__(256) void bev_gather_h_k(const u16* __restrict__ im, const float* __restrict__ xs, const float* __restrict__ ys,
+                                                      int batch, long long n, int h, int w, int c, u16* __restrict__ out) {
+  const long long p = static_cast<long long>(blockIdx.x) * 4 + (threadIdx.x >> 6);
+  if (p >= static_cast<long long>(batch) * n) return;
+  const int lane = threadIdx.x & 63;
+  const long long b = p / n;
+  const Corners k = bev_corners(xs[p], ys[p], h, w);
+  const u16* base = im + b * static_cast<long long>(h) * w * c;
+  u16* o = out + p * c;
+  for (int ch = lane * V; ch < c; ch += 64 * V) {
+    Row16<T, V> va, vb, vc, vd, r;
+    va.load(base + k.a * c + ch); vb.load(base + k.b * c + ch); vc.load(base + k.c * c + ch); vd.load(base + k.d * c + ch);
+#pragma unroll
+    for (int i = 0; i < V; ++i) r.v[i] = ((va.v[i] * k.wa + vb.v[i] * k.wb) + vc.v[i] * k.wc) + vd.v[i] * k.wd;
+    r.store(o + ch);
+  }
+}
+
+// transpose_k on 16-bit elements: bit patterns are moved, so one kernel serves both formats.  64 x 64 tile, pitch 65; a thread moves 8
+// elements per 16-byte global access on either side where the sizes and the alignment allow, element by element otherwise.
+__global__ __launch_bounds__(256) void transpose_h_k(const u16* __restrict__ in, int rows, long long cols, u16* __restrict__ out) {
+  __shared__ u16 tile[64][65];
+  const long long b = blockIdx.z;
+  const u16* src = in + b * rows * cols;
+  u16* dst = out + b * rows * cols;
+  const long long c0 = static_cast<long long>(blockIdx.x) * 64;
+  const int r0 = blockIdx.y * 64;
+  const int q = threadIdx.x & 7, t = threadIdx.x >> 3;   // 8 octets x 32
+  const bool vec_in = (cols & 7) == 0 && (reinterpret_cast<uintptr_t>(in) & 15) == 0;
+  const bool vec_out = (rows & 7) == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0;
+#pragma unroll
+  for (int j = 0; j < 64; j += 32) {
+    const int r = r0 + t + j;
+    const long long cc = c0 + 8 * q;
+    u16 v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (r < rows) {
+      const u16* p = src + static_cast<long long>(r) * cols + cc;
+      if (vec_in && cc + 7 < cols) {
+        const uint4 f = *reinterpret_cast<const uint4*>(p);
+        const unsigned wd[4] = {f.x, f.y, f.z, f.w};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { v[2 * e] = static_cast<u16>(wd[e] & 0xffffu); v[2 * e + 1] = static_cast<u16>(wd[e] >> 16); }
+      } else {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) if (cc + e < cols) v[e] = p[e];
+      }
+    }
+#pragma unroll
+    for (int e = 0; e < 8; ++e) tile[t + j][8 * q + e] = v[e];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int j = 0; j < 64; j += 32) {
+    const long long cc = c0 + t + j;
+    const int r = r0 + 8 * q;
+    if (cc >= cols) continue;
+    u16 v[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) v[e] = tile[8 * q + e][t + j];
+    u16* p = dst + cc * rows + r;
+    if (vec_out && r + 7 < rows) {
+      unsigned wd[4];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) wd[e] = static_cast<unsigned>(v[2 * e]) | (static_cast<unsigned>(v[2 * e + 1]) << 16);
+      *reinterpret_cast<uint4*>(p) = make_uint4(wd[0], wd[1], wd[2], wd[3]);
+    } else {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) if (r + e < rows) p[e] = v[e];
+    }
+  }
+}
+
+static int launch_transpose_h(const u16* in, int batch, int rows, long long cols, u16* out, hipStream_t stream) {
+  FV2P_REQUIRE(batch <= 65535 && ceil_div(rows, 64) <= 65535, FV2P_ELIMIT, "transpose_h: batch or row count too large");
+  const dim3 grid(static_cast<unsigned>(ceil_div(cols, 64)), static_cast<unsigned>(ceil_div(rows, 64)), static_cast<unsigned>(batch));
+  hipLaunchKernelGGL(transpose_h_k, grid, dim3(256), 0, stream, in, rows, cols, out);
+  return 0;
+}
+
 }  // namespace fv2p
 
 using namespace fv2p;
@@ -267,6 +351,91 @@ extern "C" int fv2p_transpose_batched(const float* in, int batch, int64_t rows, 
   FV2P_REQUIRE(in && out && in != out, FV2P_EINVAL, "transpose_batched: null or aliased pointers");
   FV2P_REQUIRE(rows < (1ll << 31) && ceil_div(cols, 64) < (1ll << 31), FV2P_ELIMIT, "transpose_batched: too large");
   if (int rc = launch_transpose(in, batch, static_cast<int>(rows), cols, out, static_cast<hipStream_t>(stream_))) return rc;
+  FV2P_LAUNCH_CHECK();
+  return 0;
+}
+
+// ---- float16 / bfloat16 maps: `dtype` (FV2P_DT_F16 / FV2P_DT_BF16) names the format of bev, out, grad_out and grad_bev ----------------
+#define FV2P_BEV_H_DTYPE(name) \
+  FV2P_REQUIRE(dtype == FV2P_DT_F16 || dtype == FV2P_DT_BF16, FV2P_EINVAL, name ": dtype %d is neither fp16 (1) nor bf16 (2)", dtype)
+
+static size_t bev_map_elems(int batch, int c, int h, int w) {
+  return (batch < 1 || c < 1 || h < 1 || w < 1) ? 0 : static_cast<size_t>(batch) * c * h * w;
+}
+
+extern "C" size_t fv2p_bev_interp_h_ws_bytes(int batch, int c, int h, int w, int channels_first) {
+  return channels_first ? bev_map_elems(batch, c, h, w) * sizeof(u16) : 0;   // the channel-last image of the map, in its own format
+}
+
+extern "C" int fv2p_bev_interp_fwd_h(const void* bev, int batch, int c, int h, int w, int channels_first, const float* x, const float* y,
+                                     int64_t n, void* out, int dtype, void* ws, size_t ws_bytes, fv2p_stream_t stream_) {
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  FV2P_BEV_H_DTYPE("bev_interp_fwd_h");
+  FV2P_REQUIRE(batch >= 1 && c >= 1 && h >= 1 && w >= 1 && n >= 0, FV2P_EINVAL, "bev_interp_fwd_h: bad sizes");
+  if (n == 0) return 0;
+  FV2P_REQUIRE(bev && x && y && out, FV2P_EINVAL, "bev_interp_fwd_h: null pointer");
+  const u16* im = static_cast<const u16*>(bev);
+  if (channels_first) {
+    FV2P_REQUIRE(ws && ws_bytes >= fv2p_bev_interp_h_ws_bytes(batch, c, h, w, 1), FV2P_EWORKSPACE, "bev_interp_fwd_h: workspace too small");
+    if (int rc = launch_transpose_h(im, batch, c, static_cast<long long>(h) * w, static_cast<u16*>(ws), stream)) return rc;
+    im = static_cast<const u16*>(ws);
+  }
+  const long long pts = static_cast<long long>(batch) * n;
+  FV2P_REQUIRE(ceil_div(pts, 4) < (1ll << 31), FV2P_ELIMIT, "bev_interp_fwd_h: too many points");
+  const bool vec = (c % 8 == 0) && aligned16(im) && aligned16(out);
+  const dim3 grid(static_cast<unsigned>(ceil_div(pts, 4)));
+  u16* o = static_cast<u16*>(out);
+  const long long nn = static_cast<long long>(n);
+  if (dtype == FV2P_DT_F16) {
+    if (vec) hipLaunchKernelGGL((bev_gather_h_k<H16, 8>), grid, dim3(256), 0, stream, im, x, y, batch, nn, h, w, c, o);
+    else hipLaunchKernelGGL((bev_gather_h_k<H16, 1>), grid, dim3(256), 0, stream, im, x, y, batch, nn, h, w, c, o);
+  } else {
+    if (vec) hipLaunchKernelGGL((bev_gather_h_k<B16, 8>), grid, dim3(256), 0, stream, im, x, y, batch, nn, h, w, c, o);
+    else hipLaunchKernelGGL((bev_gather_h_k<B16, 1>), grid, dim3(256), 0, stream, im, x, y, batch, nn, h, w, c, o);
+  }
+  FV2P_LAUNCH_CHECK();
+  return 0;
+}
+
+// the entry lists of the fixed-order sum, the [B * H * W][C] staging gradient in 16 bits (channels_first), the scatter-add's workspace
+extern "C" size_t fv2p_bev_interp_bwd_h_ws_bytes(int batch, int c, int h, int w, int channels_first, int64_t n) {
+  const size_t map = bev_map_elems(batch, c, h, w);
+  if (map == 0 || n < 0) return 0;
+  return det_lists_bytes(static_cast<int64_t>(batch) * n * 4, c, true, channels_first ? (map + 1) / 2 : 0);
+}
+
+extern "C" int fv2p_bev_interp_bwd_h(const void* grad_out, int batch, int c, int h, int w, int channels_first, const float* x, const float* y,
+                                     int64_t n, void* grad_bev, int dtype, void* ws, size_t ws_bytes, fv2p_stream_t stream_) {
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  FV2P_BEV_H_DTYPE("bev_interp_bwd_h");
+  FV2P_REQUIRE(batch >= 1 && c >= 1 && h >= 1 && w >= 1 && n >= 0 && grad_bev, FV2P_EINVAL, "bev_interp_bwd_h: bad arguments");
+  const int64_t cells = static_cast<int64_t>(batch) * h * w, entries = static_cast<int64_t>(batch) * n * 4;
+  FV2P_REQUIRE(cells < (1ll << 31) - 1 && entries < (1ll << 31), FV2P_ELIMIT, "bev_interp_bwd_h: map or point count too large");
+  const size_t map = static_cast<size_t>(cells) * c;
+  if (n == 0) {   // no entries: the gradient is zero in either layout
+    FV2P_HIP(hipMemsetAsync(grad_bev, 0, map * sizeof(u16), stream));
+    return 0;
+  }
+  FV2P_REQUIRE(grad_out && x && y, FV2P_EINVAL, "bev_interp_bwd_h: null pointer");
+  FV2P_REQUIRE(ws && ws_bytes >= fv2p_bev_interp_bwd_h_ws_bytes(batch, c, h, w, channels_first, n), FV2P_EWORKSPACE, "bev_interp_bwd_h: workspace too small");
+  const DetLists d = det_lists(ws, ws_bytes, entries, c, true, channels_first ? (map + 1) / 2 : 0);
+  u16* gim = channels_first ? reinterpret_cast<u16*>(d.stage) : static_cast<u16*>(grad_bev);
+  hipLaunchKernelGGL(bev_entries_k, dim3(static_cast<unsigned>(ceil_div(entries / 4, 256))), dim3(256), 0, stream, x, y, batch,
+                     static_cast<long long>(n), h, w, c, d.dst, d.off, d.coef);
+  if (int rc = scatter_add_h(entries, c, cells, d.dst, d.off, d.coef, grad_out, 1, gim, dtype, d.sws, d.sws_bytes, stream)) return rc;   // zero-fills gim
+  if (channels_first)
+    if (int rc = launch_transpose_h(gim, batch, h * w, c, static_cast<u16*>(grad_bev), stream)) return rc;   // [B][HW][C] -> [B][C][HW]
+  FV2P_LAUNCH_CHECK();
+  return 0;
+}
+
+// fv2p_transpose_batched on 16-bit elements of either format (bit patterns are moved)
+extern "C" int fv2p_transpose_batched_h(const void* in, int batch, int64_t rows, int64_t cols, void* out, fv2p_stream_t stream_) {
+  FV2P_REQUIRE(batch >= 0 && rows >= 0 && cols >= 0, FV2P_EINVAL, "transpose_batched_h: bad sizes");
+  if (batch == 0 || rows == 0 || cols == 0) return 0;
+  FV2P_REQUIRE(in && out && in != out, FV2P_EINVAL, "transpose_batched_h: null or aliased pointers");
+  FV2P_REQUIRE(rows < (1ll << 31) && ceil_div(cols, 64) < (1ll << 31), FV2P_ELIMIT, "transpose_batched_h: too large");
+  if (int rc = launch_transpose_h(static_cast<const u16*>(in), batch, static_cast<int>(rows), cols, static_cast<u16*>(out), static_cast<hipStream_t>(stream_))) return rc;
   FV2P_LAUNCH_CHECK();
   return 0;
 }

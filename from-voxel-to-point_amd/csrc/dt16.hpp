@@ -33,6 +33,18 @@ __device__ __forceinline__ float to_odd(double d) {
   return f;
 }
 
+// parameter vectors of the BatchNorm kernels: fp32 (pd == 0) or T; a value computed in fp64 is written with ONE rounding
+template <class T>
+__device__ __forceinline__ float par_load(const void* p, int e, int pd, float dflt) {
+  if (!p) return dflt;
+  return pd ? T::widen(static_cast<const u16*>(p)[e]) : static_cast<const float*>(p)[e];
+}
+template <class T>
+__device__ __forceinline__ void par_store(void* p, int e, int pd, double v) {
+  if (pd) static_cast<u16*>(p)[e] = T::round(to_odd(v));
+  else static_cast<float*>(p)[e] = static_cast<float>(v);
+}
+
 // V elements of a row: one 16-byte access (V = 8, address 16-byte aligned) or one element (V = 1)
 template <class T, int V>
 struct Row16;

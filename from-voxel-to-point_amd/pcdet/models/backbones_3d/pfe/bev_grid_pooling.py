@@ -4,12 +4,15 @@ Mirrors the two callables of the reference's pcdet/models/backbones_3d/pfe/bev_g
 ``bilinear_interpolate_torch(im, x, y)`` (:11-45) and ``BEVGridPooling.interpolate_from_bev_features`` (:68-83, here also
 as the free function ``interpolate_from_bev_features``).  Same arguments, same arithmetic (corners clamped to the map,
 weights from the clamped corners), kernels in csrc/bev_interp.hip: no per-sample permute copy of the map, no four
-[N, C] corner temporaries, one launch for the whole batch.  CUDA float32 only; anything else raises (no CPU fallback)."""
+[N, C] corner temporaries, one launch for the whole batch.  CUDA float32, float16 and bfloat16 maps (the 16-bit ones gathered and differentiated in their own format,
+fp32 arithmetic, one rounding: no fp32 copy of the map); anything else raises (no CPU fallback)."""
 import torch
 from torch import nn
 from torch.autograd import Function
 
 import fv2p_native as _nat
+
+_DT16 = {torch.float16: 1, torch.bfloat16: 2}   # FV2P_DT_F16 / FV2P_DT_BF16 (include/fv2p_ops.h)
 
 
 class _BevInterp(Function):
@@ -18,8 +21,8 @@ class _BevInterp(Function):
     @staticmethod
     def forward(ctx, bev, x, y, channels_first):
         _nat.require_cuda(bev, x, y)
-        if bev.is_cuda and bev.dtype != torch.float32:
-            raise _nat.Fv2pError("bev_grid_pooling: float32 feature maps expected")
+        if bev.is_cuda and bev.dtype != torch.float32 and bev.dtype not in _DT16:
+            raise _nat.Fv2pError("bev_grid_pooling: float32, float16 or bfloat16 feature maps expected")
         bev = bev.contiguous()
         x, y = x.detach().float().contiguous(), y.detach().float().contiguous()
         if channels_first:
@@ -29,6 +32,13 @@ class _BevInterp(Function):
         n = x.shape[1]
         out = torch.empty((b, n, c), dtype=bev.dtype, device=bev.device)
         with _nat.device_guard(bev.device):
+            if bev.dtype in _DT16:
+                ws = _nat.workspace(max(_nat.call("fv2p_bev_interp_h_ws_bytes", b, c, h, w, int(channels_first)), 16), bev.device)
+                _nat.call("fv2p_bev_interp_fwd_h", bev, b, c, h, w, int(channels_first), x, y, n, out, _DT16[bev.dtype], ws, ws.numel(),
+                          _nat.stream())
+                ctx.save_for_backward(x, y)
+                ctx.geom = (b, c, h, w, bool(channels_first))
+                return out
             ws = _nat.workspace(max(int(_nat.lib().fv2p_bev_interp_ws_bytes(b, c, h, w, int(channels_first))), 16), bev.device)
             _nat.call("fv2p_bev_interp_fwd", bev, b, c, h, w, int(channels_first), x, y, n, out, ws, ws.numel(), _nat.stream())
         ctx.save_for_backward(x, y)
@@ -42,6 +52,11 @@ class _BevInterp(Function):
         g = grad_out.contiguous()
         grad_bev = torch.empty((b, c, h, w) if channels_first else (b, h, w, c), dtype=g.dtype, device=g.device)
         with _nat.device_guard(g.device):
+            if g.dtype in _DT16:   # 16-bit gradients exist in the fixed-order form only, whatever deterministic() says
+                ws = _nat.workspace(max(_nat.call("fv2p_bev_interp_bwd_h_ws_bytes", b, c, h, w, int(channels_first), x.shape[1]), 16), g.device)
+                _nat.call("fv2p_bev_interp_bwd_h", g, b, c, h, w, int(channels_first), x, y, x.shape[1], grad_bev, _DT16[g.dtype], ws, ws.numel(),
+                          _nat.stream())
+                return grad_bev, None, None, None
             if _nat.deterministic():   # fixed-order form (fv2p_scatter_add) instead of float atomics
                 ws = _nat.workspace(int(_nat.lib().fv2p_bev_interp_bwd_ws_bytes(b, c, h, w, int(channels_first), x.shape[1])), g.device)
                 _nat.call("fv2p_bev_interp_bwd_gather", g, b, c, h, w, int(channels_first), x, y, x.shape[1], grad_bev, ws, ws.numel(),

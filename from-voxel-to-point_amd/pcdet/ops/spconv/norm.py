@@ -15,7 +15,8 @@ either all fp32 or all of x's dtype.  Nothing is cast on the way.  That route al
 y = relu(bn(x) + residual).
 
 Dense maps [N, C, H, W] have the same op for `nn.BatchNorm2d` (`fusable2d`, `batch_norm2d_relu`, `run_maps`; kernels in
-csrc/batchnorm2d.hip): at the end of this file.
+csrc/batchnorm2d.hip): at the end of this file.  float16 / bfloat16 maps take `fusable2d16`, `batch_norm2d_relu16` and the kernels of
+csrc/batchnorm2d_h.hip, by the rules of the 16-bit row route; `run_maps` tries them where the fp32 op declined.
 """
 import os
 
@@ -316,6 +317,109 @@ def batch_norm2d_relu(bn, x, relu_module=None):
     return _BatchNorm2dReLU.apply(x, bn.weight, bn.bias, bn, relu_module is not None)
 
 
+# ---- the same pair on float16 / bfloat16 maps (csrc/batchnorm2d_h.hip) ------------------------------------------------------------------
+# x, y and the gradients stay in 16 bits; fp32 arithmetic, fp64 sums, one rounding at the store; the module's parameters and buffers are
+# all fp32 (a BatchNorm kept in fp32 under autocast) or all of x's dtype (backbone_2d.half()).  Nothing is cast on the way.
+BN2D_CHUNK16 = 4096   # plane elements per workgroup (kBn2dChunk16 in csrc/batchnorm2d_h.hip); tests place shapes on either side of it
+_WS_BYTES2D16 = {}
+
+
+def _ws_bytes2d16(n, c, hw):
+    b = _WS_BYTES2D16.get((n, c, hw))
+    if b is None:
+        b = _WS_BYTES2D16[(n, c, hw)] = _nat.call("fv2p_batchnorm2d_h_ws_bytes", n, c, hw)
+    return b
+
+
+class _BatchNorm2dReLU16(Function):
+    """y = relu?(bn(x)) on a float16 / bfloat16 map.  Saves x, the fp32 mean / invstd and the parameters; the backward pass recomputes
+    the mask of the stored y from x."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, bn, relu):
+        n, c, h, w = x.shape
+        hw = h * w
+        dev = x.device
+        dt = _DT16[x.dtype]
+        pd = 0 if _param_dtype(bn) in (None, torch.float32) else dt
+        batch_stats = bn.training or bn.running_mean is None
+        y = torch.empty_like(x)
+        with _nat.device_guard(dev):
+            if batch_stats:
+                stats = torch.empty((2, c), dtype=torch.float32, device=dev)
+                mean, invstd = stats[0], stats[1]
+                track = bn.training and bn.running_mean is not None
+                ws = _nat.workspace(_ws_bytes2d16(n, c, hw), dev)
+                _nat.call("fv2p_batchnorm2d_forward_h", x, n, c, hw, float(bn.eps), -1.0 if bn.momentum is None else float(bn.momentum),
+                          weight, bias, int(relu), bn.running_mean if track else None, bn.running_var if track else None,
+                          bn.num_batches_tracked if track else None, mean, invstd, y, dt, pd, ws, ws.numel(), _nat.stream())
+            else:
+                # [C] values: a widened copy (the buffer may move before this call's backward runs), 1 / sqrt in float64 so that invstd is
+                # the correctly rounded fp32 value
+                mean = bn.running_mean.float().clone()
+                invstd = (1.0 / torch.sqrt(bn.running_var.double() + bn.eps)).float()
+                _nat.call("fv2p_batchnorm2d_apply_h", x, n, c, hw, mean, invstd, weight, bias, int(relu), y, dt, pd, _nat.stream())
+        ctx.save_for_backward(x, mean, invstd, weight, bias)
+        ctx.relu, ctx.batch_stats, ctx.dt, ctx.pd = bool(relu), bool(batch_stats), dt, pd
+        return y
+
+    @staticmethod
+    def backward(ctx, dz):
+        x, mean, invstd, weight, bias = ctx.saved_tensors
+        n, c, h, w = x.shape
+        hw = h * w
+        dev = x.device
+        dz = dz.contiguous()
+        dx = torch.empty_like(x)
+        dpar = torch.empty((2, c), dtype=x.dtype if ctx.pd else torch.float32, device=dev)
+        dgamma, dbeta = dpar[0], dpar[1]
+        with _nat.device_guard(dev):
+            ws = _nat.workspace(_ws_bytes2d16(n, c, hw), dev)
+            _nat.call("fv2p_batchnorm2d_backward_h", x, dz, n, c, hw, mean, invstd, weight, bias, int(ctx.relu), int(ctx.batch_stats),
+                      dx, dgamma, dbeta, ctx.dt, ctx.pd, ws, ws.numel(), _nat.stream())
+        return (dx if ctx.needs_input_grad[0] else None, dgamma if (weight is not None and ctx.needs_input_grad[1]) else None,
+                dbeta if (bias is not None and ctx.needs_input_grad[2]) else None, None, None)
+
+
+def fusable2d16(bn, relu_module, x):
+    """The plain case of the (BatchNorm2d, ReLU) pair on a float16 / bfloat16 map x [N, C, H, W] the 16-bit op covers."""
+    if not _ENABLED or type(bn) is not nn.BatchNorm2d or not _plain_forward(bn):
+        return False
+    if relu_module is not None and (type(relu_module) is not nn.ReLU or not _plain_forward(relu_module)):
+        return False
+    if not (torch.is_tensor(x) and x.is_cuda and x.dtype in _DT16 and x.dim() == 4):
+        return False
+    if not x.is_contiguous() or x.shape[1] != bn.num_features:   # (channels_last maps are not NCHW-contiguous: torch's modules run)
+        return False
+    if torch.is_autocast_enabled() and not _ops.mixed_precision():   # the rule of fusable16
+        return False
+    n, _, h, w = x.shape
+    if n * h * w < (2 if bn.training else 1):   # torch raises for a single value per channel in training mode: let it
+        return False
+    if (bn.weight is None) != (bn.bias is None):
+        return False
+    pdt = _param_dtype(bn)
+    if pdt is False or pdt not in (None, torch.float32, x.dtype):
+        return False
+    for t in (bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked):
+        if t is not None and t.device != x.device:
+            return False
+    return True
+
+
+def batch_norm2d_relu16(bn, x, relu_module=None):
+    """y = relu?(bn(x)) for a contiguous float16 / bfloat16 map x [N, C, H, W] on the GPU, in x's dtype, or None when the 16-bit path
+    does not apply."""
+    if not fusable2d16(bn, relu_module, x):
+        return None
+    return _BatchNorm2dReLU16.apply(x, bn.weight, bn.bias, bn, relu_module is not None)
+
+
+def _bn2d_either(bn, x, relu_module):
+    y = batch_norm2d_relu(bn, x, relu_module)
+    return y if y is not None else batch_norm2d_relu16(bn, x, relu_module)
+
+
 def run_maps(mods, x):
     """The modules `mods` (a Sequential of Conv2d / ConvTranspose2d / BatchNorm2d / ReLU / ...) applied to the map x in order, with every
     (BatchNorm2d, ReLU) pair - or a BatchNorm2d alone - the fused op covers as one call.  Anything else runs as the module itself."""
@@ -325,10 +429,10 @@ def run_maps(mods, x):
         m = mods[i]
         if type(m) is nn.BatchNorm2d:
             relu = mods[i + 1] if i + 1 < len(mods) and type(mods[i + 1]) is nn.ReLU else None
-            y = batch_norm2d_relu(m, x, relu)
+            y = _bn2d_either(m, x, relu)     # the fp32 op, the 16-bit op where it declined
             if y is None and relu is not None:   # the ReLU module is not a plain one: the BatchNorm alone, then the module
                 relu = None
-                y = batch_norm2d_relu(m, x, None)
+                y = _bn2d_either(m, x, None)
             if y is not None:
                 x = y
                 i += 1 + (relu is not None)

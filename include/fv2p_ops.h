@@ -394,6 +394,23 @@ size_t fv2p_bev_interp_bwd_ws_bytes(int batch, int c, int h, int w, int channels
 int fv2p_bev_interp_bwd_gather(const float* grad_out, int batch, int c, int h, int w, int channels_first, const float* x,
                                const float* y, int64_t n, float* grad_bev, void* ws, size_t ws_bytes, fv2p_stream_t stream);
 
+/* The gather on float16 / bfloat16 maps (`dtype`: FV2P_DT_F16 / FV2P_DT_BF16, the format of bev, out, grad_out and grad_bev; any
+ * other value returns FV2P_EINVAL with "dtype" in the message and launches nothing).  x / y stay fp32; no operand is converted to
+ * fp32 in memory.  fwd: the four corner rows are widened, ((a * wa + b * wb) + c * wc) + d * wd is formed in fp32 in that order and
+ * rounded to nearest even ONCE: bit for bit fv2p_bev_interp_fwd on the widened map, rounded.  Lanes take 8 channels per 16-byte
+ * access when c % 8 == 0 and the pointers are 16-byte aligned, one channel otherwise.  Workspace: the channel-last image of a
+ * channels_first map in its own format, fv2p_bev_interp_h_ws_bytes (0 otherwise, and for a non-positive size).
+ * bwd: the fixed-order form only (the entries of fv2p_bev_interp_bwd_gather summed by the 16-bit form of fv2p_scatter_add: fp32
+ * sums in the same association, each cell's total rounded once), then the 16-bit transpose back for a channels_first map.  No
+ * atomics.  grad_bev is zero-filled where no point falls; n == 0 only zero-fills it.  Workspace: fv2p_bev_interp_bwd_h_ws_bytes
+ * (0 for a non-positive map size or n < 0). */
+size_t fv2p_bev_interp_h_ws_bytes(int batch, int c, int h, int w, int channels_first);
+int fv2p_bev_interp_fwd_h(const void* bev, int batch, int c, int h, int w, int channels_first, const float* x, const float* y,
+                          int64_t n, void* out, int dtype, void* ws, size_t ws_bytes, fv2p_stream_t stream);
+size_t fv2p_bev_interp_bwd_h_ws_bytes(int batch, int c, int h, int w, int channels_first, int64_t n);
+int fv2p_bev_interp_bwd_h(const void* grad_out, int batch, int c, int h, int w, int channels_first, const float* x,
+                          const float* y, int64_t n, void* grad_bev, int dtype, void* ws, size_t ws_bytes, fv2p_stream_t stream);
+
 /* ---- (f).2: SparseConvTensor.dense() and its gradient ---------------------------------------------------------
  * Replaces scatter_nd + permute + contiguous (pcdet/ops/spconv/structure.py:5-18, 57-66; consumer HeightCompression,
  * pcdet/models/backbones_2d/map_to_bev/height_compression.py:10-26).  indices [n, 1+ndim] (batch, z, y, x) or
@@ -802,6 +819,9 @@ int fv2p_dcn_backward_grouped(const float* x_nhwc, const float* wt, const float*
  * e.g. NCHW -> NHWC with rows = C, cols = H*W.  The reference does the same copies with at::permute + contiguous
  * (modulated_deform_conv_cuda.cu:78,118). */
 int fv2p_transpose_batched(const float* in, int batch, int64_t rows, int64_t cols, float* out, fv2p_stream_t stream);
+/* The same copy on 16-bit elements.  Bit patterns are moved, so one entry point serves float16 and bfloat16 and takes no dtype;
+ * 16-byte accesses of 8 elements on a side whose extent is a multiple of 8 and whose pointer is 16-byte aligned. */
+int fv2p_transpose_batched_h(const void* in, int batch, int64_t rows, int64_t cols, void* out, fv2p_stream_t stream);
 
 /* ---- A14: deformable position-sensitive RoI pooling ----------------------------------------------
  * Replace DCN.deform_psroi_pooling_forward / _backward
@@ -977,6 +997,40 @@ int fv2p_batchnorm2d_apply(const float* x, int64_t n, int c, int64_t hw, const f
 int fv2p_batchnorm2d_backward(const float* x, const float* dz, int64_t n, int c, int64_t hw, const float* mean,
                               const float* invstd, const float* gamma, const float* beta, int relu, int batch_stats,
                               float* dx, float* dgamma, float* dbeta, void* ws, size_t ws_bytes, fv2p_stream_t stream);
+
+/* ---- BatchNorm2d (+ReLU) on contiguous float16 / bfloat16 NCHW maps [n, c, hw] ------------------------------------------------
+ * The layer above on the 16-bit volume that fv2p_sparse_to_dense_h writes and the BEV backbones' convolutions keep
+ * (csrc/batchnorm2d_h.hip), with the conventions of the 16-bit row op: `dtype` (FV2P_DT_F16 / FV2P_DT_BF16) names the format of
+ * x, y, dz and dx; `param_dtype` is 0 (fp32) or equal to `dtype` and names the format of gamma, beta, running_mean, running_var,
+ * dgamma and dbeta; mean and invstd are ALWAYS fp32.  The dtype checks come first: any other value returns FV2P_EINVAL with
+ * "dtype" in the message.  Every argument check returns before anything is launched and leaves the outputs untouched
+ * (FV2P_EINVAL, FV2P_ELIMIT, FV2P_EWORKSPACE).  No map is converted to fp32 in memory: the workspace holds the fp64 partials and
+ * the counter copy only.
+ * Same two launches per direction, same grid and same fixed-order fold as the fp32 entry points: no float atomics, no grid
+ * barrier, bit-identical from run to run.  Elements are widened on load; sums are fp64; per element, in fp32 and in this order,
+ * (x - mean) * invstd * gamma + beta, then the ReLU (NaN passes through), then ONE rounding to nearest even at the store.  16-bit
+ * parameters are widened on read; a new running value, dgamma and dbeta go from their fp64 value to 16 bits in one rounding.
+ * A thread moves 8 elements per 16-byte access when hw % 8 == 0 and the maps are 16-byte aligned, one element otherwise.
+ *   fv2p_batchnorm2d_forward_h  : the contract of fv2p_batchnorm2d_forward.
+ *   fv2p_batchnorm2d_apply_h    : the same expression with given mean / invstd (eval mode).  One launch; n == 0 launches nothing.
+ *   fv2p_batchnorm2d_backward_h : dy = dz * [y > 0] where y is the STORED output, the forward's fp32 value rounded to the format,
+ *                                 recomputed from x (y is not read): a float16 pre-activation below 2^-25 was stored as 0 and gets
+ *                                 no gradient.  dx = gamma * invstd * (dy - c1 - xhat * c2) in fp32 in that order, rounded once;
+ *                                 c1 = mean dy, c2 = mean dy * xhat (both 0 when batch_stats == 0); dgamma = sum dy * xhat,
+ *                                 dbeta = sum dy.
+ * Workspace for _forward_h and _backward_h: fv2p_batchnorm2d_h_ws_bytes(n, c, hw) (0 for a shape that cannot be launched). */
+size_t fv2p_batchnorm2d_h_ws_bytes(int64_t n, int c, int64_t hw);
+int fv2p_batchnorm2d_forward_h(const void* x, int64_t n, int c, int64_t hw, float eps, float momentum, const void* gamma,
+                               const void* beta, int relu, void* running_mean, void* running_var,
+                               int64_t* num_batches_tracked, float* mean, float* invstd, void* y, int dtype, int param_dtype,
+                               void* ws, size_t ws_bytes, fv2p_stream_t stream);
+int fv2p_batchnorm2d_apply_h(const void* x, int64_t n, int c, int64_t hw, const float* mean, const float* invstd,
+                             const void* gamma, const void* beta, int relu, void* y, int dtype, int param_dtype,
+                             fv2p_stream_t stream);
+int fv2p_batchnorm2d_backward_h(const void* x, const void* dz, int64_t n, int c, int64_t hw, const float* mean,
+                                const float* invstd, const void* gamma, const void* beta, int relu, int batch_stats, void* dx,
+                                void* dgamma, void* dbeta, int dtype, int param_dtype, void* ws, size_t ws_bytes,
+                                fv2p_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Per-kernel timings on one GPU (events on the launch stream). Not part of the product or of bench.py; used to
-iterate on kernel variants:  python tools/microbench.py [conv|conv16|amp16|bn16|bn2d|exit16|dcn|fps|voxel|nms|all]"""
+iterate on kernel variants:  python tools/microbench.py [conv|conv16|amp16|bn16|bn2d|bn2d16|bev16|exit16|dcn|fps|voxel|nms|all]"""
 import os
 import sys
 import time
@@ -854,6 +854,124 @@ def bn2d(out_path=None):
             fh.write(text)
 
 
+def _windows(routes, rounds, reps):
+    """routes: {name: fn}; the routes take turns, window by window, in one process -> {name: [us per call of each window]}"""
+    times = {k: [] for k in routes}
+    for _ in range(rounds):
+        for k, fn in routes.items():
+            times[k].append(timeit(fn, reps=reps, warm=3))
+    return times
+
+
+def _cell(t):
+    return "%8.1f+-%5.1f" % (np.median(t), (max(t) - min(t)) / 2)
+
+
+def _write(lines, out_path):
+    text = "\n".join(lines) + "\n"
+    print(text)
+    if out_path:
+        os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+        with open(out_path, "w") as fh:
+            fh.write(text)
+
+
+def bn2d16(out_path=None):
+    """BatchNorm2d(eps=1e-3, momentum=0.01) + ReLU on the BEV maps in 16-bit storage (csrc/batchnorm2d_h.hip), forward and forward +
+    backward: the 16-bit op, the fp32 op on fp32 tensors of the same shape, and nn.BatchNorm2d + nn.ReLU on the same 16-bit tensors.
+    From bytes alone the 16-bit op should take half the fp32 op's time; the measured ratio stands next to that.  Each figure: the median
+    of ROUNDS windows of REPS calls, the routes taken alternately in one process; +- is half the range of the windows."""
+    from torch import nn
+    from pcdet.ops.spconv import norm
+    dev = torch.device("cuda:0")
+    ROUNDS, REPS = 7, 20
+    lines = ["BatchNorm2d + ReLU on 16-bit maps, us per call: median of %d windows of %d calls, +- half the range.  h16: the 16-bit op; f32: the fp32 op "
+             "on fp32 tensors; torch: nn.BatchNorm2d + nn.ReLU on the same 16-bit tensors.  h16/f32: expected 0.50 from bytes alone" % (ROUNDS, REPS),
+             "%-22s %-9s %-5s %-16s %-16s %-16s %-8s %-9s" % ("map", "dtype", "leg", "h16", "f32", "torch", "h16/f32", "h16/torch")]
+    for shape in ((3, 128, 200, 176), (3, 256, 100, 88), (3, 256, 200, 176)):
+        for dt in (torch.float16, torch.bfloat16):
+            torch.manual_seed(0)
+            x32 = (torch.randn(shape, device=dev) * 2 + 1).requires_grad_(True)
+            g32 = torch.randn(shape, device=dev)
+            x16, g16 = x32.detach().to(dt).requires_grad_(True), g32.to(dt)
+            fwd, both = {}, {}
+            for name, x, g, op, pdt in (("h16", x16, g16, norm.batch_norm2d_relu16, dt), ("f32", x32, g32, norm.batch_norm2d_relu, torch.float32),
+                                        ("torch", x16, g16, None, dt)):
+                bn, relu = nn.BatchNorm2d(shape[1], eps=1e-3, momentum=0.01).to(dev).to(pdt), nn.ReLU()
+
+                def f(bn=bn, relu=relu, x=x, op=op):
+                    y = op(bn, x, relu) if op is not None else relu(bn(x))
+                    assert y is not None
+                    return y
+
+                def fn_fwd(f=f):
+                    with torch.no_grad():
+                        f()
+
+                def fn_both(f=f, x=x, g=g, bn=bn):
+                    f().backward(g)
+                    x.grad = None
+                    bn.weight.grad = bn.bias.grad = None
+                fwd[name], both[name] = fn_fwd, fn_both
+            for leg, routes in (("fwd", fwd), ("f+b", both)):
+                t = _windows(routes, ROUNDS, REPS)
+                med = {k: np.median(v) for k, v in t.items()}
+                lines.append("%-22s %-9s %-5s %-16s %-16s %-16s %-8.2f %-9.2f" % (list(shape), str(dt).replace("torch.", ""), leg, _cell(t["h16"]),
+                                                                              _cell(t["f32"]), _cell(t["torch"]), med["h16"] / med["f32"],
+                                                                              med["h16"] / med["torch"]))
+                print(lines[-1], flush=True)
+            del x32, g32, x16, g16, fwd, both
+            torch.cuda.empty_cache()
+    _write(lines, out_path)
+
+
+def bev16(out_path=None):
+    """The bilinear gather and its gradient at 3 x 2048 key points on a [3, 256, 200, 176] map in 16-bit storage (fv2p_bev_interp_fwd_h /
+    _bwd_h) against the fp32 op on an fp32 map (gradient in the fixed-order form, the only one the 16-bit op has) and against the route
+    a 16-bit detector had before: .float() of the map -> fp32 op -> .to(dtype).  Alternating windows as in bn2d16."""
+    import fv2p_native as nat
+    from pcdet.models.backbones_3d.pfe.bev_grid_pooling import _BevInterp
+    dev = torch.device("cuda:0")
+    ROUNDS, REPS = 7, 10
+    shape, n = (3, 256, 200, 176), 2048
+    lines = ["bilinear gather on %s at 3 x %d key points, us per call: median of %d windows of %d calls, +- half the range.  h16: the 16-bit op; f32: "
+             "the fp32 op on an fp32 map (deterministic gradient); cast: .float() -> fp32 op -> .to(dtype) on the 16-bit map" % (list(shape), n, ROUNDS, REPS),
+             "%-9s %-5s %-16s %-16s %-16s %-8s %-8s" % ("dtype", "leg", "h16", "f32", "cast", "h16/f32", "h16/cast")]
+    torch.manual_seed(0)
+    x = torch.rand(3, n, device=dev) * (shape[3] - 1)
+    y = torch.rand(3, n, device=dev) * (shape[2] - 1)
+    nat.set_deterministic(True)
+    try:
+        for dt in (torch.float16, torch.bfloat16):
+            m32 = torch.randn(shape, device=dev).requires_grad_(True)
+            m16 = m32.detach().to(dt).requires_grad_(True)
+            g32 = torch.randn(3, n, shape[1], device=dev)
+            g16 = g32.to(dt)
+            ops = {"h16": (lambda: _BevInterp.apply(m16, x, y, True), m16, g16), "f32": (lambda: _BevInterp.apply(m32, x, y, True), m32, g32),
+                   "cast": (lambda: _BevInterp.apply(m16.float(), x, y, True).to(dt), m16, g16)}
+            fwd, both = {}, {}
+            for name, (f, m, g) in ops.items():
+                def fn_fwd(f=f):
+                    with torch.no_grad():
+                        f()
+
+                def fn_both(f=f, m=m, g=g):
+                    f().backward(g)
+                    m.grad = None
+                fwd[name], both[name] = fn_fwd, fn_both
+            for leg, routes in (("fwd", fwd), ("f+b", both)):
+                t = _windows(routes, ROUNDS, REPS)
+                med = {k: np.median(v) for k, v in t.items()}
+                lines.append("%-9s %-5s %-16s %-16s %-16s %-8.2f %-8.2f" % (str(dt).replace("torch.", ""), leg, _cell(t["h16"]), _cell(t["f32"]), _cell(t["cast"]),
+                                                                        med["h16"] / med["f32"], med["h16"] / med["cast"]))
+                print(lines[-1], flush=True)
+            del m32, m16, g32, g16, ops, fwd, both
+            torch.cuda.empty_cache()
+    finally:
+        nat.set_deterministic(False)
+    _write(lines, out_path)
+
+
 def bev():
     """Bilinear BEV gather at the FV2P size vs the reference's torch composition (permute + 4 index gathers + weights)."""
     from pcdet.models.backbones_3d.pfe import bev_grid_pooling as bgp
@@ -1011,6 +1129,12 @@ if __name__ == "__main__":
         sys.exit(0)
     if which == "bn2d":   # python tools/microbench.py bn2d [profiles/bn2d.txt]
         bn2d(sys.argv[2] if len(sys.argv) > 2 else None)
+        sys.exit(0)
+    if which == "bn2d16":   # python tools/microbench.py bn2d16 [profiles/bn2d_half.txt]
+        bn2d16(sys.argv[2] if len(sys.argv) > 2 else None)
+        sys.exit(0)
+    if which == "bev16":   # python tools/microbench.py bev16 [profiles/bev_half.txt]
+        bev16(sys.argv[2] if len(sys.argv) > 2 else None)
         sys.exit(0)
     if which == "exit16":   # python tools/microbench.py exit16 [profiles/exit_half.txt]
         exit16(sys.argv[2] if len(sys.argv) > 2 else None)
