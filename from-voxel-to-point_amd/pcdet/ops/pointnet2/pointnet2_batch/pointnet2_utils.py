@@ -10,11 +10,31 @@ import torch.nn as nn
 import fv2p_native as _nat
 
 from ... import _glue as G
+from ..pointnet2_stack import pointnet2_utils as _stack
+from ..pointnet2_stack.pointnet2_utils import _DT16, _rows_16bit
+
+
+def _coords_f32(op, *tensors):
+    """Coordinates are float32 only: their kernels read them through a float pointer, and 16 bits cannot carry metres anyway.  As for
+    the feature rows (_rows_16bit) only a device tensor is judged; host tensors belong to the CPU mirror of the tests."""
+    for t in tensors:
+        if t.is_cuda and t.dtype != torch.float32:
+            raise TypeError(f"{op}: float32 coordinates only, got {t.dtype}")
+
+
+def _one_dtype(op, saved, grad):
+    """-> True for a 16-bit gradient (the *_h entry point), False for the fp32 forms; the gradient has the dtype of the forward's features."""
+    h = _rows_16bit(op, grad)
+    fwd = saved.get("dtype", grad.dtype)
+    if fwd != grad.dtype and (h or fwd in _DT16):   # host tensors of the CPU mirror (float64 features, float32 output) are not judged
+        raise TypeError(f"{op}: features and gradient must have one dtype, got {fwd} and {grad.dtype}")
+    return h
 
 
 # ---- sampling / gathering ------------------------------------------------------------------------------------------------------
 def _fps(saved, xyz, npoint):
     """xyz (B, N, 3) -> (B, npoint) int32: index 0 first, then the farthest remaining point each round."""
+    _coords_f32("furthest_point_sample", xyz)
     b, n, _ = xyz.shape
     idx = G.new(xyz, (b, npoint), torch.int32)
     running = G.new(xyz, (b, n), fill=1e10)
@@ -25,16 +45,25 @@ def _fps(saved, xyz, npoint):
 
 def _gather(saved, features, idx):
     """features (B, C, N), idx (B, M) -> (B, C, M)."""
+    h = _rows_16bit("gather_operation", features)
     b, c, n = features.shape
     m = idx.shape[1]
-    out = G.new(features, (b, c, m))
-    G.run("fv2p_gather_points", b, c, n, m, features, idx, out)
-    saved.update(idx=idx, shape=(b, c, n, m))
+    out = G.new(features, (b, c, m), features.dtype if h else torch.float32)
+    if not h:
+        G.run("fv2p_gather_points", b, c, n, m, features, idx, out)
+    else:   # 16-bit elements are copied as they are
+        G.run("fv2p_gather_points_h", b, c, n, m, features, idx, out, _DT16[features.dtype])
+    saved.update(idx=idx, shape=(b, c, n, m), dtype=features.dtype)
     return out
 
 
 def _gather_grad(saved, grad):
     b, c, n, m = saved["shape"]
+    if _one_dtype("gather_operation gradient", saved, grad):   # the fixed-order form is the only one: fp32 sums in the order of fv2p_scatter_add, one rounding
+        g = torch.empty((b, c, n), dtype=grad.dtype, device=grad.device)
+        ws = G.scratch("fv2p_gather_points_grad_h_ws_bytes", grad.device, b, c, n, m)
+        G.run("fv2p_gather_points_grad_h", b, c, n, m, grad.contiguous(), saved["idx"], g, _DT16[grad.dtype], ws, ws.numel())
+        return g
     if _nat.deterministic():
         g = torch.empty((b, c, n), dtype=torch.float32, device=grad.device)
         ws = G.scratch("fv2p_gather_points_grad_ws_bytes", grad.device, b, c, n, m)
@@ -48,6 +77,7 @@ def _gather_grad(saved, grad):
 # ---- nearest neighbours and interpolation -------------------------------------------------------------------------------------------
 def _three_nn(saved, unknown, known):
     """unknown (B, N, 3), known (B, M, 3) -> (distances (B, N, 3), indices (B, N, 3)) of the three nearest known points."""
+    _coords_f32("three_nn", unknown, known)
     b, n, _ = unknown.shape
     d2 = G.new(unknown, (b, n, 3))
     idx = G.new(unknown, (b, n, 3), torch.int32)
@@ -57,16 +87,27 @@ def _three_nn(saved, unknown, known):
 
 def _interp(saved, features, idx, weight):
     """features (B, C, M), idx / weight (B, N, 3) -> (B, C, N)."""
+    h = _rows_16bit("three_interpolate", features)
     b, c, m = features.shape
     n = idx.shape[1]
-    out = G.new(features, (b, c, n))
-    G.run("fv2p_three_interpolate_batch", b, c, m, n, features, idx, weight, out)
-    saved.update(idx=idx, weight=weight, shape=(b, c, m, n))
+    out = G.new(features, (b, c, n), features.dtype if h else torch.float32)
+    if not h:
+        G.run("fv2p_three_interpolate_batch", b, c, m, n, features, idx, weight, out)
+    else:   # fp32 arithmetic on the widened values, one rounding; the weight stays float32
+        weight = weight.float() if weight.dtype in _DT16 else weight
+        G.run("fv2p_three_interpolate_batch_h", b, c, m, n, features, idx, weight, out, _DT16[features.dtype])
+    saved.update(idx=idx, weight=weight, shape=(b, c, m, n), dtype=features.dtype)
     return out
 
 
 def _interp_grad(saved, grad):
     b, c, m, n = saved["shape"]
+    if _one_dtype("three_interpolate gradient", saved, grad):   # always the fixed-order form, whatever the deterministic switch says
+        g = torch.empty((b, c, m), dtype=grad.dtype, device=grad.device)
+        ws = G.scratch("fv2p_three_interpolate_batch_grad_h_ws_bytes", grad.device, b, c, n, m)
+        G.run("fv2p_three_interpolate_batch_grad_h", b, c, n, m, grad.contiguous(), saved["idx"], saved["weight"], g, _DT16[grad.dtype], ws,
+              ws.numel())
+        return g
     if _nat.deterministic():
         g = torch.empty((b, c, m), dtype=torch.float32, device=grad.device)
         ws = G.scratch("fv2p_three_interpolate_batch_grad_ws_bytes", grad.device, b, c, n, m)
@@ -80,6 +121,7 @@ def _interp_grad(saved, grad):
 # ---- ball query and grouping ----------------------------------------------------------------------------------------------------------
 def _ball(saved, radius, nsample, xyz, new_xyz):
     """xyz (B, N, 3), new_xyz (B, M, 3) -> (B, M, nsample) int32, the first nsample points within `radius` in index order."""
+    _coords_f32("ball_query", xyz, new_xyz)
     b, n, _ = xyz.shape
     m = new_xyz.shape[1]
     idx = torch.zeros((b, m, nsample), dtype=torch.int32, device=xyz.device)
@@ -89,16 +131,25 @@ def _ball(saved, radius, nsample, xyz, new_xyz):
 
 def _group(saved, features, idx):
     """features (B, C, N), idx (B, M, S) -> (B, C, M, S)."""
+    h = _rows_16bit("grouping_operation", features)
     b, c, n = features.shape
     _, m, s = idx.shape
-    out = G.new(features, (b, c, m, s))
-    G.run("fv2p_group_points_batch", b, c, n, m, s, features, idx, out)
-    saved.update(idx=idx, shape=(b, c, n, m, s))
+    out = G.new(features, (b, c, m, s), features.dtype if h else torch.float32)
+    if not h:
+        G.run("fv2p_group_points_batch", b, c, n, m, s, features, idx, out)
+    else:   # 16-bit elements are copied as they are
+        G.run("fv2p_group_points_batch_h", b, c, n, m, s, features, idx, out, _DT16[features.dtype])
+    saved.update(idx=idx, shape=(b, c, n, m, s), dtype=features.dtype)
     return out
 
 
 def _group_grad(saved, grad):
     b, c, n, m, s = saved["shape"]
+    if _one_dtype("grouping_operation gradient", saved, grad):   # the fixed-order form is the only one
+        g = torch.empty((b, c, n), dtype=grad.dtype, device=grad.device)
+        ws = G.scratch("fv2p_group_points_batch_grad_h_ws_bytes", grad.device, b, c, n, m, s)
+        G.run("fv2p_group_points_batch_grad_h", b, c, n, m, s, grad.contiguous(), saved["idx"], g, _DT16[grad.dtype], ws, ws.numel())
+        return g
     if _nat.deterministic():
         g = torch.empty((b, c, n), dtype=torch.float32, device=grad.device)
         ws = G.scratch("fv2p_group_points_batch_grad_ws_bytes", grad.device, b, c, n, m, s)
@@ -134,11 +185,15 @@ class QueryAndGroup(nn.Module):
             assert self.use_xyz, "Cannot have not features and not use xyz as a feature!"
             return rel
         grouped = grouping_operation(features, idx)
+        if self.use_xyz and grouped.dtype in _DT16:
+            rel = rel.to(grouped.dtype)   # 16-bit features stay 16-bit (cat would promote them); the offsets are bounded by the radius
         return torch.cat([rel, grouped], dim=1) if self.use_xyz else grouped
 
 
 class GroupAll(nn.Module):
-    """One group holding every point: (B, 3 + C, 1, N)."""
+    """One group holding every point: (B, 3 + C, 1, N).  With 16-bit features and use_xyz the result keeps torch's promotion to the
+    coordinates' float32: these are absolute coordinates in metres, which 16 bits cannot carry (QueryAndGroup's are offsets inside
+    the ball and are cast)."""
 
     def __init__(self, use_xyz: bool = True):
         super().__init__()
@@ -158,10 +213,13 @@ def _inverse_distance_weights(dist):
 
 def top3_interpolate(xyz, new_xyz, feats, nsamples=None):
     """Features feats (N, C) at xyz (N, 3) interpolated onto new_xyz (M, 3) from the three nearest sources with
-    inverse-distance weights -> (M, C); the gradient reaches feats only (Voxel-to-Point decoder, reference :292-326)."""
+    inverse-distance weights -> (M, C); the gradient reaches feats only (Voxel-to-Point decoder, reference :292-326).  float16 /
+    bfloat16 feats give a result and a gradient of their dtype (the stacked three_interpolate on the rows as they are)."""
     if not (xyz.dim() == new_xyz.dim() == feats.dim() == 2):
         raise NotImplementedError
     dist, idx = three_nn(new_xyz.unsqueeze(0).contiguous(), xyz.unsqueeze(0).contiguous())
+    if feats.dtype in _DT16:   # (N, C) rows are the stacked op's layout already: no transposes, forward or backward
+        return _stack.three_interpolate(feats.contiguous(), idx[0], _inverse_distance_weights(dist)[0])
     out = three_interpolate(feats.t().unsqueeze(0).contiguous(), idx, _inverse_distance_weights(dist))
     return out[0].t()
 
@@ -175,4 +233,6 @@ def top3_interpolate_with_grad(xyz, new_xyz, feats, nsamples=None):
     near_xyz = grouping_operation(xyz.t().unsqueeze(0).contiguous(), idx)[0].permute(1, 2, 0)        # (M, 3, 3)
     near_feats = grouping_operation(feats.t().unsqueeze(0).contiguous(), idx)[0].permute(1, 2, 0)    # (M, 3, C)
     weight = _inverse_distance_weights((near_xyz - new_xyz.unsqueeze(1)).norm(dim=-1))
+    if feats.dtype in _DT16:   # grouped in 16 bits, the weighted sum in fp32, one rounding
+        return (near_feats.float() * weight.unsqueeze(-1)).sum(dim=1).to(feats.dtype)
     return (near_feats * weight.unsqueeze(-1)).sum(dim=1)

@@ -40,6 +40,9 @@ def _pool(saved, rois, pts, pts_feature, out_size, max_pts_each_voxel, pool_meth
     """rois (N, 7), pts (P, 3), pts_feature (P, C) -> (N, ox, oy, oz, C): max / mean of the point features per RoI voxel."""
     if rois.shape[1] != 7 or pts.shape[1] != 3:
         raise AssertionError("RoIAwarePool3d: rois (N, 7), pts (P, 3)")
+    for t in (rois, pts, pts_feature):
+        if t.is_cuda and t.dtype != torch.float32:   # the kernels read and write floats; there is no 16-bit form
+            raise TypeError(f"RoIAwarePool3d: float32 only, got {t.dtype}")
     ox, oy, oz = (int(out_size),) * 3 if isinstance(out_size, int) else (int(v) for v in out_size)
     n, p, c = rois.shape[0], pts.shape[0], pts_feature.shape[-1]
     pooled = torch.zeros((n, ox, oy, oz, c), dtype=pts_feature.dtype, device=pts_feature.device)
@@ -54,6 +57,8 @@ def _pool(saved, rois, pts, pts_feature, out_size, max_pts_each_voxel, pool_meth
 
 def _pool_grad(saved, grad):
     n, ox, oy, oz, c, p, cap = saved["dims"]
+    if grad.is_cuda and grad.dtype != torch.float32:
+        raise TypeError(f"RoIAwarePool3d gradient: float32 only, got {grad.dtype}")
     if _nat.deterministic():
         g = torch.empty((p, c), dtype=grad.dtype, device=grad.device)
         ws = G.scratch("fv2p_roiaware_pool3d_bwd_ws_bytes", grad.device, n, ox, oy, oz, c, cap, saved["code"])

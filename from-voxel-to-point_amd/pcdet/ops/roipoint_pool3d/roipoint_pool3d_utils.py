@@ -26,6 +26,9 @@ def _pool(saved, points, point_features, boxes3d, pool_extra_width, num_sampled_
     per enlarged box the first S inside points in index order, wrapped around when there are fewer."""
     if points.dim() != 3 or points.shape[2] != 3:
         raise AssertionError("RoIPointPool3d: points must be (B, N, 3)")
+    for t in (points, point_features, boxes3d):
+        if t.is_cuda and t.dtype != torch.float32:   # the kernel reads and writes floats; there is no 16-bit form: the pooled rows carry xyz in metres
+            raise TypeError(f"RoIPointPool3d: float32 only, got {t.dtype} (the pooled rows carry xyz in metres, which 16 bits cannot hold)")
     b, n, _ = points.shape
     m, c = boxes3d.shape[1], point_features.shape[2]
     # the kernel writes every element (zeros for an empty box): no 100 MB fill in front of it, as the reference needs (:54)

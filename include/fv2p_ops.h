@@ -725,6 +725,43 @@ size_t fv2p_three_interpolate_stack_grad_h_ws_bytes(int n, int c, int m);
 int fv2p_three_interpolate_stack_grad_h(int n, int c, int m, const void* grad_out, const int* idx, const float* weight,
                                         void* grad_features, int dtype, void* ws, size_t ws_bytes, fv2p_stream_t stream);
 
+/* ---- Batch gather, grouping and interpolation on 16-bit feature rows (csrc/pointnet2_batch_h.hip) ---------------------------------
+ * What GatherOperation, GroupingOperation and ThreeInterpolate of pointnet2_batch/pointnet2_utils.py:46-215 (sampling_gpu.cu:10-98,
+ * group_points_gpu.cu, interpolate_gpu.cu:76-160: float only in the reference) do on float16 / bfloat16 features; the PointnetSAModuleMSG
+ * of IoUGuidedRoIHead (iouguided_roi_head.py:51-69, 266-278) and PointnetFPModule reach them.  Layouts are the fp32 batch ops':
+ * features [B][C][N] channel-major, idx int32, weight fp32.  `dtype` (FV2P_DT_F16 / FV2P_DT_BF16) names the format of the feature,
+ * output and gradient elements.  Any other dtype, a null feature / gradient pointer where the sizes are non-zero, or c < 1 returns
+ * FV2P_EINVAL before anything is launched; zero-sized calls return 0 without a launch.  Nothing is converted to fp32 in memory.
+ *   fv2p_gather_points_h : points (b, c, n), idx (b, npoints) -> out (b, c, npoints);
+ *   fv2p_group_points_batch_h : points (b, c, n), idx (b, npoints, nsample) -> out (b, c, npoints, nsample).  Both are copies of 16-bit
+ *     elements (one kernel for both formats); an index outside [0, n) gives zeros (the fp32 kernels read it unguarded).
+ *   fv2p_three_interpolate_batch_h : points (b, c, m), idx / weight (b, n, 3) -> out (b, c, n) = w0 * f0 + w1 * f1 + w2 * f2 in fp32 on
+ *     the widened values, in the order of fv2p_three_interpolate_batch (no contraction), rounded to nearest even once: the bits of the
+ *     fp32 op on the widened features, rounded.  A known index outside [0, m) counts as a zero.
+ *   8 consecutive outputs of a (b, c) row per 16-byte store (their 8 indices as two 16-byte loads) when the row length (npoints,
+ *     npoints * nsample, n) is a multiple of 8 and idx / weight / out are 16-byte aligned; one element at a time otherwise.
+ *   The three gradients exist in the fixed-order form only (siblings of the fp32 *_grad_gather entry points; no float atomics): entries
+ *     in the order of those entry points, fp32 sums in the association of fv2p_scatter_add, every element of grad_points rounded ONCE -
+ *     the bits of the fp32 *_grad_gather result on the widened gradient, rounded.  grad_points is WRITTEN: elements no entry reaches are
+ *     zero, entries whose index is out of range are dropped.  The workspace (*_ws_bytes, pure host functions) holds the entry lists and
+ *     a 16-bit [b * rows][c] staging image that one 16-bit transpose moves into grad_points, never an fp32 image of the gradient.
+ *     FV2P_EWORKSPACE for a workspace that is too small, FV2P_ELIMIT from 2^31 entries or 2^30 rows on. */
+int fv2p_gather_points_h(int b, int c, int n, int npoints, const void* points, const int* idx, void* out, int dtype,
+                         fv2p_stream_t stream);
+size_t fv2p_gather_points_grad_h_ws_bytes(int b, int c, int n, int npoints);
+int fv2p_gather_points_grad_h(int b, int c, int n, int npoints, const void* grad_out, const int* idx, void* grad_points, int dtype,
+                              void* ws, size_t ws_bytes, fv2p_stream_t stream);
+int fv2p_group_points_batch_h(int b, int c, int n, int npoints, int nsample, const void* points, const int* idx, void* out,
+                              int dtype, fv2p_stream_t stream);
+size_t fv2p_group_points_batch_grad_h_ws_bytes(int b, int c, int n, int npoints, int nsample);
+int fv2p_group_points_batch_grad_h(int b, int c, int n, int npoints, int nsample, const void* grad_out, const int* idx,
+                                   void* grad_points, int dtype, void* ws, size_t ws_bytes, fv2p_stream_t stream);
+int fv2p_three_interpolate_batch_h(int b, int c, int m, int n, const void* points, const int* idx, const float* weight, void* out,
+                                   int dtype, fv2p_stream_t stream);
+size_t fv2p_three_interpolate_batch_grad_h_ws_bytes(int b, int c, int n, int m);
+int fv2p_three_interpolate_batch_grad_h(int b, int c, int n, int m, const void* grad_out, const int* idx, const float* weight,
+                                        void* grad_points, int dtype, void* ws, size_t ws_bytes, fv2p_stream_t stream);
+
 /* ---- A11 consumer: fused grid set-abstraction (gather -> shared-MLP layer -> max over the samples) ---------------------
  * The part of PointnetSAModuleMSG.forward (pointnet2_batch/pointnet2_modules.py:30-62) that follows the ball query, for the
  * bn=False module of IoUGuidedRoIHead (iouguided_roi_head.py:52-76) after its first, linear layer has been applied per point

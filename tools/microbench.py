@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Per-kernel timings on one GPU (events on the launch stream). Not part of the product or of bench.py; used to
-iterate on kernel variants:  python tools/microbench.py [conv|conv16|amp16|bn16|bn2d|bn2d16|bev16|exit16|dcn|fps|voxel|nms|all]"""
+iterate on kernel variants:  python tools/microbench.py [conv|conv16|amp16|bn16|bn2d|bn2d16|bev16|exit16|batch16|dcn|fps|voxel|nms|all]"""
 import os
 import sys
 import time
@@ -571,6 +571,71 @@ def exit16(out_path=None):
             fh.write(text)
 
 
+def batch16(out_path=None):
+    """The batched pointnet2 ops on 16-bit features (csrc/pointnet2_batch_h.hip) at the shapes FV2P gives them: the RoI head's grid
+    grouping (384 RoIs x 128 channels x 512 points, 216 grid points x 32 / 16 samples), the Voxel-to-Point decoder's interpolation
+    (35 000 known rows x 64 channels onto 16 384 queries: the batch op on (1, C, M) and the top3_interpolate route on (M, C) rows,
+    three_nn included) and a gather (3, 128, 16384) -> 4096.  Forward (no_grad) and forward + backward, four routes on the same data:
+      fp16 / bf16 op : the 16-bit op on float16 / bfloat16 tensors (gradient: the fixed-order form, the only one);
+      fp32 op        : the fp32 op on fp32 tensors of the same shape (gradient: the atomic form, the default);
+      round trip     : .float() -> fp32 op -> .to(float16), what a 16-bit caller had to do before.
+    From bytes alone the copies should take about half the fp32 op's time.  Each figure: the median of ROUNDS windows of REPS calls
+    (events on the stream, after a warm-up), the routes taken alternately round by round in one process; +- is half the range of the
+    windows.  The table also goes to `out_path` (profiles/batch_half.txt)."""
+    from pcdet.ops.pointnet2.pointnet2_batch import pointnet2_utils as bu
+    dev = torch.device("cuda:0")
+    ROUNDS, REPS = 7, 10
+    rng = np.random.default_rng(0)
+    lines = ["batched pointnet2 ops on 16-bit features, us per call: median of %d windows of %d calls, +- half the range; fwd | fwd+bwd" % (ROUNDS, REPS),
+             "%-46s %-24s %-24s %-24s %-24s" % ("op", "fp16 op", "bf16 op", "fp32 op", "round trip (fp16)")]
+
+    def group_case(s):
+        b, c, n, m = 384, 128, 512, 216
+        idx = torch.from_numpy(rng.integers(0, n, size=(b, m, s)).astype(np.int32)).to(dev)
+        return "grouping (384,128,512) idx (384,216,%d)" % s, (b, c, n), lambda x: bu.grouping_operation(x, idx)
+
+    def interp_case():
+        m, c, n = 35000, 64, 16384
+        idx = torch.from_numpy(rng.integers(0, m, size=(1, n, 3)).astype(np.int32)).to(dev)
+        w = torch.rand(1, n, 3, device=dev)
+        w = (w / w.sum(2, keepdim=True)).contiguous()
+        return "three_interpolate (1,64,35000) -> 16384", (1, c, m), lambda x: bu.three_interpolate(x, idx, w)
+
+    def top3_case():
+        m, c, n = 35000, 64, 16384
+        xyz, new_xyz = torch.rand(m, 3, device=dev) * 70, torch.rand(n, 3, device=dev) * 70
+        return "top3_interpolate (35000,64) -> 16384", (m, c), lambda x: bu.top3_interpolate(xyz, new_xyz, x)
+
+    def gather_case():
+        b, c, n, m = 3, 128, 16384, 4096
+        idx = torch.from_numpy(rng.integers(0, n, size=(b, m)).astype(np.int32)).to(dev)
+        return "gather (3,128,16384) -> 4096", (b, c, n), lambda x: bu.gather_operation(x, idx)
+
+    for title, shape, op in (group_case(32), group_case(16), interp_case(), top3_case(), gather_case()):
+        routes = []
+        for name, dt, trip in (("fp16 op", torch.float16, False), ("bf16 op", torch.bfloat16, False), ("fp32 op", torch.float32, False),
+                               ("round trip", torch.float16, True)):
+            x = torch.randn(shape, device=dev).to(dt).requires_grad_(True)
+            fwd = (lambda x=x, dt=dt: op(x.float()).to(dt)) if trip else (lambda x=x: op(x))
+            g = torch.randn(fwd().shape, device=dev).to(dt)
+
+            def both(fwd=fwd, g=g, x=x):
+                fwd().backward(g)
+                x.grad = None
+            routes.append((fwd, both, [], []))
+        for _ in range(ROUNDS):
+            for fwd, both, tf, tb in routes:
+                with torch.no_grad():
+                    tf.append(timeit(fwd, reps=REPS, warm=3))
+                tb.append(timeit(both, reps=REPS, warm=3))
+        cell = lambda tf, tb: "%8.1f+-%5.1f |%8.1f+-%5.1f" % (np.median(tf), (max(tf) - min(tf)) / 2, np.median(tb), (max(tb) - min(tb)) / 2)
+        lines.append("%-46s " % title + " ".join("%-24s" % cell(tf, tb) for _, _, tf, tb in routes))
+        print(lines[-1], flush=True)
+        del routes
+        torch.cuda.empty_cache()
+    _write(lines, out_path)
+
+
 def dcn():
     from pcdet.ops.DeformableConvolutionV2PyTorch.modules.mdeformable_conv_block import MdeformConvBlock
     dev = torch.device("cuda:0")
@@ -1138,6 +1203,9 @@ if __name__ == "__main__":
         sys.exit(0)
     if which == "exit16":   # python tools/microbench.py exit16 [profiles/exit_half.txt]
         exit16(sys.argv[2] if len(sys.argv) > 2 else None)
+        sys.exit(0)
+    if which == "batch16":   # python tools/microbench.py batch16 [profiles/batch_half.txt]
+        batch16(sys.argv[2] if len(sys.argv) > 2 else None)
         sys.exit(0)
     for name, fn in (("conv", conv), ("conv16", conv16), ("bn16", bn16), ("dcn", dcn), ("fps", fps), ("voxel", voxel), ("fpstrace", fpstrace), ("nn", nn), ("nms", nms), ("sa", sa), ("bn", bn), ("bev", bev), ("oproof", oproof)):
         if which in (name, "all"):
