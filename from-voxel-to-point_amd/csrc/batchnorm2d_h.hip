@@ -231,7 +231,7 @@ void launch_bwd2d(const BwdArgs2d& a, hipStream_t stream) {
 using namespace fv2p;
 
 #define FV2P_BN2D_H_DTYPES(name)                                                                                                                \
-  FV2P_REQUIRE(dtype == FV2P_DT_F16 || dtype == FV2P_DT_BF16, FV2P_EINVAL, name ": dtype %d is neither fp16 (1) nor bf16 (2)", dtype);        \
+  FV2P_DT16_OK(name, dtype);                                                                                                                    \
   FV2P_REQUIRE(param_dtype == 0 || param_dtype == dtype, FV2P_EINVAL, name ": param_dtype %d is neither 0 (fp32) nor the call's dtype %d",     \
                param_dtype, dtype)
 

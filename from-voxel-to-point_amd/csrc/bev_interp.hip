@@ -356,9 +356,6 @@ extern "C" int fv2p_transpose_batched(const float* in, int batch, int64_t rows, 
 }
 
 // ---- float16 / bfloat16 maps: `dtype` (FV2P_DT_F16 / FV2P_DT_BF16) names the format of bev, out, grad_out and grad_bev ----------------
-#define FV2P_BEV_H_DTYPE(name) \
-  FV2P_REQUIRE(dtype == FV2P_DT_F16 || dtype == FV2P_DT_BF16, FV2P_EINVAL, name ": dtype %d is neither fp16 (1) nor bf16 (2)", dtype)
-
 static size_t bev_map_elems(int batch, int c, int h, int w) {
   return (batch < 1 || c < 1 || h < 1 || w < 1) ? 0 : static_cast<size_t>(batch) * c * h * w;
 }
@@ -370,7 +367,7 @@ extern "C" size_t fv2p_bev_interp_h_ws_bytes(int batch, int c, int h, int w, int
 extern "C" int fv2p_bev_interp_fwd_h(const void* bev, int batch, int c, int h, int w, int channels_first, const float* x, const float* y,
                                      int64_t n, void* out, int dtype, void* ws, size_t ws_bytes, fv2p_stream_t stream_) {
   hipStream_t stream = static_cast<hipStream_t>(stream_);
-  FV2P_BEV_H_DTYPE("bev_interp_fwd_h");
+  FV2P_DT16_OK("bev_interp_fwd_h", dtype);
   FV2P_REQUIRE(batch >= 1 && c >= 1 && h >= 1 && w >= 1 && n >= 0, FV2P_EINVAL, "bev_interp_fwd_h: bad sizes");
   if (n == 0) return 0;
   FV2P_REQUIRE(bev && x && y && out, FV2P_EINVAL, "bev_interp_fwd_h: null pointer");
@@ -407,7 +404,7 @@ extern "C" size_t fv2p_bev_interp_bwd_h_ws_bytes(int batch, int c, int h, int w,
 extern "C" int fv2p_bev_interp_bwd_h(const void* grad_out, int batch, int c, int h, int w, int channels_first, const float* x, const float* y,
                                      int64_t n, void* grad_bev, int dtype, void* ws, size_t ws_bytes, fv2p_stream_t stream_) {
   hipStream_t stream = static_cast<hipStream_t>(stream_);
-  FV2P_BEV_H_DTYPE("bev_interp_bwd_h");
+  FV2P_DT16_OK("bev_interp_bwd_h", dtype);
   FV2P_REQUIRE(batch >= 1 && c >= 1 && h >= 1 && w >= 1 && n >= 0 && grad_bev, FV2P_EINVAL, "bev_interp_bwd_h: bad arguments");
   const int64_t cells = static_cast<int64_t>(batch) * h * w, entries = static_cast<int64_t>(batch) * n * 4;
   FV2P_REQUIRE(cells < (1ll << 31) - 1 && entries < (1ll << 31), FV2P_ELIMIT, "bev_interp_bwd_h: map or point count too large");

@@ -24,6 +24,10 @@ int set_error(int code, const char* fmt, ...);
     if (!(cond)) return ::fv2p::set_error((code), __VA_ARGS__); \
   } while (0)
 
+// `dtype` argument of a *_h entry point: one of the two 16-bit storage formats (`who` a literal or a const char*)
+#define FV2P_DT16_OK(who, dtype) \
+  FV2P_REQUIRE((dtype) == FV2P_DT_F16 || (dtype) == FV2P_DT_BF16, FV2P_EINVAL, "%s: dtype %d is neither fp16 (1) nor bf16 (2)", (who), (dtype))
+
 #define FV2P_HIP(expr)                                                              \
   do {                                                                              \
     hipError_t e__ = (expr);                                                        \

@@ -252,7 +252,7 @@ static int scatter_run(int64_t entries, int c, int64_t n_dst, const int* dst_row
 // once.  Only the pieces of rows that span segments are kept in fp32 (`part`, in the workspace of fv2p_scatter_add_ws_bytes).
 int scatter_add_h(int64_t entries, int c, int64_t n_dst, const int* dst_row, const int64_t* src_off, const float* coef, const void* src,
                   int64_t src_cs, void* out, int dtype, void* ws, size_t ws_bytes, hipStream_t st) {
-  FV2P_REQUIRE(dtype == FV2P_DT_F16 || dtype == FV2P_DT_BF16, FV2P_EINVAL, "scatter_add_h: dtype %d is neither fp16 (1) nor bf16 (2)", dtype);
+  FV2P_DT16_OK("scatter_add_h", dtype);
   FV2P_REQUIRE(entries >= 0 && c >= 1 && n_dst >= 0 && src_cs >= 1, FV2P_EINVAL, "scatter_add_h: bad sizes");
   if (n_dst == 0) return 0;
   FV2P_REQUIRE(out, FV2P_EINVAL, "scatter_add_h: null pointer");

@@ -273,7 +273,7 @@ static void launch_maxpool_bwd_h(bool vec, const void* in, const void* out, cons
 }
 extern "C" int fv2p_sparse_maxpool_fwd_h(const void* in, int64_t n_in, int c, const int* tab, int kvol, int64_t n_out, int flip_k, void* out, int dtype,
                                          fv2p_stream_t s) {
-  FV2P_REQUIRE(dtype == FV2P_DT_F16 || dtype == FV2P_DT_BF16, FV2P_EINVAL, "maxpool_fwd_h: dtype %d is neither fp16 (1) nor bf16 (2)", dtype);
+  FV2P_DT16_OK("maxpool_fwd_h", dtype);
   FV2P_REQUIRE(c >= 1 && kvol >= 1 && n_out >= 0 && n_in >= 0, FV2P_EINVAL, "maxpool_fwd_h: bad sizes");
   if (n_out == 0) return 0;
   FV2P_REQUIRE(in && tab && out, FV2P_EINVAL, "maxpool_fwd_h: null pointer");
@@ -285,7 +285,7 @@ extern "C" int fv2p_sparse_maxpool_fwd_h(const void* in, int64_t n_in, int c, co
 }
 extern "C" int fv2p_sparse_maxpool_bwd_h(const void* in, const void* out, const void* dout, int64_t n_in, int c, const int* tab_in, int kvol, void* din,
                                          int dtype, fv2p_stream_t s) {
-  FV2P_REQUIRE(dtype == FV2P_DT_F16 || dtype == FV2P_DT_BF16, FV2P_EINVAL, "maxpool_bwd_h: dtype %d is neither fp16 (1) nor bf16 (2)", dtype);
+  FV2P_DT16_OK("maxpool_bwd_h", dtype);
   FV2P_REQUIRE(c >= 1 && kvol >= 1 && n_in >= 0, FV2P_EINVAL, "maxpool_bwd_h: bad sizes");
   if (n_in == 0) return 0;
   FV2P_REQUIRE(in && out && dout && tab_in && din, FV2P_EINVAL, "maxpool_bwd_h: null pointer");
@@ -321,7 +321,7 @@ static void launch_group_bwd_h(bool vec, const void* g, int64_t n_out, int c, co
 }
 extern "C" int fv2p_sparse_group_fwd_h(const void* in, int64_t n_in, int c, const int* tab, int kvol, int64_t n_out, int flip_k, void* out, int dtype,
                                        fv2p_stream_t s) {
-  FV2P_REQUIRE(dtype == FV2P_DT_F16 || dtype == FV2P_DT_BF16, FV2P_EINVAL, "group_fwd_h: dtype %d is neither fp16 (1) nor bf16 (2)", dtype);
+  FV2P_DT16_OK("group_fwd_h", dtype);
   FV2P_REQUIRE(c >= 1 && kvol >= 1 && n_out >= 0 && n_in >= 0, FV2P_EINVAL, "group_fwd_h: bad sizes");
   FV2P_REQUIRE(n_out * kvol * c < (1ll << 40) && n_out < (1ll << 31) && n_in < (1ll << 31), FV2P_ELIMIT, "group_fwd_h: too many rows");
   if (n_out == 0) return 0;
@@ -337,7 +337,7 @@ extern "C" int fv2p_sparse_group_fwd_h(const void* in, int64_t n_in, int c, cons
 }
 extern "C" int fv2p_sparse_group_bwd_h(const void* grad, int64_t n_out, int c, const int* tab, int kvol, int64_t n_in, int flip_k, void* din, int dtype,
                                        fv2p_stream_t s) {
-  FV2P_REQUIRE(dtype == FV2P_DT_F16 || dtype == FV2P_DT_BF16, FV2P_EINVAL, "group_bwd_h: dtype %d is neither fp16 (1) nor bf16 (2)", dtype);
+  FV2P_DT16_OK("group_bwd_h", dtype);
   FV2P_REQUIRE(c >= 1 && kvol >= 1 && n_in >= 0 && n_out >= 0, FV2P_EINVAL, "group_bwd_h: bad sizes");
   FV2P_REQUIRE(n_out < (1ll << 31) && n_in < (1ll << 31), FV2P_ELIMIT, "group_bwd_h: too many rows");
   if (n_in == 0) return 0;
@@ -391,7 +391,7 @@ static void launch_dense_move_h(const int* ind, int64_t n, int c, int ndim, cons
 extern "C" int fv2p_sparse_to_dense_h(const void* features, const int* indices, int64_t n, int c, int ndim, int batch, const int spatial[3],
                                       int channels_first, void* dense, int dtype, fv2p_stream_t s_) {
   hipStream_t s = static_cast<hipStream_t>(s_);
-  FV2P_REQUIRE(dtype == FV2P_DT_F16 || dtype == FV2P_DT_BF16, FV2P_EINVAL, "sparse_to_dense_h: dtype %d is neither fp16 (1) nor bf16 (2)", dtype);
+  FV2P_DT16_OK("sparse_to_dense_h", dtype);
   FV2P_REQUIRE(c >= 1 && n >= 0 && n < (1ll << 31) && batch >= 1 && (ndim == 2 || ndim == 3), FV2P_EINVAL, "sparse_to_dense_h: bad sizes");
   FV2P_REQUIRE(dense && spatial, FV2P_EINVAL, "sparse_to_dense_h: null pointer");
   FV2P_REQUIRE(n == 0 || (features && indices), FV2P_EINVAL, "sparse_to_dense_h: null pointer");
@@ -406,7 +406,7 @@ extern "C" int fv2p_sparse_to_dense_h(const void* features, const int* indices, 
 extern "C" int fv2p_dense_to_sparse_h(const void* dense, const int* indices, int64_t n, int c, int ndim, int batch, const int spatial[3],
                                       int channels_first, void* rows, int dtype, fv2p_stream_t s_) {
   hipStream_t s = static_cast<hipStream_t>(s_);
-  FV2P_REQUIRE(dtype == FV2P_DT_F16 || dtype == FV2P_DT_BF16, FV2P_EINVAL, "dense_to_sparse_h: dtype %d is neither fp16 (1) nor bf16 (2)", dtype);
+  FV2P_DT16_OK("dense_to_sparse_h", dtype);
   FV2P_REQUIRE(c >= 1 && n >= 0 && n < (1ll << 31) && batch >= 1 && (ndim == 2 || ndim == 3), FV2P_EINVAL, "dense_to_sparse_h: bad sizes");
   FV2P_REQUIRE(n == 0 || (dense && indices && rows && spatial), FV2P_EINVAL, "dense_to_sparse_h: null pointer");
   if (n == 0) return 0;

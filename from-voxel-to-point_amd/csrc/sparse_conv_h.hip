@@ -383,7 +383,7 @@ void launch_wgrad(const WgradArgs& a, float* partial, unsigned chunks, hipStream
 template <bool W32>
 int conv_rows_entry(const char* name, const void* src, int64_t n_src, int c_src, const void* weight, int kvol, const int* tab, int64_t n_dst, int c_dst,
                     int flip_k, int transpose_w, const void* bias, void* dst, int dtype, fv2p_stream_t stream_) {
-  FV2P_REQUIRE(dtype == FV2P_DT_F16 || dtype == FV2P_DT_BF16, FV2P_EINVAL, "%s: dtype %d is neither fp16 (1) nor bf16 (2)", name, dtype);
+  FV2P_DT16_OK(name, dtype);
   FV2P_REQUIRE(c_src >= 1 && c_dst >= 1 && kvol >= 1 && n_dst >= 0 && n_src >= 0, FV2P_EINVAL, "%s: bad sizes", name);
   if (n_dst == 0) return 0;
   FV2P_REQUIRE(weight && tab && dst && (src || n_src == 0), FV2P_EINVAL, "%s: null pointer", name);
@@ -415,7 +415,7 @@ size_t wgrad_ws_bytes(int64_t n_dst, int c_src, int c_dst, int kvol) {
 template <bool F32>
 int conv_wgrad_entry(const char* name, const void* src, int64_t n_src, int c_src, const void* grad, const int* tab, int64_t n_dst, int c_dst, int kvol,
                      int flip_k, void* dweight, int dtype, void* ws, size_t ws_bytes, fv2p_stream_t stream_) {
-  FV2P_REQUIRE(dtype == FV2P_DT_F16 || dtype == FV2P_DT_BF16, FV2P_EINVAL, "%s: dtype %d is neither fp16 (1) nor bf16 (2)", name, dtype);
+  FV2P_DT16_OK(name, dtype);
   FV2P_REQUIRE(c_src >= 1 && c_dst >= 1 && kvol >= 1 && n_dst >= 0 && n_src >= 0, FV2P_EINVAL, "%s: bad sizes", name);
   if (n_dst == 0) return 0;
   FV2P_REQUIRE(dweight && (src || n_src == 0) && grad && tab, FV2P_EINVAL, "%s: null pointer", name);

@@ -12,7 +12,7 @@ from torch.autograd import Function
 
 import fv2p_native as _nat
 
-_DT16 = {torch.float16: 1, torch.bfloat16: 2}   # FV2P_DT_F16 / FV2P_DT_BF16 (include/fv2p_ops.h)
+from pcdet.ops._glue import DT16 as _DT16
 
 
 class _BevInterp(Function):
@@ -36,11 +36,9 @@ class _BevInterp(Function):
                 ws = _nat.workspace(max(_nat.call("fv2p_bev_interp_h_ws_bytes", b, c, h, w, int(channels_first)), 16), bev.device)
                 _nat.call("fv2p_bev_interp_fwd_h", bev, b, c, h, w, int(channels_first), x, y, n, out, _DT16[bev.dtype], ws, ws.numel(),
                           _nat.stream())
-                ctx.save_for_backward(x, y)
-                ctx.geom = (b, c, h, w, bool(channels_first))
-                return out
-            ws = _nat.workspace(max(int(_nat.lib().fv2p_bev_interp_ws_bytes(b, c, h, w, int(channels_first))), 16), bev.device)
-            _nat.call("fv2p_bev_interp_fwd", bev, b, c, h, w, int(channels_first), x, y, n, out, ws, ws.numel(), _nat.stream())
+            else:
+                ws = _nat.workspace(max(int(_nat.lib().fv2p_bev_interp_ws_bytes(b, c, h, w, int(channels_first))), 16), bev.device)
+                _nat.call("fv2p_bev_interp_fwd", bev, b, c, h, w, int(channels_first), x, y, n, out, ws, ws.numel(), _nat.stream())
         ctx.save_for_backward(x, y)
         ctx.geom = (b, c, h, w, bool(channels_first))
         return out

@@ -7,11 +7,9 @@ Each operator is a forward / backward function pair calling the C ABI directly (
 import torch
 import torch.nn as nn
 
-import fv2p_native as _nat
-
 from ... import _glue as G
+from ..._glue import rows_16bit as _rows_16bit   # kept under its earlier name here beside _coords_f32
 from ..pointnet2_stack import pointnet2_utils as _stack
-from ..pointnet2_stack.pointnet2_utils import _DT16, _rows_16bit
 
 
 def _coords_f32(op, *tensors):
@@ -23,12 +21,11 @@ def _coords_f32(op, *tensors):
 
 
 def _one_dtype(op, saved, grad):
-    """-> True for a 16-bit gradient (the *_h entry point), False for the fp32 forms; the gradient has the dtype of the forward's features."""
+    """The gradient has a dtype the library serves, and it is the dtype of the forward's features."""
     h = _rows_16bit(op, grad)
     fwd = saved.get("dtype", grad.dtype)
-    if fwd != grad.dtype and (h or fwd in _DT16):   # host tensors of the CPU mirror (float64 features, float32 output) are not judged
+    if fwd != grad.dtype and (h or fwd in G.DT16):   # host tensors of the CPU mirror (float64 features, float32 output) are not judged
         raise TypeError(f"{op}: features and gradient must have one dtype, got {fwd} and {grad.dtype}")
-    return h
 
 
 # ---- sampling / gathering ------------------------------------------------------------------------------------------------------
@@ -52,26 +49,15 @@ def _gather(saved, features, idx):
     if not h:
         G.run("fv2p_gather_points", b, c, n, m, features, idx, out)
     else:   # 16-bit elements are copied as they are
-        G.run("fv2p_gather_points_h", b, c, n, m, features, idx, out, _DT16[features.dtype])
+        G.run("fv2p_gather_points_h", b, c, n, m, features, idx, out, G.DT16[features.dtype])
     saved.update(idx=idx, shape=(b, c, n, m), dtype=features.dtype)
     return out
 
 
 def _gather_grad(saved, grad):
     b, c, n, m = saved["shape"]
-    if _one_dtype("gather_operation gradient", saved, grad):   # the fixed-order form is the only one: fp32 sums in the order of fv2p_scatter_add, one rounding
-        g = torch.empty((b, c, n), dtype=grad.dtype, device=grad.device)
-        ws = G.scratch("fv2p_gather_points_grad_h_ws_bytes", grad.device, b, c, n, m)
-        G.run("fv2p_gather_points_grad_h", b, c, n, m, grad.contiguous(), saved["idx"], g, _DT16[grad.dtype], ws, ws.numel())
-        return g
-    if _nat.deterministic():
-        g = torch.empty((b, c, n), dtype=torch.float32, device=grad.device)
-        ws = G.scratch("fv2p_gather_points_grad_ws_bytes", grad.device, b, c, n, m)
-        G.run("fv2p_gather_points_grad_gather", b, c, n, m, grad.contiguous(), saved["idx"], g, ws, ws.numel())
-        return g
-    g = torch.zeros((b, c, n), dtype=torch.float32, device=grad.device)
-    G.run("fv2p_gather_points_grad", b, c, n, m, grad.contiguous(), saved["idx"], g)
-    return g
+    _one_dtype("gather_operation gradient", saved, grad)
+    return G.grad_route("fv2p_gather_points_grad", grad, (b, c, n), (b, c, n, m), (grad.contiguous(), saved["idx"]), (b, c, n, m))
 
 
 # ---- nearest neighbours and interpolation -------------------------------------------------------------------------------------------
@@ -94,28 +80,17 @@ def _interp(saved, features, idx, weight):
     if not h:
         G.run("fv2p_three_interpolate_batch", b, c, m, n, features, idx, weight, out)
     else:   # fp32 arithmetic on the widened values, one rounding; the weight stays float32
-        weight = weight.float() if weight.dtype in _DT16 else weight
-        G.run("fv2p_three_interpolate_batch_h", b, c, m, n, features, idx, weight, out, _DT16[features.dtype])
+        weight = weight.float() if weight.dtype in G.DT16 else weight
+        G.run("fv2p_three_interpolate_batch_h", b, c, m, n, features, idx, weight, out, G.DT16[features.dtype])
     saved.update(idx=idx, weight=weight, shape=(b, c, m, n), dtype=features.dtype)
     return out
 
 
 def _interp_grad(saved, grad):
     b, c, m, n = saved["shape"]
-    if _one_dtype("three_interpolate gradient", saved, grad):   # always the fixed-order form, whatever the deterministic switch says
-        g = torch.empty((b, c, m), dtype=grad.dtype, device=grad.device)
-        ws = G.scratch("fv2p_three_interpolate_batch_grad_h_ws_bytes", grad.device, b, c, n, m)
-        G.run("fv2p_three_interpolate_batch_grad_h", b, c, n, m, grad.contiguous(), saved["idx"], saved["weight"], g, _DT16[grad.dtype], ws,
-              ws.numel())
-        return g
-    if _nat.deterministic():
-        g = torch.empty((b, c, m), dtype=torch.float32, device=grad.device)
-        ws = G.scratch("fv2p_three_interpolate_batch_grad_ws_bytes", grad.device, b, c, n, m)
-        G.run("fv2p_three_interpolate_batch_grad_gather", b, c, n, m, grad.contiguous(), saved["idx"], saved["weight"], g, ws, ws.numel())
-        return g
-    g = torch.zeros((b, c, m), dtype=torch.float32, device=grad.device)
-    G.run("fv2p_three_interpolate_batch_grad", b, c, n, m, grad.contiguous(), saved["idx"], saved["weight"], g)
-    return g
+    _one_dtype("three_interpolate gradient", saved, grad)
+    return G.grad_route("fv2p_three_interpolate_batch_grad", grad, (b, c, m), (b, c, n, m),
+                        (grad.contiguous(), saved["idx"], saved["weight"]), (b, c, n, m))
 
 
 # ---- ball query and grouping ----------------------------------------------------------------------------------------------------------
@@ -138,26 +113,15 @@ def _group(saved, features, idx):
     if not h:
         G.run("fv2p_group_points_batch", b, c, n, m, s, features, idx, out)
     else:   # 16-bit elements are copied as they are
-        G.run("fv2p_group_points_batch_h", b, c, n, m, s, features, idx, out, _DT16[features.dtype])
+        G.run("fv2p_group_points_batch_h", b, c, n, m, s, features, idx, out, G.DT16[features.dtype])
     saved.update(idx=idx, shape=(b, c, n, m, s), dtype=features.dtype)
     return out
 
 
 def _group_grad(saved, grad):
     b, c, n, m, s = saved["shape"]
-    if _one_dtype("grouping_operation gradient", saved, grad):   # the fixed-order form is the only one
-        g = torch.empty((b, c, n), dtype=grad.dtype, device=grad.device)
-        ws = G.scratch("fv2p_group_points_batch_grad_h_ws_bytes", grad.device, b, c, n, m, s)
-        G.run("fv2p_group_points_batch_grad_h", b, c, n, m, s, grad.contiguous(), saved["idx"], g, _DT16[grad.dtype], ws, ws.numel())
-        return g
-    if _nat.deterministic():
-        g = torch.empty((b, c, n), dtype=torch.float32, device=grad.device)
-        ws = G.scratch("fv2p_group_points_batch_grad_ws_bytes", grad.device, b, c, n, m, s)
-        G.run("fv2p_group_points_batch_grad_gather", b, c, n, m, s, grad.contiguous(), saved["idx"], g, ws, ws.numel())
-        return g
-    g = torch.zeros((b, c, n), dtype=torch.float32, device=grad.device)
-    G.run("fv2p_group_points_batch_grad", b, c, n, m, s, grad.contiguous(), saved["idx"], g)
-    return g
+    _one_dtype("grouping_operation gradient", saved, grad)
+    return G.grad_route("fv2p_group_points_batch_grad", grad, (b, c, n), (b, c, n, m, s), (grad.contiguous(), saved["idx"]), (b, c, n, m, s))
 
 
 FurthestPointSampling = G.autograd_op("FurthestPointSampling", _fps)
@@ -185,7 +149,7 @@ class QueryAndGroup(nn.Module):
             assert self.use_xyz, "Cannot have not features and not use xyz as a feature!"
             return rel
         grouped = grouping_operation(features, idx)
-        if self.use_xyz and grouped.dtype in _DT16:
+        if self.use_xyz and grouped.dtype in G.DT16:
             rel = rel.to(grouped.dtype)   # 16-bit features stay 16-bit (cat would promote them); the offsets are bounded by the radius
         return torch.cat([rel, grouped], dim=1) if self.use_xyz else grouped
 
@@ -218,7 +182,7 @@ def top3_interpolate(xyz, new_xyz, feats, nsamples=None):
     if not (xyz.dim() == new_xyz.dim() == feats.dim() == 2):
         raise NotImplementedError
     dist, idx = three_nn(new_xyz.unsqueeze(0).contiguous(), xyz.unsqueeze(0).contiguous())
-    if feats.dtype in _DT16:   # (N, C) rows are the stacked op's layout already: no transposes, forward or backward
+    if feats.dtype in G.DT16:   # (N, C) rows are the stacked op's layout already: no transposes, forward or backward
         return _stack.three_interpolate(feats.contiguous(), idx[0], _inverse_distance_weights(dist)[0])
     out = three_interpolate(feats.t().unsqueeze(0).contiguous(), idx, _inverse_distance_weights(dist))
     return out[0].t()
@@ -233,6 +197,6 @@ def top3_interpolate_with_grad(xyz, new_xyz, feats, nsamples=None):
     near_xyz = grouping_operation(xyz.t().unsqueeze(0).contiguous(), idx)[0].permute(1, 2, 0)        # (M, 3, 3)
     near_feats = grouping_operation(feats.t().unsqueeze(0).contiguous(), idx)[0].permute(1, 2, 0)    # (M, 3, C)
     weight = _inverse_distance_weights((near_xyz - new_xyz.unsqueeze(1)).norm(dim=-1))
-    if feats.dtype in _DT16:   # grouped in 16 bits, the weighted sum in fp32, one rounding
+    if feats.dtype in G.DT16:   # grouped in 16 bits, the weighted sum in fp32, one rounding
         return (near_feats.float() * weight.unsqueeze(-1)).sum(dim=1).to(feats.dtype)
     return (near_feats * weight.unsqueeze(-1)).sum(dim=1)

@@ -15,22 +15,6 @@ def _cnt(t):
     return (t if t.dtype == torch.int32 else t.int()).contiguous()
 
 
-# 16-bit storage formats of the *_h entry points (FV2P_DT_F16 / FV2P_DT_BF16 of include/fv2p_ops.h)
-_DT16 = {torch.float16: 1, torch.bfloat16: 2}
-
-
-def _rows_16bit(op, t):
-    """-> True for float16 / bfloat16 rows (the *_h kernels of csrc/pointnet2.hip), False for the fp32 kernels.  The library reads
-    the rows through a pointer of that type and nothing is cast on the way, so a device tensor of any other dtype is an error.  (A
-    host tensor never reaches the library: G.run refuses it; the CPU mirror of the tests, oracle/backend.py, answers the fp32 call
-    names for float32 and float64 host tensors alike.)"""
-    if t.dtype in _DT16:
-        return True
-    if t.is_cuda and t.dtype != torch.float32:
-        raise TypeError(f"{op}: float32, float16 and bfloat16 rows only, got {t.dtype}")
-    return False
-
-
 def _ball(saved, radius, nsample, xyz, xyz_batch_cnt, new_xyz, new_xyz_batch_cnt):
     """-> (idx (M, nsample) rows LOCAL to the sample, empty_ball_mask (M) bool); empty balls come back as row 0."""
     m = new_xyz.shape[0]
@@ -47,7 +31,7 @@ def _group(saved, features, features_batch_cnt, idx, idx_batch_cnt):
     if features.shape[0] != int(features_batch_cnt.sum()) or idx.shape[0] != int(idx_batch_cnt.sum()):
         raise AssertionError(f"rows and batch counts disagree: features {tuple(features.shape)} / {features_batch_cnt.tolist()}, "
                              f"idx {tuple(idx.shape)} / {idx_batch_cnt.tolist()}")
-    h = _rows_16bit("grouping_operation (stack)", features)
+    h = G.rows_16bit("grouping_operation (stack)", features)
     dt = features.dtype if h else torch.float32
     (m, s), (n, c) = idx.shape, features.shape
     b = idx_batch_cnt.shape[0]
@@ -55,27 +39,16 @@ def _group(saved, features, features_batch_cnt, idx, idx_batch_cnt):
     if not h:
         G.run("fv2p_group_points_stack", b, m, c, s, features, _cnt(features_batch_cnt), idx, _cnt(idx_batch_cnt), out)
     else:   # 16-bit rows are copied as they are
-        G.run("fv2p_group_points_stack_h", b, m, c, n, s, features, _cnt(features_batch_cnt), idx, _cnt(idx_batch_cnt), out, _DT16[dt])
+        G.run("fv2p_group_points_stack_h", b, m, c, n, s, features, _cnt(features_batch_cnt), idx, _cnt(idx_batch_cnt), out, G.DT16[dt])
     saved.update(idx=idx, fc=_cnt(features_batch_cnt), ic=_cnt(idx_batch_cnt), dims=(b, m, c, n, s))
     return out
 
 
 def _group_grad(saved, grad):
     b, m, c, n, s = saved["dims"]
-    dt = grad.dtype
-    if _rows_16bit("grouping_operation (stack) gradient", grad):   # the fixed-order form is the only one: fp32 sums in the order of fv2p_scatter_add, every row rounded once
-        g = torch.empty((n, c), dtype=dt, device=grad.device)
-        ws = G.scratch("fv2p_group_points_stack_grad_h_ws_bytes", grad.device, m, c, s)
-        G.run("fv2p_group_points_stack_grad_h", b, m, c, n, s, grad.contiguous(), saved["idx"], saved["ic"], saved["fc"], g, _DT16[dt], ws, ws.numel())
-        return g
-    if _nat.deterministic():
-        g = torch.empty((n, c), dtype=torch.float32, device=grad.device)
-        ws = G.scratch("fv2p_group_points_stack_grad_ws_bytes", grad.device, m, c, s)
-        G.run("fv2p_group_points_stack_grad_gather", b, m, c, n, s, grad.contiguous(), saved["idx"], saved["ic"], saved["fc"], g, ws, ws.numel())
-        return g
-    g = torch.zeros((n, c), dtype=torch.float32, device=grad.device)
-    G.run("fv2p_group_points_stack_grad", b, m, c, n, s, grad.contiguous(), saved["idx"], saved["ic"], saved["fc"], g)
-    return g
+    G.rows_16bit("grouping_operation (stack) gradient", grad)
+    return G.grad_route("fv2p_group_points_stack_grad", grad, (n, c), (b, m, c, n, s),
+                        (grad.contiguous(), saved["idx"], saved["ic"], saved["fc"]), (m, c, s))
 
 
 def _fps(saved, xyz, npoint):
@@ -167,14 +140,14 @@ def _interp(saved, features, idx, weight):
     """features (M, C), idx / weight (N, 3) -> (N, C)."""
     if idx.shape != weight.shape or idx.shape[1] != 3:
         raise AssertionError("three_interpolate (stack): idx and weight must both be (N, 3)")
-    h = _rows_16bit("three_interpolate (stack)", features)
+    h = G.rows_16bit("three_interpolate (stack)", features)
     dt = features.dtype
     idx, weight = idx.contiguous(), weight.contiguous()
     out = torch.zeros((idx.shape[0], features.shape[1]), dtype=dt, device=features.device)
     if not h:
         G.run("fv2p_three_interpolate_stack", idx.shape[0], features.shape[1], features.contiguous(), idx, weight, out)
     else:   # fp32 arithmetic on the widened rows, one rounding
-        G.run("fv2p_three_interpolate_stack_h", idx.shape[0], features.shape[1], features.shape[0], features.contiguous(), idx, weight, out, _DT16[dt])
+        G.run("fv2p_three_interpolate_stack_h", idx.shape[0], features.shape[1], features.shape[0], features.contiguous(), idx, weight, out, G.DT16[dt])
     saved.update(idx=idx, weight=weight, rows=features.shape[0])
     return out
 
@@ -191,20 +164,10 @@ GATHER_GRAD_MIN_QUERIES = 8192
 
 def _interp_grad(saved, grad):
     n, c, m = grad.shape[0], grad.shape[1], saved["rows"]
-    dt = grad.dtype
-    if _rows_16bit("three_interpolate (stack) gradient", grad):   # always the fixed-order form, whatever FV2P_INTERP_GATHER or the deterministic switch say
-        g = torch.empty((m, c), dtype=dt, device=grad.device)
-        ws = G.scratch("fv2p_three_interpolate_stack_grad_h_ws_bytes", grad.device, n, c, m)
-        G.run("fv2p_three_interpolate_stack_grad_h", n, c, m, grad.contiguous(), saved["idx"], saved["weight"], g, _DT16[dt], ws, ws.numel())
-        return g
-    if _nat.deterministic() or (n >= GATHER_GRAD_MIN_QUERIES and os.environ.get("FV2P_INTERP_GATHER", "1") != "0"):
-        g = torch.empty((m, c), dtype=grad.dtype, device=grad.device)
-        ws = G.scratch("fv2p_three_interpolate_stack_grad_ws_bytes", grad.device, n, c, m)
-        G.run("fv2p_three_interpolate_stack_grad_gather", n, c, m, grad.contiguous(), saved["idx"], saved["weight"], g, ws, ws.numel())
-        return g
-    g = torch.zeros((m, c), dtype=grad.dtype, device=grad.device)
-    G.run("fv2p_three_interpolate_stack_grad", n, c, grad.contiguous(), saved["idx"], saved["weight"], g)
-    return g
+    G.rows_16bit("three_interpolate (stack) gradient", grad)
+    return G.grad_route("fv2p_three_interpolate_stack_grad", grad, (m, c), (n, c, m), (grad.contiguous(), saved["idx"], saved["weight"]),
+                        (n, c, m), atomic_sizes=(n, c), dtype=grad.dtype,
+                        gather=n >= GATHER_GRAD_MIN_QUERIES and os.environ.get("FV2P_INTERP_GATHER", "1") != "0")
 
 
 BallQuery = G.autograd_op("BallQuery", _ball)
@@ -238,6 +201,6 @@ class QueryAndGroup(nn.Module):
             return rel, idx
         grouped = grouping_operation(features, xyz_batch_cnt, idx, new_xyz_batch_cnt)
         grouped[empty] = 0
-        if self.use_xyz and grouped.dtype in _DT16:
+        if self.use_xyz and grouped.dtype in G.DT16:
             rel = rel.to(grouped.dtype)   # 16-bit features stay 16-bit: cat would promote them to the coordinates' float32
         return (torch.cat([rel, grouped], dim=1) if self.use_xyz else grouped), idx

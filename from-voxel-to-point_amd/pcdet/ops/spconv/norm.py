@@ -27,6 +27,7 @@ from torch.autograd import Function
 import fv2p_native as _nat
 
 from . import ops as _ops
+from .._glue import DT16 as _DT16
 
 _ENABLED = os.environ.get("FV2P_FUSED_BN", "1") != "0"
 
@@ -82,7 +83,6 @@ class _BatchNormReLU(Function):
                 dbeta if (bias is not None and ctx.needs_input_grad[2]) else None, None, None)
 
 
-_DT16 = {torch.float16: 1, torch.bfloat16: 2}   # FV2P_DT_F16 / FV2P_DT_BF16 (include/fv2p_ops.h)
 _WS_BYTES16 = {}
 
 

@@ -10,6 +10,9 @@ import torch
 
 import fv2p_native as _nat
 
+from .. import _glue as G
+from .._glue import DT16 as _DT16
+
 
 def get_conv_output_size(input_size, kernel_size, stride, padding, dilation):
     out = []
@@ -367,20 +370,11 @@ def _rulebook_of(indice_pairs, indice_pair_num, n_src_rows, num_activate_out, in
     return rb
 
 
-_DT16 = {torch.float16: 1, torch.bfloat16: 2}   # FV2P_DT_F16 / FV2P_DT_BF16 (include/fv2p_ops.h)
-
-
 def _conv_dtype(*tensors):
     """The one dtype of a sparse conv call's floating operands: float32 (the fp32 kernels) or a key of _DT16 (the 16-bit MFMA
-    kernels of csrc/sparse_conv_h.hip).  Nothing is converted on the way, so every operand has to have it."""
-    dts = {t.dtype for t in tensors if t is not None}
-    if len(dts) > 1:
-        raise TypeError("sparse conv: features, weights, bias and gradients must share one dtype, got "
-                        + ", ".join(sorted(str(d) for d in dts)) + " (convert the module or the features; nothing is cast here)")
-    dt = dts.pop()
-    if dt != torch.float32 and dt not in _DT16:
-        raise NotImplementedError("sparse conv: float32, float16 and bfloat16 only, got %s" % dt)
-    return dt
+    kernels of csrc/sparse_conv_h.hip)."""
+    return G.one_dtype("sparse conv", "features, weights, bias and gradients", *tensors,
+                       advice="convert the module or the features; nothing is cast here")
 
 
 _MIXED = False
@@ -538,69 +532,41 @@ def indice_maxpool_backward(features, out_features, out_bp, indice_pairs, indice
     return _table_maxpool_backward(features, out_features, out_bp, table)
 
 
-def _pool_dtype(*tensors):
-    """The one dtype of a max-pool call's tensors: float32 (the fp32 kernels) or a key of _DT16 (the *_h kernels of
-    csrc/sparse_aux.hip).  Nothing is converted on the way, so every tensor has to have it."""
-    dts = {t.dtype for t in tensors}
-    if len(dts) > 1:
-        raise TypeError("sparse max-pool: features, outputs and gradients must share one dtype, got "
-                        + ", ".join(sorted(str(d) for d in dts)) + " (nothing is cast here)")
-    dt = dts.pop()
-    if dt != torch.float32 and dt not in _DT16:
-        raise NotImplementedError("sparse max-pool: float32, float16 and bfloat16 only, got %s" % dt)
-    return dt
-
-
 def _table_maxpool(features, table, flip, n_out):
     _nat.require_cuda(features)
-    dt = _pool_dtype(features)
+    dt = G.one_dtype("sparse max-pool", "features, outputs and gradients", features)
     if dt != torch.float32:   # 16-bit rows in, 16-bit rows out: compared on the widened values, the result is an input or 0
         f = features.contiguous()
         out = torch.empty((n_out, f.shape[1]), dtype=dt, device=f.device)
         with _nat.device_guard(f.device):
             _nat.call("fv2p_sparse_maxpool_fwd_h", f, f.shape[0], f.shape[1], table, table.shape[0], n_out, int(flip), out, _DT16[dt], _nat.stream())
         return out
-    half = features.dtype == torch.half
-    f = features.float().contiguous()
+    f = features.contiguous()
     out = torch.empty((n_out, f.shape[1]), dtype=torch.float32, device=f.device)
     with _nat.device_guard(f.device):
         _nat.call("fv2p_sparse_maxpool_fwd", f, f.shape[0], f.shape[1], table, table.shape[0], n_out, int(flip), out, _nat.stream())
-    return out.half() if half else out
+    return out
 
 
 def _table_maxpool_backward(features, out_features, out_bp, tab_in):
-    dt = _pool_dtype(features, out_features, out_bp)
+    dt = G.one_dtype("sparse max-pool", "features, outputs and gradients", features, out_features, out_bp)
     if dt != torch.float32:   # fp32 sum over ascending k, rounded once
         f, o, g = features.contiguous(), out_features.contiguous(), out_bp.contiguous()
         din = torch.empty_like(f)
         with _nat.device_guard(f.device):
             _nat.call("fv2p_sparse_maxpool_bwd_h", f, o, g, f.shape[0], f.shape[1], tab_in, tab_in.shape[0], din, _DT16[dt], _nat.stream())
         return din
-    half = features.dtype == torch.half
-    f, o, g = features.float().contiguous(), out_features.float().contiguous(), out_bp.float().contiguous()
+    f, o, g = features.contiguous(), out_features.contiguous(), out_bp.contiguous()
     din = torch.empty_like(f)
     with _nat.device_guard(f.device):
         _nat.call("fv2p_sparse_maxpool_bwd", f, o, g, f.shape[0], f.shape[1], tab_in, tab_in.shape[0], din, _nat.stream())
-    return din.half() if half else din
-
-
-def _group_dtype(*tensors):
-    """The one dtype of a group call's tensors: float32 (the fp32 kernels) or a key of _DT16 (the *_h kernels of csrc/sparse_aux.hip).
-    Nothing is converted on the way, so every tensor has to have it."""
-    dts = {t.dtype for t in tensors}
-    if len(dts) > 1:
-        raise TypeError("sparse group: features and gradients must share one dtype, got "
-                        + ", ".join(sorted(str(d) for d in dts)) + " (nothing is cast here)")
-    dt = dts.pop()
-    if dt != torch.float32 and dt not in _DT16:
-        raise NotImplementedError("sparse group: float32, float16 and bfloat16 only, got %s" % dt)
-    return dt
+    return din
 
 
 def indice_group(features, indice_pairs, indice_pair_num, num_activate_out, inverse=False, subm=False):
     """[K, n_out, C] gather of neighbour features, zeros where no neighbour (reference ops.py:196-211).  16-bit rows are copied as
     they are."""
-    dt = _group_dtype(features)
+    dt = G.one_dtype("sparse group", "features and gradients", features)
     rb = _rulebook_of(indice_pairs, indice_pair_num, features.shape[0], num_activate_out, inverse)
     table, flip = rb.in_table() if inverse else rb.out_table()
     f = features.contiguous()
@@ -617,7 +583,7 @@ def indice_group(features, indice_pairs, indice_pair_num, num_activate_out, inve
 def indice_group_backward(features, out_bp, indice_pairs, indice_pair_num, inverse=False, subm=False):
     """d_features[i] = sum_k out_bp[k, tab_in[k][i]] (reference ops.py:214-230); on 16-bit rows an fp32 sum over ascending k, rounded
     once."""
-    dt = _group_dtype(features, out_bp)
+    dt = G.one_dtype("sparse group", "features and gradients", features, out_bp)
     rb = _rulebook_of(indice_pairs, indice_pair_num, features.shape[0], out_bp.shape[1], inverse)
     table, flip = rb.out_table() if inverse else rb.in_table()
     g = out_bp.contiguous()

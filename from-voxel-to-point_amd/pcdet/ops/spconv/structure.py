@@ -4,9 +4,7 @@ import math
 import numpy as np
 import torch
 
-
-# 16-bit storage formats of the *_h entry points (FV2P_DT_F16 / FV2P_DT_BF16 of include/fv2p_ops.h)
-_DT16 = {torch.float16: 1, torch.bfloat16: 2}
+from .._glue import DT16 as _DT16
 
 
 def scatter_nd(indices, updates, shape):

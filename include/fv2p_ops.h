@@ -725,7 +725,7 @@ size_t fv2p_three_interpolate_stack_grad_h_ws_bytes(int n, int c, int m);
 int fv2p_three_interpolate_stack_grad_h(int n, int c, int m, const void* grad_out, const int* idx, const float* weight,
                                         void* grad_features, int dtype, void* ws, size_t ws_bytes, fv2p_stream_t stream);
 
-/* ---- Batch gather, grouping and interpolation on 16-bit feature rows (csrc/pointnet2_batch_h.hip) ---------------------------------
+/* ---- Batch gather, grouping and interpolation on 16-bit feature rows (csrc/pointnet2.hip) -----------------------------------------
  * What GatherOperation, GroupingOperation and ThreeInterpolate of pointnet2_batch/pointnet2_utils.py:46-215 (sampling_gpu.cu:10-98,
  * group_points_gpu.cu, interpolate_gpu.cu:76-160: float only in the reference) do on float16 / bfloat16 features; the PointnetSAModuleMSG
  * of IoUGuidedRoIHead (iouguided_roi_head.py:51-69, 266-278) and PointnetFPModule reach them.  Layouts are the fp32 batch ops':

@@ -1,4 +1,4 @@
-"""GPU: the batch gather / grouping / interpolation on float16 / bfloat16 features (csrc/pointnet2_batch_h.hip, the 16-bit form of
+"""GPU: the batch gather / grouping / interpolation on float16 / bfloat16 features (csrc/pointnet2.hip, the 16-bit form of
 csrc/scatter_add.hip), through the Python ops, the ext-module wrappers and the raw entry points.
 
   copies (gather, grouping forward): bit-equal to the fp32 op on the widened input, rounded back; an index outside [0, n) gives zeros;

@@ -1,5 +1,6 @@
 """Deterministic mode without a GPU: the switch, the new C-ABI entry points, and which entry point every wrapper reaches with the mode off
-(the existing one, unchanged) and on (its fixed-order *_gather form).  The library calls are recorded, not executed."""
+(the existing one, unchanged) and on (its fixed-order *_gather form), and that float16 / bfloat16 tensors reach the *_h one either way.
+The library calls are recorded, not executed."""
 import contextlib
 import types
 
@@ -137,3 +138,58 @@ def test_stack_interpolation_keeps_its_size_rule_when_off(recorded):
     for n in (100, ps.GATHER_GRAD_MIN_QUERIES):
         ps._interp_grad({"rows": 4, "idx": i, "weight": torch.zeros(1, 3)}, torch.zeros(n, 3))
     assert recorded == ["fv2p_three_interpolate_stack_grad", "fv2p_three_interpolate_stack_grad_gather"]
+
+
+def _half_sites(dt, queries=100):
+    """(existing entry point, a call on float16 / bfloat16 host tensors) for the ten pointnet2 gradient sites: the first ten of _wrappers()."""
+    from pcdet.ops.pointnet2.pointnet2_batch import pointnet2_utils as pb, pointnet2_batch_cuda as pbc
+    from pcdet.ops.pointnet2.pointnet2_stack import pointnet2_utils as ps, pointnet2_stack_cuda as psc
+    z = lambda *shape: torch.zeros(*shape, dtype=dt)
+    f, i = torch.zeros(2, 3, 4), torch.zeros(2, 3, 4, dtype=torch.int32)
+    cnt = torch.tensor([2], dtype=torch.int32)
+    qi, qw = torch.zeros(queries, 3, dtype=torch.int32), torch.zeros(queries, 3)
+    return [
+        ("fv2p_group_points_batch_grad", lambda: pb._group_grad({"shape": (2, 3, 4, 5, 6), "idx": i}, z(2, 3, 5, 6))),
+        ("fv2p_gather_points_grad", lambda: pb._gather_grad({"shape": (2, 3, 4, 5), "idx": i}, z(2, 3, 5))),
+        ("fv2p_three_interpolate_batch_grad", lambda: pb._interp_grad({"shape": (2, 3, 4, 5), "idx": i, "weight": f}, z(2, 3, 5))),
+        ("fv2p_group_points_batch_grad", lambda: pbc.group_points_grad_wrapper(2, 3, 4, 5, 6, z(2, 3, 5, 6), i, z(2, 3, 4))),
+        ("fv2p_gather_points_grad", lambda: pbc.gather_points_grad_wrapper(2, 3, 4, 5, z(2, 3, 5), i, z(2, 3, 4))),
+        ("fv2p_three_interpolate_batch_grad", lambda: pbc.three_interpolate_grad_wrapper(2, 3, 5, 4, z(2, 3, 5), i, f, z(2, 3, 4))),
+        ("fv2p_group_points_stack_grad", lambda: ps._group_grad({"dims": (1, 2, 3, 4, 5), "idx": i, "ic": cnt, "fc": cnt}, z(2, 3, 5))),
+        ("fv2p_three_interpolate_stack_grad", lambda: ps._interp_grad({"rows": 4, "idx": qi, "weight": qw}, z(queries, 3))),
+        ("fv2p_group_points_stack_grad", lambda: psc.group_points_grad_wrapper(1, 2, 3, 4, 5, z(2, 3, 5), i, cnt, cnt, z(4, 3))),
+        ("fv2p_three_interpolate_stack_grad", lambda: psc.three_interpolate_grad_wrapper(z(queries, 3), qi, qw, z(4, 3))),
+    ]
+
+
+@pytest.mark.parametrize("dt", [torch.float16, torch.bfloat16], ids=["float16", "bfloat16"])
+@pytest.mark.parametrize("k", range(10))
+def test_each_pointnet2_gradient_site_reaches_the_16_bit_entry_point_whatever_the_switch_says(recorded, k, dt):
+    from pcdet.ops.pointnet2.pointnet2_stack import pointnet2_utils as ps
+    sizes = (100, ps.GATHER_GRAD_MIN_QUERIES) if k in (7, 9) else (100,)   # the stack interpolation: below and at its size rule
+    for queries in sizes:
+        name, fn = _half_sites(dt, queries)[k]
+        for on in (False, True):
+            recorded.clear()
+            ops.set_deterministic(on)
+            fn()
+            assert recorded == [name + "_h"], (queries, on, recorded)
+
+
+@pytest.mark.parametrize("dt", [torch.float16, torch.bfloat16], ids=["float16", "bfloat16"])
+def test_stack_ext_wrappers_send_16_bit_tensors_to_the_16_bit_entry_points_and_refuse_mixed_dtypes(recorded, dt):
+    from pcdet.ops.pointnet2.pointnet2_stack import pointnet2_stack_cuda as psc
+    z = lambda *shape: torch.zeros(*shape, dtype=dt)
+    i, cnt = torch.zeros(2, 5, dtype=torch.int32), torch.tensor([2], dtype=torch.int32)
+    qi, qw = torch.zeros(6, 3, dtype=torch.int32), torch.zeros(6, 3)
+    assert psc.group_points_wrapper(1, 2, 3, 5, z(4, 3), cnt, i, cnt, z(2, 3, 5)) == 1
+    assert psc.three_interpolate_wrapper(z(4, 3), qi, qw, z(6, 3)) == 1
+    assert recorded == ["fv2p_group_points_stack_h", "fv2p_three_interpolate_stack_h"], recorded
+    recorded.clear()
+    for call in (lambda: psc.group_points_wrapper(1, 2, 3, 5, z(4, 3), cnt, i, cnt, torch.zeros(2, 3, 5)),
+                 lambda: psc.group_points_grad_wrapper(1, 2, 3, 4, 5, z(2, 3, 5), i, cnt, cnt, torch.zeros(4, 3)),
+                 lambda: psc.three_interpolate_wrapper(torch.zeros(4, 3), qi, qw, z(6, 3)),
+                 lambda: psc.three_interpolate_grad_wrapper(z(6, 3), qi, qw, torch.zeros(4, 3))):
+        with pytest.raises(TypeError, match="one dtype"):
+            call()
+    assert recorded == []

@@ -1,5 +1,5 @@
 """GPU: the sparse group and the stacked grouping / interpolation on float16 / bfloat16 rows (csrc/sparse_aux.hip, csrc/pointnet2.hip,
-the 16-bit form of csrc/scatter_add.hip), through the Python ops and the raw entry points.
+the 16-bit form of csrc/scatter_add.hip), through the Python ops, the ext-module wrappers and the raw entry points.
 
   copies (grouping forward, indice_group forward): bit-equal to the fp32 op on the widened input, rounded back;
   interpolation forward: integer features in [-8, 8] with weights from {0, 1/4, 1/2, 1} are exact; random inputs satisfy
@@ -261,6 +261,43 @@ def test_grouping_gradient(gpu, dtype, c):
                 nat.set_deterministic(False)
             assert feats.grad.dtype == dtype
             assert np.array_equal(bits(feats.grad), bits(_group_grad_raw(g, safe, ic, fc, n, dtype, gpu)))
+
+
+# ---- the ext-module wrappers -------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("c", [8, 5])                                        # the 16-byte path and the element path
+@pytest.mark.parametrize("dtype", DTYPES, ids=dtype_id)
+def test_ext_wrappers_take_16_bit_tensors(gpu, dtype, c):
+    """pointnet2_stack_cuda on 16-bit buffers: the forward wrappers fill the caller's buffer with the bits of the Python ops, the gradient
+    wrappers accumulate the autograd route's gradient into it once, switch off and on; source and destination of two dtypes raise."""
+    from pcdet.ops.pointnet2.pointnet2_stack import pointnet2_stack_cuda as ext
+    rng = np.random.default_rng(500 + c)
+    n, m = GROUP["n"], GROUP["m"]
+    gidx, fc, ic, iidx = _i(GROUP["idx"], gpu), _i(GROUP["fc"], gpu), _i(GROUP["ic"], gpu), _i(INTERP["idx"], gpu)
+    w = torch.from_numpy(rng.random((INTERP["n"], 3)).astype(np.float32)).to(gpu)
+    cases = [(n, lambda f: pu.grouping_operation(f, fc, gidx, ic), lambda f, out: ext.group_points_wrapper(2, m, c, S, f, fc, gidx, ic, out),
+              lambda g, buf: ext.group_points_grad_wrapper(2, m, c, n, S, g, gidx, ic, fc, buf)),
+             (INTERP["m"], lambda f: pu.three_interpolate(f, iidx, w), lambda f, out: ext.three_interpolate_wrapper(f, iidx, w, out),
+              lambda g, buf: ext.three_interpolate_grad_wrapper(g, iidx, w, buf))]
+    for rows, apply, fwd, bwd in cases:
+        f = _t(rng.standard_normal((rows, c)), dtype, gpu).requires_grad_(True)
+        out = apply(f)
+        g = _t(rng.standard_normal(tuple(out.shape)), dtype, gpu)
+        out.backward(g)
+        mine = torch.full_like(out, float("nan"))
+        assert fwd(f.detach(), mine) == 1 and np.array_equal(bits(mine), bits(out))
+        start = _t(rng.integers(-4, 5, size=(rows, c)), dtype, gpu)
+        for det in (False, True):                                           # the caller's buffer is accumulated into, once
+            nat.set_deterministic(det)
+            try:
+                buf = start.clone()
+                assert bwd(g, buf) == 1
+            finally:
+                nat.set_deterministic(False)
+            assert bool((f.grad != 0).any()) and np.array_equal(bits(buf), bits(start + f.grad))
+        with pytest.raises(TypeError, match="one dtype"):
+            fwd(f.detach(), torch.empty(tuple(out.shape), device=gpu))
+        with pytest.raises(TypeError, match="one dtype"):
+            bwd(g, torch.zeros((rows, c), device=gpu))
 
 
 # ---- dtypes that are not served, and float32 left alone ---------------------------------------------------------------------------------

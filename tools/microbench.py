@@ -572,7 +572,7 @@ def exit16(out_path=None):
 
 
 def batch16(out_path=None):
-    """The batched pointnet2 ops on 16-bit features (csrc/pointnet2_batch_h.hip) at the shapes FV2P gives them: the RoI head's grid
+    """The batched pointnet2 ops on 16-bit features (csrc/pointnet2.hip) at the shapes FV2P gives them: the RoI head's grid
     grouping (384 RoIs x 128 channels x 512 points, 216 grid points x 32 / 16 samples), the Voxel-to-Point decoder's interpolation
     (35 000 known rows x 64 channels onto 16 384 queries: the batch op on (1, C, M) and the top3_interpolate route on (M, C) rows,
     three_nn included) and a gather (3, 128, 16384) -> 4096.  Forward (no_grad) and forward + backward, four routes on the same data:
