@@ -11,6 +11,7 @@
 // Backward (gradient of the map): the transposed scatter with float atomics (torch's index backward is an unordered
 // accumulation as well), then the transpose back.
 #include "common.hpp"
+#include <type_traits>
 #include "dt16.hpp"
 
 namespace fv2p {
@@ -262,6 +263,86 @@ static int launch_transpose_h(const u16* in, int batch, int rows, long long cols
   return 0;
 }
 
+// transpose_k with the conversion at the load (WIDEN: 16-bit in, fp32 out) or at the store (fp32 in, 16-bit out, one rounding to nearest
+// even): the layout copy and the dtype copy of the DCN backward's entry and exit in one pass.  Same tile, same 4-element accesses
+// (8 bytes on the 16-bit side, 16 on the fp32 side) where the sizes and the alignment allow.
+template <class T, bool WIDEN>
+__global__ __launch_bounds__(256) void transpose_cvt_k(const void* __restrict__ in_, int rows, long long cols, void* __restrict__ out_) {
+  using TI = std::conditional_t<WIDEN, u16, float>;
+  using TO = std::conditional_t<WIDEN, float, u16>;
+  __shared__ float tile[64][65];
+  const long long b = blockIdx.z;
+  const TI* src = static_cast<const TI*>(in_) + b * rows * cols;
+  TO* dst = static_cast<TO*>(out_) + b * rows * cols;
+  const long long c0 = static_cast<long long>(blockIdx.x) * 64;
+  const int r0 = blockIdx.y * 64;
+  const int q = threadIdx.x & 15, t = threadIdx.x >> 4;   // 16 quads x 16
+  const bool vec_in = (cols & 3) == 0 && (reinterpret_cast<uintptr_t>(in_) & (4 * sizeof(TI) - 1)) == 0;
+  const bool vec_out = (rows & 3) == 0 && (reinterpret_cast<uintptr_t>(out_) & (4 * sizeof(TO) - 1)) == 0;
+#pragma unroll
+  for (int j = 0; j < 64; j += 16) {
+    const int r = r0 + t + j;
+    const long long cc = c0 + 4 * q;
+    float v[4] = {0.f, 0.f, 0.f, 0.f};
+    if (r < rows) {
+      const TI* p = src + static_cast<long long>(r) * cols + cc;
+      if constexpr (WIDEN) {
+        if (vec_in && cc + 3 < cols) {
+          const uint2 f = *reinterpret_cast<const uint2*>(p);
+          v[0] = T::widen(static_cast<u16>(f.x & 0xffffu)); v[1] = T::widen(static_cast<u16>(f.x >> 16));
+          v[2] = T::widen(static_cast<u16>(f.y & 0xffffu)); v[3] = T::widen(static_cast<u16>(f.y >> 16));
+        } else {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) if (cc + e < cols) v[e] = T::widen(p[e]);
+        }
+      } else {
+        if (vec_in && cc + 3 < cols) { const float4 f = *reinterpret_cast<const float4*>(p); v[0] = f.x; v[1] = f.y; v[2] = f.z; v[3] = f.w; }
+        else {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) if (cc + e < cols) v[e] = p[e];
+        }
+      }
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) tile[t + j][4 * q + e] = v[e];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int j = 0; j < 64; j += 16) {
+    const long long cc = c0 + t + j;
+    const int r = r0 + 4 * q;
+    if (cc >= cols) continue;
+    float v[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[e] = tile[4 * q + e][t + j];
+    TO* p = dst + cc * rows + r;
+    if constexpr (WIDEN) {
+      if (vec_out && r + 3 < rows) *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
+      else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) if (r + e < rows) p[e] = v[e];
+      }
+    } else {
+      if (vec_out && r + 3 < rows)
+        *reinterpret_cast<uint2*>(p) = make_uint2(static_cast<unsigned>(T::round(v[0])) | (static_cast<unsigned>(T::round(v[1])) << 16),
+                                                  static_cast<unsigned>(T::round(v[2])) | (static_cast<unsigned>(T::round(v[3])) << 16));
+      else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) if (r + e < rows) p[e] = T::round(v[e]);
+      }
+    }
+  }
+}
+
+template <bool WIDEN>
+static int launch_transpose_cvt(const void* in, int dtype, int batch, int rows, long long cols, void* out, hipStream_t stream) {
+  FV2P_REQUIRE(batch <= 65535 && ceil_div(rows, 64) <= 65535, FV2P_ELIMIT, "transpose: batch or row count too large");
+  const dim3 grid(static_cast<unsigned>(ceil_div(cols, 64)), static_cast<unsigned>(ceil_div(rows, 64)), static_cast<unsigned>(batch));
+  if (dtype == FV2P_DT_F16) hipLaunchKernelGGL((transpose_cvt_k<H16, WIDEN>), grid, dim3(256), 0, stream, in, rows, cols, out);
+  else hipLaunchKernelGGL((transpose_cvt_k<B16, WIDEN>), grid, dim3(256), 0, stream, in, rows, cols, out);
+  return 0;
+}
+
 }  // namespace fv2p
 
 using namespace fv2p;
@@ -433,6 +514,30 @@ extern "C" int fv2p_transpose_batched_h(const void* in, int batch, int64_t rows,
   FV2P_REQUIRE(in && out && in != out, FV2P_EINVAL, "transpose_batched_h: null or aliased pointers");
   FV2P_REQUIRE(rows < (1ll << 31) && ceil_div(cols, 64) < (1ll << 31), FV2P_ELIMIT, "transpose_batched_h: too large");
   if (int rc = launch_transpose_h(static_cast<const u16*>(in), batch, static_cast<int>(rows), cols, static_cast<u16*>(out), static_cast<hipStream_t>(stream_))) return rc;
+  FV2P_LAUNCH_CHECK();
+  return 0;
+}
+
+// fv2p_transpose_batched of a float16 / bfloat16 source widened on the way (the bits of .float() then fv2p_transpose_batched) ...
+extern "C" int fv2p_transpose_batched_widen(const void* in, int dtype, int batch, int64_t rows, int64_t cols, float* out, fv2p_stream_t stream_) {
+  FV2P_DT16_OK("transpose_batched_widen", dtype);
+  FV2P_REQUIRE(batch >= 0 && rows >= 0 && cols >= 0, FV2P_EINVAL, "transpose_batched_widen: bad sizes");
+  if (batch == 0 || rows == 0 || cols == 0) return 0;
+  FV2P_REQUIRE(in && out && in != static_cast<const void*>(out), FV2P_EINVAL, "transpose_batched_widen: null or aliased pointers");
+  FV2P_REQUIRE(rows < (1ll << 31) && ceil_div(cols, 64) < (1ll << 31), FV2P_ELIMIT, "transpose_batched_widen: too large");
+  if (int rc = launch_transpose_cvt<true>(in, dtype, batch, static_cast<int>(rows), cols, out, static_cast<hipStream_t>(stream_))) return rc;
+  FV2P_LAUNCH_CHECK();
+  return 0;
+}
+
+// ... and of an fp32 source rounded once at the store (the bits of fv2p_transpose_batched then .to(dtype))
+extern "C" int fv2p_transpose_batched_round(const float* in, int batch, int64_t rows, int64_t cols, void* out, int dtype, fv2p_stream_t stream_) {
+  FV2P_DT16_OK("transpose_batched_round", dtype);
+  FV2P_REQUIRE(batch >= 0 && rows >= 0 && cols >= 0, FV2P_EINVAL, "transpose_batched_round: bad sizes");
+  if (batch == 0 || rows == 0 || cols == 0) return 0;
+  FV2P_REQUIRE(in && out && static_cast<const void*>(in) != out, FV2P_EINVAL, "transpose_batched_round: null or aliased pointers");
+  FV2P_REQUIRE(rows < (1ll << 31) && ceil_div(cols, 64) < (1ll << 31), FV2P_ELIMIT, "transpose_batched_round: too large");
+  if (int rc = launch_transpose_cvt<false>(in, dtype, batch, static_cast<int>(rows), cols, out, static_cast<hipStream_t>(stream_))) return rc;
   FV2P_LAUNCH_CHECK();
   return 0;
 }

@@ -18,19 +18,13 @@
 // keep the reference layout [B, dg*2*K, Ho, Wo] / [B, dg*K, Ho, Wo] with (2*(i*kw+j), +1) = (dh, dw).  Out-of-map corners are read at the
 // nearest in-map pixel with weight 0 (loads are unconditional).
 #include "common.hpp"
+#include "dcn_common.hpp"
 #include <stdlib.h>
 #include <stdio.h>
 #include <algorithm>
 #include <type_traits>
 
 namespace fv2p {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-// G: convolution groups - input channels [g*Cin/G, (g+1)*Cin/G) feed output channels [g*Cout/G, (g+1)*Cout/G) only
-struct DcnGeom {
-  int B, H, W, Cin, Cout, Ho, Wo, kh, kw, sh, sw, ph, pw, dh, dw, dg, G;
-};
 
 // out = (accumulate ? out : 0) + partial[0] + partial[1] + ...: a fixed order, also across the batch chunks of one call
 __global__ void dcn_reduce_k(const float* __restrict__ partial, int chunks, long long per_chunk, float* __restrict__ out, int accumulate) {
@@ -41,53 +35,6 @@ __global__ void dcn_reduce_k(const float* __restrict__ partial, int chunks, long
   out[t] = s;
 }
 
-
-// Workgroup b of a launch runs on XCD b % 8, each XCD with an L2 of its own.  Handing out tiles in launch order gives every XCD every
-// eighth tile: the eight L2s then all hold the same band of the map (a tile's bilinear samples reach into its neighbours' pixels) and
-// each line is fetched from the fabric eight times - 815 MB of L2 fills for 83 MB of input at [4,128,200,176], rocprofv3 FETCH_SIZE.
-// XCD-major order gives every XCD one contiguous eighth of the tiles instead.  (tile, sub): sub is the fast index (column block / share).
-__device__ __forceinline__ void xcd_tile(int n_sub, long long& tile, int& sub) {
-  const long long total = gridDim.x, b = blockIdx.x;
-  const long long x = b & 7, slot = b >> 3;
-  const long long lp = x * (total >> 3) + (x < (total & 7) ? x : (total & 7)) + slot;
-  tile = lp / n_sub;
-  sub = static_cast<int>(lp % n_sub);
-}
-
-__device__ __forceinline__ void glds16(const float* gsrc, float* lds_dst) {
-  const unsigned dst = __builtin_amdgcn_readfirstlane(static_cast<unsigned>(reinterpret_cast<uintptr_t>(lds_dst)));
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(gsrc), "s"(dst) : "memory");
-}
-
-struct Corner4 {
-  unsigned o[4];
-  float w[4];
-  float m;
-};
-
-__device__ __forceinline__ void make_corners(const DcnGeom& g, bool live, int b, float h_im, float w_im, float m, unsigned lane_bytes, Corner4& t) {
-  const bool valid = live && (h_im > -1.f && w_im > -1.f && h_im < static_cast<float>(g.H) && w_im < static_cast<float>(g.W));
-  const float hf = floorf(h_im), wf = floorf(w_im);
-  const int h_low = static_cast<int>(hf), w_low = static_cast<int>(wf);
-  const int h_high = h_low + 1, w_high = w_low + 1;
-  const float lh = h_im - hf, lw = w_im - wf, hh = 1.f - lh, hw = 1.f - lw;
-  const bool hl = valid && h_low >= 0, hhi = valid && h_high <= g.H - 1, wl = w_low >= 0, whi = w_high <= g.W - 1;
-  t.w[0] = (hl && wl) ? hh * hw : 0.f;
-  t.w[1] = (hl && whi) ? hh * lw : 0.f;
-  t.w[2] = (hhi && wl) ? lh * hw : 0.f;
-  t.w[3] = (hhi && whi) ? lh * lw : 0.f;
-  t.m = valid ? m : 0.f;
-  const int h0 = min(max(h_low, 0), g.H - 1), h1 = min(max(h_high, 0), g.H - 1);
-  const int w0 = min(max(w_low, 0), g.W - 1), w1 = min(max(w_high, 0), g.W - 1);
-  const unsigned row0 = static_cast<unsigned>((b * g.H + h0) * g.W), row1 = static_cast<unsigned>((b * g.H + h1) * g.W);
-  const unsigned pitch = static_cast<unsigned>(g.Cin) * 4u;
-  t.o[0] = (row0 + w0) * pitch + lane_bytes;
-  t.o[1] = (row0 + w1) * pitch + lane_bytes;
-  t.o[2] = (row1 + w0) * pitch + lane_bytes;
-  t.o[3] = (row1 + w1) * pitch + lane_bytes;
-}
 
 __device__ __forceinline__ f32x4 ldx4(const char* base, unsigned off) { return *reinterpret_cast<const f32x4*>(base + off); }
 
@@ -989,26 +936,10 @@ static void dcn_fwd_launch(const DcnGeom& g, const float* x, const float* wt_oc,
     hipLaunchKernelGGL((dcn_fwd_k<NB, 1>), grid, dim3(256), 2 * NB * 256 * sizeof(float), stream, g, x, wt_oc, bias, offset, mask, y, 0ll, n_sub);
 }
 
-// Samples per launch sequence: the kernels address x, the column gradients and the sample lists with 32-bit offsets, so a call is
-// cut into chunks of whole samples that stay below those limits (the reference's im2col_step chunking, modulated_deform_conv_cuda.cu:
-// 85-118, serves the same purpose) - and, for the backward, below kColgCapBytes of column gradients, which bounds the workspace
-// whatever the batch.  Per-pixel arithmetic does not depend on the chunking; the weight gradient adds the chunks in ascending order.
+// Samples per launch sequence: the rule of dcn_common.hpp (dcn_chunk_samples) with this file's cap on a chunk's column gradients.
 constexpr long long kColgCapBytes = 3ll << 29;   // 1.5 GiB: the MGAF head at batch 4 (1.30 GB) is still one chunk
 static long long g_colg_cap = kColgCapBytes;     // fv2p_dcn_set_colg_cap (tests: several chunks at shapes the oracle can answer)
-static int dcn_chunk_samples(const DcnGeom& g, bool backward) {
-  const long long K = static_cast<long long>(g.kh) * g.kw;
-  const long long x_bytes = static_cast<long long>(g.H) * g.W * g.Cin * 4;
-  const long long pix = static_cast<long long>(g.Ho) * g.Wo;
-  long long bs = g.B > 0 ? g.B : 1;
-  bs = std::min(bs, ((1ll << 32) - 1) / std::max(x_bytes, 1ll));
-  bs = std::min(bs, ((1ll << 32) - 1) / std::max(pix * std::max<long long>(g.Cout, g.dg * 2 * K) * 4, 1ll));   // y / dy, offset
-  if (backward) {
-    bs = std::min(bs, std::max(1ll, g_colg_cap / std::max(pix * K * g.Cin * 4, 1ll)));   // the cap is a preference: never below one sample
-    bs = std::min(bs, ((1ll << 32) - 1) / std::max(pix * K * g.Cin * 4, 1ll));             // ... the 32-bit limit on its column gradients is hard
-    bs = std::min(bs, ((1ll << 31) - 1) / std::max(pix * g.dg * K, 1ll));
-  }
-  return static_cast<int>(bs);   // 0: one sample alone is above a limit
-}
+static int dcn_chunk_samples(const DcnGeom& g, bool backward) { return dcn_chunk_samples(g, backward, g_colg_cap, 4); }
 
 extern "C" int fv2p_dcn_set_forward_order(int order) {
   FV2P_REQUIRE(order >= -1 && order <= 1, FV2P_EINVAL, "dcn_set_forward_order: -1 (by shape), 0 (tap outer) or 1 (tap inner)");

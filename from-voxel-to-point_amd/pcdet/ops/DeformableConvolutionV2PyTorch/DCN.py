@@ -3,12 +3,20 @@ shim over libfv2p_ops: same six function names and positional arguments.
 
 Two routes.  groups == 1, Cout <= 256 and Cin / deformable_group a multiple of 16 (every reference config, the MGAF head) reach
 fv2p_dcn_forward / fv2p_dcn_backward as they always did.  Every other geometry the reference accepts (groups > 1, channel tails,
-Cout > 256) reaches fv2p_dcn_*_grouped, with the input channels zero-padded on the host (_tail_pad)."""
+Cout > 256) reaches fv2p_dcn_*_grouped, with the input channels zero-padded on the host (_tail_pad).
+
+float16 / bfloat16 maps: the forward of groups == 1 with Cin / deformable_group a multiple of 16 reaches fv2p_dcn_forward_h, the same
+implicit GEMM on the 16-bit MFMA with no fp32 copy of any map (NATIVE_16BIT, on by default; off = the fp32 route on widened copies, as
+before).  The backward keeps the fp32 kernels and reaches them through fv2p_transpose_batched_widen / _round: the layout copy and the
+dtype copy of x, grad_output and grad_input are one pass each."""
 import math
 
 import torch
 
 import fv2p_native as _nat
+
+NATIVE_16BIT = True    # float16 / bfloat16 forward on fv2p_dcn_forward_h where it serves the geometry; False: the fp32 kernels on widened copies
+_DT16 = {torch.float16: 1, torch.bfloat16: 2}   # FV2P_DT_F16 / FV2P_DT_BF16
 
 
 def _geom(input, weight, kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w, group, deformable_group):
@@ -101,6 +109,64 @@ def _to_nchw(t_nhwc):
     return out
 
 
+def _to_nhwc_f32(t):
+    """_to_nhwc with the widening inside the copy: a contiguous 16-bit [B, C, H, W] -> contiguous fp32 [B, H, W, C] in one pass,
+    the bits of t.float() followed by the transpose."""
+    if t.dtype in _DT16 and t.is_cuda and t.is_contiguous() and t.numel() > 0 and not t.permute(0, 2, 3, 1).is_contiguous():
+        B, C, H, W = t.shape
+        out = torch.empty((B, H, W, C), dtype=torch.float32, device=t.device)
+        with _nat.device_guard(t.device):
+            _nat.call("fv2p_transpose_batched_widen", t, _DT16[t.dtype], B, C, H * W, out, _nat.stream())
+        return out
+    return _to_nhwc(t)
+
+
+def _to_nchw_as(t_nhwc, dtype):
+    """_to_nchw(t).to(dtype) with the rounding inside the copy for a 16-bit dtype: fp32 [B, H, W, C] -> [B, C, H, W] in one pass."""
+    if dtype in _DT16 and t_nhwc.is_cuda and t_nhwc.numel() > 0:
+        B, H, W, C = t_nhwc.shape
+        out = torch.empty((B, C, H, W), dtype=dtype, device=t_nhwc.device)
+        with _nat.device_guard(t_nhwc.device):
+            _nat.call("fv2p_transpose_batched_round", t_nhwc, B, H * W, C, out, _DT16[dtype], _nat.stream())
+        return out
+    return _to_nchw(t_nhwc).to(dtype)
+
+
+def _native_16bit(input, weight, group, deformable_group):
+    """The calls fv2p_dcn_forward_h takes: a float16 / bfloat16 map on the GPU, no conv groups, a geometry the kernel serves."""
+    if not (NATIVE_16BIT and input.dtype in _DT16 and input.is_cuda and group == 1 and deformable_group >= 1):
+        return False
+    return bool(_nat.lib().fv2p_dcn_forward_h_supported(input.shape[1], weight.shape[0], deformable_group))
+
+
+def _forward_16bit(input, weight, bias, offset, mask, g):
+    """fv2p_dcn_forward_h: x, the weight and y in input.dtype, no .float() of any map.  The weight (fp32 master weights under
+    autocast) is rounded once while it is permuted; offset and mask go as they are in input.dtype or float32."""
+    B, H, W, C, Cout, Ho, Wo = g[:7]
+    dt, dev = input.dtype, input.device
+    x = input.permute(0, 2, 3, 1)
+    if B * H * W > 0 and not x.is_contiguous():
+        if input.is_contiguous():
+            x = torch.empty((B, H, W, C), dtype=dt, device=dev)
+            with _nat.device_guard(dev):
+                _nat.call("fv2p_transpose_batched_h", input, B, C, H * W, x, _nat.stream())
+        else:
+            x = x.contiguous()
+    wt_oc = _wt_oc(weight if weight.dtype == dt else weight.to(dt))
+    om = offset.dtype if offset.dtype == mask.dtype and offset.dtype in (dt, torch.float32) else torch.float32
+    off = (offset if offset.dtype == om else offset.to(om)).contiguous()
+    msk = (mask if mask.dtype == om else mask.to(om)).contiguous()
+    y = torch.empty((B, Ho, Wo, Cout), dtype=dt, device=dev)
+    with _nat.device_guard(dev):
+        _nat.call("fv2p_dcn_forward_h", x, wt_oc, bias.float().contiguous() if bias is not None else None, off, msk, *g, y,
+                  _DT16[dt], 0 if om == torch.float32 else _DT16[dt], _nat.stream())
+        if _channels_last(input) or y.numel() == 0:
+            return y.permute(0, 3, 1, 2) if _channels_last(input) else y.permute(0, 3, 1, 2).contiguous()
+        out = torch.empty((B, Cout, Ho, Wo), dtype=dt, device=dev)
+        _nat.call("fv2p_transpose_batched_h", y, B, Ho * Wo, Cout, out, _nat.stream())
+    return out
+
+
 def _wt(weight):
     """[Cout, Cin, kh, kw] -> [kh*kw][Cin][Cout]: the backward kernels' layout (output channels contiguous)."""
     cout, cin, kh, kw = weight.shape
@@ -184,6 +250,9 @@ def modulated_deform_conv_forward(input, weight, bias, offset, mask, kernel_h, k
     """-> output [B, Cout, Ho, Wo] (contiguous NCHW, as modulated_deform_conv_cuda.cu:118). im2col_step is accepted and
     irrelevant: the forward has no columns buffer to chunk.  A channels-last `input` is taken as it is and the output is channels-last
     too (the kernels' own layout: no copy on either side); grad_input follows the input's format likewise."""
+    if _native_16bit(input, weight, group, deformable_group):
+        g = _geom(input, weight, kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w, group, deformable_group)
+        return _forward_16bit(input, weight, bias, offset, mask, g)
     if not _plain(input, weight, group, deformable_group):
         return _grouped_forward(input, weight, bias, offset, mask, kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w, dilation_h,
                                 dilation_w, group, deformable_group)
@@ -206,8 +275,8 @@ def modulated_deform_conv_backward(input, weight, bias, offset, mask, grad_outpu
     g = _geom(input, weight, kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w, group, deformable_group)
     B, H, W, C, Cout, Ho, Wo = g[:7]
     dev = input.device
-    x = _to_nhwc(input)
-    dy = _to_nhwc(grad_output).view(B * Ho * Wo, Cout)
+    x = _to_nhwc_f32(input)
+    dy = _to_nhwc_f32(grad_output).view(B * Ho * Wo, Cout)
     wt = _wt(weight.float())
     pad = (-Cout) % 4            # the kernels read output channels four at a time: pad with zero columns
     if pad:
@@ -223,7 +292,7 @@ def modulated_deform_conv_backward(input, weight, bias, offset, mask, grad_outpu
         ws = _nat.workspace(nb, dev)
         _nat.call("fv2p_dcn_backward", x, wt, offset.float().contiguous(), mask.float().contiguous(), dy, *g, dx, doff,
                   dmask, dwt, ws, ws.numel(), _nat.stream())
-    grad_input = dx.permute(0, 3, 1, 2) if _channels_last(input) else _to_nchw(dx)
+    grad_input = dx.permute(0, 3, 1, 2) if _channels_last(input) else _to_nchw_as(dx, input.dtype if input.dtype in _DT16 else dx.dtype)
     grad_weight = dwt[:, :, :Cout].reshape(kernel_h, kernel_w, C, Cout).permute(3, 2, 0, 1).contiguous()
     grad_bias = dy[:, :Cout].sum(dim=0)
     return [grad_input, doff, dmask, grad_weight, grad_bias]
@@ -233,7 +302,8 @@ def deform_conv_forward(input, weight, bias, offset, kernel_h, kernel_w, stride_
                         group, deformable_group, im2col_step):
     """DCNv1 = DCNv2 with an all-ones modulation mask (deform_im2col_cuda.cuh:127-190 vs modulated_*:127-194)."""
     B, _, Ho, Wo = offset.shape
-    mask = torch.ones((B, deformable_group * kernel_h * kernel_w, Ho, Wo), dtype=torch.float32, device=input.device)
+    mask = torch.ones((B, deformable_group * kernel_h * kernel_w, Ho, Wo), device=input.device,
+                      dtype=input.dtype if _native_16bit(input, weight, group, deformable_group) else torch.float32)
     return modulated_deform_conv_forward(input, weight, bias, offset, mask, kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w,
                                          dilation_h, dilation_w, group, deformable_group, im2col_step)
 

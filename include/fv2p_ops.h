@@ -852,6 +852,24 @@ int fv2p_dcn_backward_grouped(const float* x_nhwc, const float* wt, const float*
                               int deformable_group, int group, float* dx_nhwc, float* doffset, float* dmask, float* dwt,
                               void* ws, size_t ws_bytes, fv2p_stream_t stream);
 
+/* The forward on float16 / bfloat16 maps (csrc/dcn_h.hip): the same implicit GEMM on v_mfma_f32_16x16x32_{f16,bf16}, no fp32 copy of
+ * any map.  `dtype` (FV2P_DT_F16 / FV2P_DT_BF16) names the format of x_nhwc [B,H,W,Cin], wt_oc [kh*kw][Cout][Cin] and y_nhwc
+ * [B*Ho*Wo][Cout]; bias stays fp32 (Cout floats, may be null); offset and mask, in the reference layouts, are fp32 (om_dtype 0) or in
+ * the call's format (om_dtype == dtype) and are widened on load, positions are always formed in fp32.  The dtype / om_dtype checks come
+ * first: any other value returns FV2P_EINVAL before any HIP call.  Arithmetic: a sample is w0 v0 + w1 v1 + w2 v2 + w3 v3 of the
+ * widened corner values in fp32 (the fp32 kernel's fmaf chain), times the mask, rounded to nearest even once into the MFMA operand;
+ * fp32 accumulators in the fixed step order (tap, deformable group, 32-channel chunk); bias added in fp32; one rounding at the store.
+ * No atomics: two runs give the same bits.  Geometry: groups == 1, Cin / deformable_group a multiple of 16 (a group 16 mod 32 wide
+ * ends in a 32-step whose upper half is zero in both operands), any Cout >= 1, any stride / padding / dilation / kernel size of
+ * fv2p_dcn_forward; FV2P_ELIMIT otherwise - fv2p_dcn_forward_h_supported (pure host, no HIP call) answers 1 / 0 for it.  x_nhwc and
+ * wt_oc must be 16-byte aligned.  Nothing outside x, wt_oc, offset or mask is read.  Batches are cut into chunks of whole samples
+ * as above; a zero-sized call returns 0 without a launch; the work runs on `stream`, takes no workspace and allocates nothing. */
+int fv2p_dcn_forward_h(const void* x_nhwc, const void* wt_oc, const float* bias, const void* offset, const void* mask,
+                       int batch, int height, int width, int c_in, int c_out, int h_out, int w_out, int kh, int kw,
+                       int sh, int sw, int ph, int pw, int dh, int dw, int deformable_group,
+                       void* y_nhwc, int dtype, int om_dtype, fv2p_stream_t stream);
+int fv2p_dcn_forward_h_supported(int c_in, int c_out, int deformable_group);
+
 /* Layout copies around the NHWC entry points above (and fv2p_bev_interp_*): in [batch][rows][cols] -> out [batch][cols][rows],
  * e.g. NCHW -> NHWC with rows = C, cols = H*W.  The reference does the same copies with at::permute + contiguous
  * (modulated_deform_conv_cuda.cu:78,118). */
@@ -859,6 +877,12 @@ int fv2p_transpose_batched(const float* in, int batch, int64_t rows, int64_t col
 /* The same copy on 16-bit elements.  Bit patterns are moved, so one entry point serves float16 and bfloat16 and takes no dtype;
  * 16-byte accesses of 8 elements on a side whose extent is a multiple of 8 and whose pointer is 16-byte aligned. */
 int fv2p_transpose_batched_h(const void* in, int batch, int64_t rows, int64_t cols, void* out, fv2p_stream_t stream);
+/* The layout copy and the dtype copy in one pass (`dtype`: FV2P_DT_F16 / FV2P_DT_BF16, the format of the 16-bit side; any other value
+ * returns FV2P_EINVAL): _widen reads 16-bit elements and writes fp32, the bits of .float() followed by fv2p_transpose_batched; _round
+ * reads fp32 and rounds to nearest even once at the store, the bits of fv2p_transpose_batched followed by .to(dtype).  They carry the
+ * float16 / bfloat16 tensors of the DCN backward to and from its fp32 kernels. */
+int fv2p_transpose_batched_widen(const void* in, int dtype, int batch, int64_t rows, int64_t cols, float* out, fv2p_stream_t stream);
+int fv2p_transpose_batched_round(const float* in, int batch, int64_t rows, int64_t cols, void* out, int dtype, fv2p_stream_t stream);
 
 /* ---- A14: deformable position-sensitive RoI pooling ----------------------------------------------
  * Replace DCN.deform_psroi_pooling_forward / _backward

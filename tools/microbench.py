@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Per-kernel timings on one GPU (events on the launch stream). Not part of the product or of bench.py; used to
-iterate on kernel variants:  python tools/microbench.py [conv|conv16|amp16|bn16|bn2d|bn2d16|bev16|exit16|batch16|dcn|fps|voxel|nms|all]"""
+iterate on kernel variants:  python tools/microbench.py [conv|conv16|amp16|bn16|bn2d|bn2d16|bev16|exit16|batch16|dcn|dcn16|fps|voxel|nms|all]"""
 import os
 import sys
 import time
@@ -1037,6 +1037,62 @@ def bev16(out_path=None):
     _write(lines, out_path)
 
 
+def dcn16(out_path=None):
+    """ModulatedDeformConv 3 x 3 on 16-bit maps, forward and forward + backward.  native: fv2p_dcn_forward_h (DCN.NATIVE_16BIT, the
+    default); widen: the route before it on the same 16-bit tensors (NATIVE_16BIT = False: .float() copies around the fp32 kernels); f32:
+    the fp32 op on fp32 tensors.  The backward runs the fp32 kernels on every route.  Alternating windows as in bn2d16."""
+    from pcdet.ops.DeformableConvolutionV2PyTorch import DCN
+    from pcdet.ops.DeformableConvolutionV2PyTorch.modules.modulated_deform_conv import ModulatedDeformConv
+    dev = torch.device("cuda:0")
+    ROUNDS, REPS = 7, 5
+    lines = ["ModulatedDeformConv 3x3 (Cout = Cin) on 16-bit maps, us per call: median of %d windows of %d calls, +- half the range.  native: "
+             "fv2p_dcn_forward_h; widen: NATIVE_16BIT = False on the same 16-bit tensors; f32: the fp32 op on fp32 tensors" % (ROUNDS, REPS),
+             "%-22s %-3s %-9s %-5s %-16s %-16s %-16s %-12s %-10s" % ("map", "dg", "dtype", "leg", "native", "widen", "f32", "native/widen", "native/f32")]
+    for shape, dg in (((4, 128, 200, 176), 1), ((4, 256, 200, 176), 4), ((4, 256, 100, 88), 4), ((4, 256, 50, 44), 4)):
+        B, C, H, W = shape
+        for dt in (torch.float16, torch.bfloat16):
+            torch.manual_seed(0)
+            m32 = ModulatedDeformConv(C, C, 3, 1, 1, 1, 1, dg, 64, bias=True).to(dev)
+            m16 = ModulatedDeformConv(C, C, 3, 1, 1, 1, 1, dg, 64, bias=True).to(dev)
+            m16.load_state_dict(m32.state_dict())
+            m16 = m16.to(dt)
+            x32 = torch.randn(shape, device=dev).requires_grad_(True)
+            o32 = (torch.randn((B, dg * 18, H, W), device=dev) * 1.5).requires_grad_(True)
+            k32 = torch.rand((B, dg * 9, H, W), device=dev).requires_grad_(True)
+            g32 = torch.randn(shape, device=dev)
+            x16, o16, k16 = (t.detach().to(dt).requires_grad_(True) for t in (x32, o32, k32))
+            g16 = g32.to(dt)
+            fwd, both = {}, {}
+            for name, m, x, o, k, g, flag in (("native", m16, x16, o16, k16, g16, True), ("widen", m16, x16, o16, k16, g16, False),
+                                              ("f32", m32, x32, o32, k32, g32, True)):
+                def f(m=m, x=x, o=o, k=k, flag=flag):
+                    DCN.NATIVE_16BIT = flag
+                    try:
+                        return m(x, o, k)
+                    finally:
+                        DCN.NATIVE_16BIT = True
+
+                def fn_fwd(f=f):
+                    with torch.no_grad():
+                        f()
+
+                def fn_both(f=f, m=m, x=x, o=o, k=k, g=g):
+                    f().backward(g)
+                    x.grad = o.grad = k.grad = None
+                    m.weight.grad = m.bias.grad = None
+                fwd[name], both[name] = fn_fwd, fn_both
+            for leg, routes in (("fwd", fwd), ("f+b", both)):
+                t = _windows(routes, ROUNDS, REPS)
+                med = {k_: np.median(v) for k_, v in t.items()}
+                lines.append("%-22s %-3d %-9s %-5s %-16s %-16s %-16s %-12.2f %-10.2f" % (list(shape), dg, str(dt).replace("torch.", ""), leg, _cell(t["native"]),
+                                                                                      _cell(t["widen"]), _cell(t["f32"]), med["native"] / med["widen"],
+                                                                                      med["native"] / med["f32"]))
+                print(lines[-1], flush=True)
+            del m32, m16, x32, o32, k32, g32, x16, o16, k16, g16, fwd, both
+            torch.cuda.empty_cache()
+    _write(lines, out_path)
+
+
 def bev():
     """Bilinear BEV gather at the FV2P size vs the reference's torch composition (permute + 4 index gathers + weights)."""
     from pcdet.models.backbones_3d.pfe import bev_grid_pooling as bgp
@@ -1200,6 +1256,9 @@ if __name__ == "__main__":
         sys.exit(0)
     if which == "bev16":   # python tools/microbench.py bev16 [profiles/bev_half.txt]
         bev16(sys.argv[2] if len(sys.argv) > 2 else None)
+        sys.exit(0)
+    if which == "dcn16":   # python tools/microbench.py dcn16 [profiles/dcn_half.txt]
+        dcn16(sys.argv[2] if len(sys.argv) > 2 else None)
         sys.exit(0)
     if which == "exit16":   # python tools/microbench.py exit16 [profiles/exit_half.txt]
         exit16(sys.argv[2] if len(sys.argv) > 2 else None)
