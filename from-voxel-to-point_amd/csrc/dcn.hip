@@ -19,6 +19,7 @@
 // nearest in-map pixel with weight 0 (loads are unconditional).
 #include "common.hpp"
 #include "dcn_common.hpp"
+#include "dt16.hpp"
 #include <stdlib.h>
 #include <stdio.h>
 #include <algorithm>
@@ -267,37 +268,6 @@ __global__ __launch_bounds__(256, 2) void dcn_fwd_k(DcnGeom g, const float* __re
 // lane ends up with FOUR ADJACENT CHANNELS of ONE pixel: exactly the float4 it gathers from x at the four bilinear corners.  Epilogue per
 // (tap, group, 32-channel block):  D_q += <dcol, x[corner q]>  (-> grad_mask, grad_offset at the end of the (tap, group) segment,
 // modulated_deform_im2col_cuda.cuh:256-328) and  colg[p, k, ci] = dcol * mask  (what pass 2 sums into grad_input, :196-254).
-struct CornerB {
-  unsigned o[4];
-  float w[4];
-  float m, lh, lw;
-  unsigned vb;   // bit q: corner q is inside the map (and the sample valid)
-};
-
-__device__ __forceinline__ void make_corners_b(const DcnGeom& g, bool live, int b, float h_im, float w_im, float m, unsigned lane_bytes, CornerB& t) {
-  const bool valid = live && (h_im > -1.f && w_im > -1.f && h_im < static_cast<float>(g.H) && w_im < static_cast<float>(g.W));
-  const float hf = floorf(h_im), wf = floorf(w_im);
-  const int h_low = static_cast<int>(hf), w_low = static_cast<int>(wf);
-  const int h_high = h_low + 1, w_high = w_low + 1;
-  const float lh = h_im - hf, lw = w_im - wf, hh = 1.f - lh, hw = 1.f - lw;
-  const bool hl = valid && h_low >= 0, hhi = valid && h_high <= g.H - 1, wl = w_low >= 0, whi = w_high <= g.W - 1;
-  t.w[0] = (hl && wl) ? hh * hw : 0.f;
-  t.w[1] = (hl && whi) ? hh * lw : 0.f;
-  t.w[2] = (hhi && wl) ? lh * hw : 0.f;
-  t.w[3] = (hhi && whi) ? lh * lw : 0.f;
-  t.vb = (hl && wl ? 1u : 0u) | (hl && whi ? 2u : 0u) | (hhi && wl ? 4u : 0u) | (hhi && whi ? 8u : 0u);
-  t.m = valid ? m : 0.f;
-  t.lh = lh; t.lw = lw;
-  const int h0 = min(max(h_low, 0), g.H - 1), h1 = min(max(h_high, 0), g.H - 1);
-  const int w0 = min(max(w_low, 0), g.W - 1), w1 = min(max(w_high, 0), g.W - 1);
-  const unsigned row0 = static_cast<unsigned>((b * g.H + h0) * g.W), row1 = static_cast<unsigned>((b * g.H + h1) * g.W);
-  const unsigned pitch = static_cast<unsigned>(g.Cin) * 4u;
-  t.o[0] = (row0 + w0) * pitch + lane_bytes;
-  t.o[1] = (row0 + w1) * pitch + lane_bytes;
-  t.o[2] = (row1 + w0) * pitch + lane_bytes;
-  t.o[3] = (row1 + w1) * pitch + lane_bytes;
-}
-
 // JO = ceil(columns of the slice / 16); NBP = 16-pixel blocks per wave; block = 4 waves = 64 * NBP pixels; step = (tap, group,
 // 16 * MC input channels).  wt = [K][Cin][Cout/G].  A workgroup covers the input channels of ONE conv group (grp0 + sub / n_share) and
 // the group's output columns [256 slice, 256 slice + 256): its dy registers hold those columns only.  slice > 0 adds to colg and to
@@ -508,16 +478,17 @@ __global__ __launch_bounds__(256, 2) void dcn_bwd_col_k(DcnGeom g, const float* 
 // (r, c+1), (r+1, c), (r+1, c+1) of the tile with its four bilinear weights.  Keys are visited in a fixed order and every list in
 // ascending sample order (ranked inside the wave), so each pixel's sum has one order: no float atomics, no zero fill, same bits every run.
 //   key grid per (sample, deformable group): (H + 1) x (W + 1), key (h_low + 1, w_low + 1); entry = {src = pixel * K + tap, lh, lw}
-struct DcnEntries {
-  unsigned* src;
-  float* lh;
-  float* lw;
-};
-
 // one thread per sample (b, group, tap, output pixel): FILL = 0 counts the entries of every key, FILL = 1 writes them
 // (cursor[key] starts at the list's first slot and ends at its end: list = [cursor[key - 1], cursor[key]) afterwards)
-template <int FILL>
-__global__ __launch_bounds__(256) void dcn_index_k(DcnGeom g, const float* __restrict__ offset, int* __restrict__ cursor, DcnEntries en) {
+// OM: format of the offsets (0 fp32, FV2P_DT_F16, FV2P_DT_BF16), widened at the load: positions are fp32 either way
+template <int OM>
+__device__ __forceinline__ float dcn_off_load(const void* p, long long i) {
+  if constexpr (OM == FV2P_DT_F16) return H16::widen(static_cast<const u16*>(p)[i]);
+  else if constexpr (OM == FV2P_DT_BF16) return B16::widen(static_cast<const u16*>(p)[i]);
+  else return static_cast<const float*>(p)[i];
+}
+template <int FILL, int OM = 0>
+__global__ __launch_bounds__(256) void dcn_index_k(DcnGeom g, const void* __restrict__ offset, int* __restrict__ cursor, DcnEntries en) {
   const int plane = g.Ho * g.Wo, K = g.kh * g.kw;
   const long long total = static_cast<long long>(g.B) * g.dg * K * plane;
   const long long id = static_cast<long long>(blockIdx.x) * 256 + threadIdx.x;
@@ -526,8 +497,9 @@ __global__ __launch_bounds__(256) void dcn_index_k(DcnGeom g, const float* __res
   const int k = static_cast<int>((id / plane) % K);
   const int bd = static_cast<int>(id / (static_cast<long long>(plane) * K));   // b * dg + dgi
   const int b = bd / g.dg;
-  const float* ob = offset + static_cast<long long>(bd) * 2 * K * plane + pos;
-  const float off_h = ob[static_cast<long long>(2 * k) * plane], off_w = ob[static_cast<long long>(2 * k + 1) * plane];
+  const long long ob = static_cast<long long>(bd) * 2 * K * plane + pos;
+  const float off_h = dcn_off_load<OM>(offset, ob + static_cast<long long>(2 * k) * plane);
+  const float off_w = dcn_off_load<OM>(offset, ob + static_cast<long long>(2 * k + 1) * plane);
   const int ho = pos / g.Wo, wo = pos % g.Wo, i = k / g.kw, j = k % g.kw;
   const float h_im = static_cast<float>(ho * g.sh - g.ph + i * g.dh) + off_h;
   const float w_im = static_cast<float>(wo * g.sw - g.pw + j * g.dw) + off_w;
@@ -903,16 +875,6 @@ using namespace fv2p;
 #define DCN_GEOM_INIT DcnGeom g = {batch, height, width, c_in, c_out, h_out, w_out, kh, kw, sh, sw, ph, pw, dh, dw, deformable_group, 1}
 
 
-static int dcn_cu_count() {
-  static int cus = 0;
-  if (cus == 0) {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) cus = n;
-    else cus = 256;
-  }
-  return cus;
-}
-
 // forward step order: -1 by shape, 0 (tap, group, chunk), 1 (group, chunk, tap) - fv2p_dcn_set_forward_order (tests, A/B runs)
 constexpr int kDcnTapInnerDefault = 0;   // forward step order when nobody chose one (measured: see DESIGN 3.6)
 static int g_dcn_fwd_order = -1;
@@ -940,6 +902,9 @@ static void dcn_fwd_launch(const DcnGeom& g, const float* x, const float* wt_oc,
 constexpr long long kColgCapBytes = 3ll << 29;   // 1.5 GiB: the MGAF head at batch 4 (1.30 GB) is still one chunk
 static long long g_colg_cap = kColgCapBytes;     // fv2p_dcn_set_colg_cap (tests: several chunks at shapes the oracle can answer)
 static int dcn_chunk_samples(const DcnGeom& g, bool backward) { return dcn_chunk_samples(g, backward, g_colg_cap, 4); }
+namespace fv2p {
+long long dcn_colg_cap() { return g_colg_cap; }
+}
 
 extern "C" int fv2p_dcn_set_forward_order(int order) {
   FV2P_REQUIRE(order >= -1 && order <= 1, FV2P_EINVAL, "dcn_set_forward_order: -1 (by shape), 0 (tap outer) or 1 (tap inner)");
@@ -1044,10 +1009,6 @@ static void dcn_bwd_carve(C& c, const DcnGeom& g, const DcnBwdPlan& p, float** c
   *scan_ws = c.template take<char>(scan_ws_bytes(p.nkeys));
   *partial = c.template take<float>(static_cast<size_t>(p.splits_cap) * K * g.Cin * (g.Cout / g.G));
 }
-struct SizerC : Sizer {
-  template <typename T> T* take(size_t n) { Sizer::take<T>(n); return nullptr; }
-};
-
 static size_t dcn_backward_ws(DcnGeom g) {
   g.B = std::max(1, std::min(g.B, dcn_chunk_samples(g, true)));   // the workspace of one chunk serves every chunk
   const DcnBwdPlan p = dcn_bwd_plan(g);
@@ -1067,6 +1028,33 @@ extern "C" size_t fv2p_dcn_backward_grouped_ws_bytes(int batch, int height, int 
   const int G = group > 0 && c_in % group == 0 && c_out % group == 0 ? group : 1;
   return dcn_backward_ws({batch, height, width, c_in, c_out, h_out, w_out, kh, kw, 1, 1, 0, 0, 1, 1, deformable_group > 0 ? deformable_group : 1, G});
 }
+
+namespace fv2p {
+// the sample lists of one chunk (cursor: nkeys + 1 ints; afterwards the end of every key's list), offsets in format `om`
+int dcn_sample_lists(const DcnGeom& gc, const void* offset, int om, int* cursor, DcnEntries entries, void* sws, hipStream_t stream) {
+  const long long nkeys = static_cast<long long>(gc.B) * gc.dg * (gc.H + 1) * (gc.W + 1);
+  FV2P_HIP(hipMemsetAsync(cursor, 0, sizeof(int) * (size_t)(nkeys + 1), stream));
+  const long long nsamples = static_cast<long long>(gc.B) * gc.Ho * gc.Wo * gc.dg * gc.kh * gc.kw;
+  const unsigned iblocks = static_cast<unsigned>(ceil_div(nsamples, 256));
+#define DCN_INDEX(FILL) do { \
+    if (om == FV2P_DT_F16) hipLaunchKernelGGL((dcn_index_k<FILL, FV2P_DT_F16>), dim3(iblocks), dim3(256), 0, stream, gc, offset, cursor, entries); \
+    else if (om == FV2P_DT_BF16) hipLaunchKernelGGL((dcn_index_k<FILL, FV2P_DT_BF16>), dim3(iblocks), dim3(256), 0, stream, gc, offset, cursor, entries); \
+    else hipLaunchKernelGGL((dcn_index_k<FILL, 0>), dim3(iblocks), dim3(256), 0, stream, gc, offset, cursor, entries); } while (0)
+  DCN_INDEX(0);
+  if (int rc = exclusive_scan_i32(cursor, cursor, nkeys, nullptr, sws, scan_ws_bytes(nkeys), stream)) return rc;
+  DCN_INDEX(1);
+#undef DCN_INDEX
+  hipLaunchKernelGGL(dcn_index_sort_long_k, dim3(static_cast<unsigned>(std::min<long long>(1024, ceil_div(nkeys, 256)))), dim3(256), 0, stream,
+                     cursor, nkeys, entries);
+  return 0;
+}
+
+// out = (accumulate ? out : 0) + the `chunks` partials in ascending order
+void dcn_reduce_launch(const float* partial, int chunks, long long per_chunk, float* out, bool accumulate, hipStream_t stream) {
+  hipLaunchKernelGGL(dcn_reduce_k, dim3(static_cast<unsigned>(ceil_div(per_chunk, 256))), dim3(256), 0, stream, partial, chunks, per_chunk, out,
+                     accumulate ? 1 : 0);
+}
+}  // namespace fv2p
 
 // grid: pixel tiles x ng conv groups (grp0 ..) x n_share shares of a group's segments; output columns [256 slice, 256 slice + 256) of each group
 template <int JO, int MC>
@@ -1115,14 +1103,7 @@ static int dcn_backward_run(const DcnGeom& g, const float* x_nhwc, const float* 
     float* doc = doffset + static_cast<long long>(s0) * g.dg * 2 * K * pix;
     float* dmc = dmask + static_cast<long long>(s0) * g.dg * K * pix;
     // 1. per-target sample lists
-    FV2P_HIP(hipMemsetAsync(cursor, 0, sizeof(int) * (size_t)(p.nkeys + 1), stream));
-    const long long nsamples = cpix * g.dg * K;
-    const unsigned iblocks = static_cast<unsigned>(ceil_div(nsamples, 256));
-    hipLaunchKernelGGL((dcn_index_k<0>), dim3(iblocks), dim3(256), 0, stream, gc, oc, cursor, entries);
-    if (int rc = exclusive_scan_i32(cursor, cursor, p.nkeys, nullptr, sws, scan_ws_bytes(p.nkeys), stream)) return rc;
-    hipLaunchKernelGGL((dcn_index_k<1>), dim3(iblocks), dim3(256), 0, stream, gc, oc, cursor, entries);
-    hipLaunchKernelGGL(dcn_index_sort_long_k, dim3(static_cast<unsigned>(std::min<long long>(1024, ceil_div(p.nkeys, 256)))), dim3(256), 0, stream,
-                       cursor, p.nkeys, entries);
+    if (int rc = dcn_sample_lists(gc, oc, 0, cursor, entries, sws, stream)) return rc;
     // 2. column gradients, grad_mask, grad_offset.  Conv groups whose channels hold whole deformable groups share a launch; otherwise
     // (a deformable group spans conv groups) the groups run one launch each in ascending order, the later ones adding their share of
     // grad_offset / grad_mask.  Groups wider than 256 output columns run in slices of 256, in ascending order, each adding to colg
@@ -1159,9 +1140,7 @@ static int dcn_backward_run(const DcnGeom& g, const float* x_nhwc, const float* 
     const dim3 wgrid(static_cast<unsigned>(static_cast<long long>(p.splits) * K * g.G * p.ci_tiles * p.co_tiles));
     hipLaunchKernelGGL(dcn_bwd_weight_k, wgrid, dim3(256), 2 * 2 * 16 * kDwPitch * sizeof(float), stream, gc, xc, oc, mc, dyc,
                        p.pix_per_block, g.G * p.ci_tiles * p.co_tiles, partial);
-    const long long per_chunk = static_cast<long long>(K) * g.Cin * coutg;
-    hipLaunchKernelGGL(dcn_reduce_k, dim3(static_cast<unsigned>(ceil_div(per_chunk, 256))), dim3(256), 0, stream, partial, p.splits, per_chunk, dwt,
-                       s0 > 0 ? 1 : 0);
+    dcn_reduce_launch(partial, p.splits, static_cast<long long>(K) * g.Cin * coutg, dwt, s0 > 0, stream);
   }
   FV2P_LAUNCH_CHECK();
   return 0;

@@ -202,16 +202,6 @@ __global__ __launch_bounds__(256, 2) void dcn_fwd_h_k(DcnGeom g, const u16* __re
   }
 }
 
-static int dcn_h_cu_count() {
-  static int cus = 0;
-  if (cus == 0) {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) cus = n;
-    else cus = 256;
-  }
-  return cus;
-}
-
 template <class T, int NB>
 static void dcn_fwd_h_launch(const DcnGeom& g, const u16* x, const u16* wt_oc, const float* bias, const void* offset, const void* mask, int om16,
                              u16* y, long long npix, int col_blocks, hipStream_t stream) {
@@ -238,7 +228,7 @@ static int dcn_forward_h_run(const DcnGeom& g, const u16* x, const u16* wt_oc, c
     // the plan of dcn_forward_run: 64 pixels x 16*NB columns per workgroup; 256 columns in one workgroup unless the map is too small
     // to fill the chip, then two column halves.  Per-pixel arithmetic does not depend on the plan.
     int nb = nb_all <= 4 ? 4 : (nb_all <= 8 ? 8 : 16);
-    if (nb == 16 && ceil_div(npix, 64) < 2 * dcn_h_cu_count()) nb = 8;
+    if (nb == 16 && ceil_div(npix, 64) < 2 * dcn_cu_count()) nb = 8;
     const int col_blocks = static_cast<int>(ceil_div(nb_all, nb));
     if (nb == 4) dcn_fwd_h_launch<T, 4>(gc, xc, wt_oc, bias, oc, mc, om16, yc, npix, col_blocks, stream);
     else if (nb == 8) dcn_fwd_h_launch<T, 8>(gc, xc, wt_oc, bias, oc, mc, om16, yc, npix, col_blocks, stream);

@@ -7,8 +7,10 @@ Cout > 256) reaches fv2p_dcn_*_grouped, with the input channels zero-padded on t
 
 float16 / bfloat16 maps: the forward of groups == 1 with Cin / deformable_group a multiple of 16 reaches fv2p_dcn_forward_h, the same
 implicit GEMM on the 16-bit MFMA with no fp32 copy of any map (NATIVE_16BIT, on by default; off = the fp32 route on widened copies, as
-before).  The backward keeps the fp32 kernels and reaches them through fv2p_transpose_batched_widen / _round: the layout copy and the
-dtype copy of x, grad_output and grad_input are one pass each."""
+before).  The backward keeps the fp32 kernels by default and reaches them through fv2p_transpose_batched_widen / _round: the layout copy
+and the dtype copy of x, grad_output and grad_input are one pass each.  NATIVE_16BIT_BACKWARD (off by default) sends the backward of the
+same calls with Cout <= 256 to fv2p_dcn_backward_h instead: x, grad_output, the weight, the column gradients and grad_input stay in 16
+bits, grad_offset / grad_mask come in the offsets' dtype and grad_weight from an fp32 buffer (csrc/dcn_bwd_h.hip)."""
 import math
 
 import torch
@@ -16,6 +18,7 @@ import torch
 import fv2p_native as _nat
 
 NATIVE_16BIT = True    # float16 / bfloat16 forward on fv2p_dcn_forward_h where it serves the geometry; False: the fp32 kernels on widened copies
+NATIVE_16BIT_BACKWARD = False   # float16 / bfloat16 backward on fv2p_dcn_backward_h where it serves the geometry; False: the fp32 kernels on widened copies
 _DT16 = {torch.float16: 1, torch.bfloat16: 2}   # FV2P_DT_F16 / FV2P_DT_BF16
 
 
@@ -179,6 +182,64 @@ def _wt_oc(weight):
     return weight.permute(2, 3, 0, 1).reshape(kh * kw, cout, cin).contiguous()
 
 
+def _nhwc_16bit(t):
+    """[B, C, H, W] 16-bit (any strides) -> contiguous [B, H, W, C] in the same dtype: a view for a channels-last tensor, else
+    fv2p_transpose_batched_h."""
+    B, C, H, W = t.shape
+    v = t.permute(0, 2, 3, 1)
+    if t.numel() == 0 or v.is_contiguous() or not t.is_contiguous():
+        return v.contiguous()
+    out = torch.empty((B, H, W, C), dtype=t.dtype, device=t.device)
+    with _nat.device_guard(t.device):
+        _nat.call("fv2p_transpose_batched_h", t, B, C, H * W, out, _nat.stream())
+    return out
+
+
+def _native_16bit_backward(input, weight, group, deformable_group):
+    """The calls fv2p_dcn_backward_h takes: a float16 / bfloat16 map on the GPU, no conv groups, the forward's geometry with
+    Cout <= 256 (a Cout that is no multiple of 8 is zero-padded on the way in)."""
+    if not (NATIVE_16BIT_BACKWARD and input.dtype in _DT16 and input.is_cuda and group == 1 and deformable_group >= 1):
+        return False
+    cout = weight.shape[0]
+    return bool(_nat.lib().fv2p_dcn_backward_h_supported(input.shape[1], cout + (-cout) % 8, deformable_group))
+
+
+def _backward_16bit(input, weight, offset, mask, grad_output, g):
+    """fv2p_dcn_backward_h: x, grad_output, the weight and grad_input in input.dtype, no .float() of any map.  The weight (fp32 master
+    weights under autocast) is rounded once while it is permuted; offset and mask go as they are in input.dtype or float32 and their
+    gradients come back in that dtype; grad_weight is the kernel's fp32 buffer cast to weight.dtype (unrounded for an fp32 weight)."""
+    B, H, W, C, Cout, Ho, Wo, kh, kw = g[:9]
+    dt, dev, K = input.dtype, input.device, g[7] * g[8]
+    x = _nhwc_16bit(input)
+    dy0 = _nhwc_16bit(grad_output if grad_output.dtype == dt else grad_output.to(dt)).view(B * Ho * Wo, Cout)
+    wt = _wt(weight if weight.dtype == dt else weight.to(dt))
+    dy = dy0
+    pad = (-Cout) % 8            # the kernels read output channels eight at a time: pad with zero columns
+    if pad:
+        dy = torch.nn.functional.pad(dy0, (0, pad))
+        wt = torch.nn.functional.pad(wt, (0, pad))
+        g = g[:4] + (Cout + pad,) + g[5:]
+    om = offset.dtype if offset.dtype == mask.dtype and offset.dtype in (dt, torch.float32) else torch.float32
+    off = (offset if offset.dtype == om else offset.to(om)).contiguous()
+    msk = (mask if mask.dtype == om else mask.to(om)).contiguous()
+    dx = torch.empty((B, H, W, C), dtype=dt, device=dev)
+    doff, dmask = torch.empty_like(off), torch.empty_like(msk)
+    dwt = torch.empty((K, C, Cout + pad), dtype=torch.float32, device=dev)
+    with _nat.device_guard(dev):
+        nb = _nat.lib().fv2p_dcn_backward_h_ws_bytes(B, H, W, Ho, Wo, C, Cout + pad, kh, kw, g[15])
+        ws = _nat.workspace(nb, dev)
+        _nat.call("fv2p_dcn_backward_h", x, wt, off, msk, dy, *g, dx, doff, dmask, dwt, ws, ws.numel(), _DT16[dt],
+                  0 if om == torch.float32 else _DT16[dt], _nat.stream())
+        if _channels_last(input) or dx.numel() == 0:
+            grad_input = dx.permute(0, 3, 1, 2) if _channels_last(input) else dx.permute(0, 3, 1, 2).contiguous()
+        else:
+            grad_input = torch.empty((B, C, H, W), dtype=dt, device=dev)
+            _nat.call("fv2p_transpose_batched_h", dx, B, H * W, C, grad_input, _nat.stream())
+    grad_weight = dwt[:, :, :Cout].reshape(kh, kw, C, Cout).permute(3, 2, 0, 1).contiguous().to(weight.dtype)
+    grad_bias = dy0.sum(dim=0, dtype=torch.float32)
+    return [grad_input, doff, dmask, grad_weight, grad_bias]
+
+
 def _forward_nhwc(x, weight, bias, offset, mask, g):
     """x NHWC contiguous fp32 -> y [B*Ho*Wo, Cout] (the C-ABI call)."""
     B, H, W, C, Cout, Ho, Wo = g[:7]
@@ -269,6 +330,9 @@ def modulated_deform_conv_backward(input, weight, bias, offset, mask, grad_outpu
                                    pad_w, dilation_h, dilation_w, group, deformable_group, im2col_step):
     """-> [grad_input, grad_offset, grad_mask, grad_weight, grad_bias] (modulated_deform_conv_cuda.cu:127-280).
     No float atomics anywhere: the five gradients are bit-identical from run to run (include/fv2p_ops.h, A13)."""
+    if _native_16bit_backward(input, weight, group, deformable_group):
+        g = _geom(input, weight, kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w, group, deformable_group)
+        return _backward_16bit(input, weight, offset, mask, grad_output, g)
     if not _plain(input, weight, group, deformable_group):
         return _grouped_backward(input, weight, offset, mask, grad_output, kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w,
                                  dilation_h, dilation_w, group, deformable_group)
@@ -312,7 +376,8 @@ def deform_conv_backward(input, weight, bias, offset, grad_output, kernel_h, ker
                          dilation_w, group, deformable_group, im2col_step):
     """-> [grad_input, grad_offset, grad_weight, grad_bias]."""
     B, _, Ho, Wo = offset.shape
-    mask = torch.ones((B, deformable_group * kernel_h * kernel_w, Ho, Wo), dtype=torch.float32, device=input.device)
+    mask = torch.ones((B, deformable_group * kernel_h * kernel_w, Ho, Wo), device=input.device,
+                      dtype=input.dtype if _native_16bit_backward(input, weight, group, deformable_group) else torch.float32)
     gi, go, _, gw, gb = modulated_deform_conv_backward(input, weight, bias, offset, mask, grad_output, kernel_h, kernel_w, stride_h,
                                                        stride_w, pad_h, pad_w, dilation_h, dilation_w, group, deformable_group,
                                                        im2col_step)

@@ -870,6 +870,30 @@ int fv2p_dcn_forward_h(const void* x_nhwc, const void* wt_oc, const float* bias,
                        void* y_nhwc, int dtype, int om_dtype, fv2p_stream_t stream);
 int fv2p_dcn_forward_h_supported(int c_in, int c_out, int deformable_group);
 
+/* The backward on float16 / bfloat16 maps (csrc/dcn_bwd_h.hip): the three passes of fv2p_dcn_backward on
+ * v_mfma_f32_16x16x32_{f16,bf16}, no fp32 copy of any map.  `dtype` names the format of x_nhwc [B,H,W,Cin], wt [kh*kw][Cin][Cout],
+ * dy_nhwc [B*Ho*Wo][Cout], dx_nhwc [B,H,W,Cin] and of the column gradients in the workspace; offset and mask are fp32 (om_dtype 0) or
+ * in the call's format (om_dtype == dtype), and doffset / dmask leave in THAT format; dwt [kh*kw][Cin][Cout] is fp32 (the caller
+ * casts it: an fp32 master weight gets an unrounded gradient).  The dtype / om_dtype checks come first (FV2P_EINVAL before any HIP
+ * call).  Arithmetic: fp32 accumulators everywhere; dcol = wt dy from the 16-bit operands; grad_mask / grad_offset from the fp32 dcol
+ * and the widened corners of x with fv2p_dcn_backward's formulas, written once per (pixel, tap, deformable group) with one rounding;
+ * colg = dcol * mask rounded once to the format (it reaches dx only); dx = fp32 sums over the sample lists in the fixed key and
+ * sample order, rounded once; dwt from the column operand formed as fv2p_dcn_forward_h forms it (one rounding) and dy, per-split
+ * fp32 partials folded in ascending split and chunk order.  No float atomics, nothing to zero, two runs give the same bits.
+ * Geometry: that of fv2p_dcn_forward_h, and Cout <= 256, Cout a multiple of 8 (the caller zero-pads dy and wt); FV2P_ELIMIT
+ * otherwise - fv2p_dcn_backward_h_supported (pure host) answers 1 / 0.  x, wt, dy and dx must be 16-byte aligned; nothing outside
+ * x, wt, dy, offset or mask is read.  Batches are cut into chunks of whole samples as above (fv2p_dcn_set_colg_cap governs this
+ * route too, and the same value gives the same chunks: the cap counts column gradients at 4 bytes an element on both routes, so
+ * this route's 2-byte column gradients take half the capped bytes); fv2p_dcn_backward_h_ws_bytes is the workspace of one chunk.  B = 0: dwt is zeroed, nothing else is touched. */
+int fv2p_dcn_backward_h_supported(int c_in, int c_out, int deformable_group);
+size_t fv2p_dcn_backward_h_ws_bytes(int batch, int height, int width, int h_out, int w_out, int c_in, int c_out, int kh,
+                                    int kw, int deformable_group);
+int fv2p_dcn_backward_h(const void* x_nhwc, const void* wt, const void* offset, const void* mask, const void* dy_nhwc,
+                        int batch, int height, int width, int c_in, int c_out, int h_out, int w_out, int kh, int kw,
+                        int sh, int sw, int ph, int pw, int dh, int dw, int deformable_group,
+                        void* dx_nhwc, void* doffset, void* dmask, float* dwt, void* ws, size_t ws_bytes, int dtype,
+                        int om_dtype, fv2p_stream_t stream);
+
 /* Layout copies around the NHWC entry points above (and fv2p_bev_interp_*): in [batch][rows][cols] -> out [batch][cols][rows],
  * e.g. NCHW -> NHWC with rows = C, cols = H*W.  The reference does the same copies with at::permute + contiguous
  * (modulated_deform_conv_cuda.cu:78,118). */

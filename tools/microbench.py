@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Per-kernel timings on one GPU (events on the launch stream). Not part of the product or of bench.py; used to
-iterate on kernel variants:  python tools/microbench.py [conv|conv16|amp16|bn16|bn2d|bn2d16|bev16|exit16|batch16|dcn|dcn16|fps|voxel|nms|all]"""
+iterate on kernel variants:  python tools/microbench.py [conv|conv16|amp16|bn16|bn2d|bn2d16|bev16|exit16|batch16|dcn|dcn16|dcn16bwd|fps|voxel|nms|all]"""
 import os
 import sys
 import time
@@ -1093,6 +1093,77 @@ def dcn16(out_path=None):
     _write(lines, out_path)
 
 
+def dcn16bwd(out_path=None):
+    """ModulatedDeformConv 3 x 3 on 16-bit maps, forward + backward through the module (layout copies included), the forward on
+    fv2p_dcn_forward_h on both 16-bit routes.  on: DCN.NATIVE_16BIT_BACKWARD = True (fv2p_dcn_backward_h); off: the default, the fp32
+    backward kernels between the converting transposes; f32: the fp32 op on fp32 tensors.  Alternating windows as in bn2d16; the claim
+    is on / off, the spread of the windows beside it."""
+    from pcdet.ops.DeformableConvolutionV2PyTorch import DCN
+    from pcdet.ops.DeformableConvolutionV2PyTorch.modules.modulated_deform_conv import ModulatedDeformConv
+    dev = torch.device("cuda:0")
+    ROUNDS, REPS = 7, 5
+    lines = ["ModulatedDeformConv 3x3 (Cout = Cin) on 16-bit maps, forward + backward, us per call: median of %d windows of %d calls, +- half the "
+             "range.  on: NATIVE_16BIT_BACKWARD = True (fv2p_dcn_backward_h); off: the default (fv2p_dcn_backward on widened copies); f32: "
+             "the fp32 op on fp32 tensors" % (ROUNDS, REPS),
+             "%-22s %-3s %-9s %-16s %-16s %-16s %-8s %-8s" % ("map", "dg", "dtype", "on", "off", "f32", "on/off", "on/f32")]
+    for shape, dg in (((4, 128, 200, 176), 1), ((4, 256, 200, 176), 4), ((4, 256, 100, 88), 4), ((4, 256, 50, 44), 4)):
+        B, C, H, W = shape
+        for dt in (torch.float16, torch.bfloat16):
+            torch.manual_seed(0)
+            m32 = ModulatedDeformConv(C, C, 3, 1, 1, 1, 1, dg, 64, bias=True).to(dev)
+            m16 = ModulatedDeformConv(C, C, 3, 1, 1, 1, 1, dg, 64, bias=True).to(dev)
+            m16.load_state_dict(m32.state_dict())
+            m16 = m16.to(dt)
+            x32 = torch.randn(shape, device=dev).requires_grad_(True)
+            o32 = (torch.randn((B, dg * 18, H, W), device=dev) * 1.5).requires_grad_(True)
+            k32 = torch.rand((B, dg * 9, H, W), device=dev).requires_grad_(True)
+            g32 = torch.randn(shape, device=dev)
+            x16, o16, k16 = (t.detach().to(dt).requires_grad_(True) for t in (x32, o32, k32))
+            g16 = g32.to(dt)
+            routes = {}
+            for name, m, x, o, k, g, flag in (("on", m16, x16, o16, k16, g16, True), ("off", m16, x16, o16, k16, g16, False),
+                                              ("f32", m32, x32, o32, k32, g32, False)):
+                def fn(m=m, x=x, o=o, k=k, g=g, flag=flag):
+                    DCN.NATIVE_16BIT_BACKWARD = flag
+                    try:
+                        m(x, o, k).backward(g)
+                    finally:
+                        DCN.NATIVE_16BIT_BACKWARD = False
+                    x.grad = o.grad = k.grad = None
+                    m.weight.grad = m.bias.grad = None
+                routes[name] = fn
+            t = _windows(routes, ROUNDS, REPS)
+            med = {k_: np.median(v) for k_, v in t.items()}
+            lines.append("%-22s %-3d %-9s %-16s %-16s %-16s %-8.2f %-8.2f" % (list(shape), dg, str(dt).replace("torch.", ""), _cell(t["on"]), _cell(t["off"]),
+                                                                         _cell(t["f32"]), med["on"] / med["off"], med["on"] / med["f32"]))
+            print(lines[-1], flush=True)
+            del m32, m16, x32, o32, k32, g32, x16, o16, k16, g16, routes
+            torch.cuda.empty_cache()
+    _write(lines, out_path)
+
+
+def dcn16bwd_once():
+    """Four forward + backward calls of the MGAF head's DCN layer on float16 maps with the native backward, and nothing else: the run
+    to put under `rocprofv3 --kernel-trace --stats` for the per-kernel split.  All four calls are traced, the first included; read the
+    averages."""
+    from pcdet.ops.DeformableConvolutionV2PyTorch import DCN
+    from pcdet.ops.DeformableConvolutionV2PyTorch.modules.modulated_deform_conv import ModulatedDeformConv
+    dev, dt, (B, C, H, W), dg = torch.device("cuda:0"), torch.float16, (4, 256, 200, 176), 4
+    torch.manual_seed(0)
+    m = ModulatedDeformConv(C, C, 3, 1, 1, 1, 1, dg, 64, bias=True).to(dev).to(dt)
+    x = torch.randn((B, C, H, W), device=dev).to(dt).requires_grad_(True)
+    o = (torch.randn((B, dg * 18, H, W), device=dev) * 1.5).to(dt).requires_grad_(True)
+    k = torch.rand((B, dg * 9, H, W), device=dev).to(dt).requires_grad_(True)
+    g = torch.randn((B, C, H, W), device=dev).to(dt)
+    DCN.NATIVE_16BIT_BACKWARD = True
+    try:
+        for _ in range(4):
+            m(x, o, k).backward(g)
+        torch.cuda.synchronize()
+    finally:
+        DCN.NATIVE_16BIT_BACKWARD = False
+
+
 def bev():
     """Bilinear BEV gather at the FV2P size vs the reference's torch composition (permute + 4 index gathers + weights)."""
     from pcdet.models.backbones_3d.pfe import bev_grid_pooling as bgp
@@ -1256,6 +1327,12 @@ if __name__ == "__main__":
         sys.exit(0)
     if which == "bev16":   # python tools/microbench.py bev16 [profiles/bev_half.txt]
         bev16(sys.argv[2] if len(sys.argv) > 2 else None)
+        sys.exit(0)
+    if which == "dcn16bwd":   # python tools/microbench.py dcn16bwd [profiles/dcn_bwd_half.txt]
+        dcn16bwd(sys.argv[2] if len(sys.argv) > 2 else None)
+        sys.exit(0)
+    if which == "dcn16bwd_once":   # rocprofv3 --kernel-trace --stats -- python tools/microbench.py dcn16bwd_once
+        dcn16bwd_once()
         sys.exit(0)
     if which == "dcn16":   # python tools/microbench.py dcn16 [profiles/dcn_half.txt]
         dcn16(sys.argv[2] if len(sys.argv) > 2 else None)
