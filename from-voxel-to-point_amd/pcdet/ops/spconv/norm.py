@@ -15,8 +15,8 @@ either all fp32 or all of x's dtype.  Nothing is cast on the way.  That route al
 y = relu(bn(x) + residual).
 
 Dense maps [N, C, H, W] have the same op for `nn.BatchNorm2d` (`fusable2d`, `batch_norm2d_relu`, `run_maps`; kernels in
-csrc/batchnorm2d.hip): at the end of this file.  float16 / bfloat16 maps take `fusable2d16`, `batch_norm2d_relu16` and the kernels of
-csrc/batchnorm2d_h.hip, by the rules of the 16-bit row route; `run_maps` tries them where the fp32 op declined.
+csrc/batchnorm2d.hip): at the end of this file.  float16 / bfloat16 maps take `fusable2d16`, `batch_norm2d_relu16` and the same kernels
+in their format, by the rules of the 16-bit row route; `run_maps` tries them where the fp32 op declined.
 """
 import os
 
@@ -228,120 +228,38 @@ def batch_norm_relu(bn, x, relu_module=None, residual=None):
 # The pair behind every Conv2d / ConvTranspose2d of the BEV backbones (base_bev_backbone.py:35-46, :53-70).  Same contract as the row op
 # above: the module's parameters and running statistics, torch's result within fp32 rounding, None whenever the situation is not the
 # plain one - and the caller then runs the torch modules one by one.
+# float16 / bfloat16 maps run the same kernels in their format: x, y and the gradients stay in 16 bits; fp32 arithmetic, fp64 sums, one
+# rounding at the store; the module's parameters and buffers are all fp32 (a BatchNorm kept in fp32 under autocast) or all of x's dtype
+# (backbone_2d.half()).  Nothing is cast on the way.
 BN2D_CHUNK = 4096   # plane elements per workgroup (kBn2dChunk in csrc/batchnorm2d.hip); tests place shapes on either side of it
+BN2D_CHUNK16 = BN2D_CHUNK   # the same kernels, the same chunk
+_WS_BYTES2D = {}
 
 
-class _BatchNorm2dReLU(Function):
-    """The ctypes form of the compiled binding's BnRelu2dFn (used when lib/fv2p_torch.so is absent)."""
-
-    @staticmethod
-    def forward(ctx, x, weight, bias, bn, relu):
-        n, c, h, w = x.shape
-        hw = h * w
-        dev = x.device
-        batch_stats = bn.training or bn.running_mean is None
-        y = torch.empty_like(x)
-        with _nat.device_guard(dev):
-            if batch_stats:
-                stats = torch.empty((2, c), dtype=torch.float32, device=dev)
-                mean, invstd = stats[0], stats[1]
-                track = bn.training and bn.running_mean is not None
-                ws = _nat.workspace(_nat.call("fv2p_batchnorm2d_ws_bytes", n, c, hw), dev)
-                _nat.call("fv2p_batchnorm2d_forward", x, n, c, hw, float(bn.eps), -1.0 if bn.momentum is None else float(bn.momentum),
-                          weight, bias, int(relu), bn.running_mean if track else None, bn.running_var if track else None,
-                          bn.num_batches_tracked if track else None, mean, invstd, y, ws, ws.numel(), _nat.stream())
-            else:
-                mean = bn.running_mean.clone()   # a copy: the buffer may move before this call's backward runs
-                invstd = torch.rsqrt(bn.running_var + bn.eps)
-                _nat.call("fv2p_batchnorm2d_apply", x, n, c, hw, mean, invstd, weight, bias, int(relu), y, _nat.stream())
-        ctx.save_for_backward(x, mean, invstd, weight, bias)
-        ctx.relu, ctx.batch_stats = bool(relu), bool(batch_stats)
-        return y
-
-    @staticmethod
-    def backward(ctx, dz):
-        x, mean, invstd, weight, bias = ctx.saved_tensors
-        n, c, h, w = x.shape
-        hw = h * w
-        dev = x.device
-        dz = dz.contiguous()
-        dx = torch.empty_like(x)
-        dpar = torch.empty((2, c), dtype=torch.float32, device=dev)
-        dgamma, dbeta = dpar[0], dpar[1]
-        with _nat.device_guard(dev):
-            ws = _nat.workspace(_nat.call("fv2p_batchnorm2d_ws_bytes", n, c, hw), dev)
-            _nat.call("fv2p_batchnorm2d_backward", x, dz, n, c, hw, mean, invstd, weight, bias, int(ctx.relu), int(ctx.batch_stats),
-                      dx, dgamma, dbeta, ws, ws.numel(), _nat.stream())
-        return (dx if ctx.needs_input_grad[0] else None, dgamma if (weight is not None and ctx.needs_input_grad[1]) else None,
-                dbeta if (bias is not None and ctx.needs_input_grad[2]) else None, None, None)
-
-
-def _plain_forward(module):
-    """No hooks, and `forward` is the class's own (not replaced on the instance)."""
-    return _plain(module) and "forward" not in module.__dict__
-
-
-def fusable2d(bn, relu_module, x):
-    """The plain case of the (BatchNorm2d, ReLU) pair on a map x [N, C, H, W] the fused op covers."""
-    if not _ENABLED or type(bn) is not nn.BatchNorm2d or not _plain_forward(bn):
-        return False
-    if relu_module is not None and (type(relu_module) is not nn.ReLU or not _plain_forward(relu_module)):
-        return False
-    if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4):
-        return False
-    if not x.is_contiguous() or x.shape[1] != bn.num_features:   # (channels_last maps are not NCHW-contiguous: torch's modules run)
-        return False
-    if torch.is_autocast_enabled():
-        return False
-    n, _, h, w = x.shape
-    if n * h * w < (2 if bn.training else 1):   # torch raises for a single value per channel in training mode: let it
-        return False
-    if (bn.weight is None) != (bn.bias is None):
-        return False
-    for t in (bn.weight, bn.bias, bn.running_mean, bn.running_var):
-        if t is not None and (t.dtype != torch.float32 or t.device != x.device):
-            return False
-    if bn.num_batches_tracked is not None and bn.num_batches_tracked.device != x.device:
-        return False
-    return True
-
-
-def batch_norm2d_relu(bn, x, relu_module=None):
-    """y = relu?(bn(x)) for a contiguous fp32 map x [N, C, H, W] on the GPU, or None when the fused path does not apply."""
-    if not fusable2d(bn, relu_module, x):
-        return None
-    ext = _nat.torch_ext()
-    if ext is not None:
-        return ext.batch_norm2d_relu(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked, bn.training,
-                                     -1.0 if bn.momentum is None else float(bn.momentum), float(bn.eps), relu_module is not None)
-    return _BatchNorm2dReLU.apply(x, bn.weight, bn.bias, bn, relu_module is not None)
-
-
-# ---- the same pair on float16 / bfloat16 maps (csrc/batchnorm2d_h.hip) ------------------------------------------------------------------
-# x, y and the gradients stay in 16 bits; fp32 arithmetic, fp64 sums, one rounding at the store; the module's parameters and buffers are
-# all fp32 (a BatchNorm kept in fp32 under autocast) or all of x's dtype (backbone_2d.half()).  Nothing is cast on the way.
-BN2D_CHUNK16 = 4096   # plane elements per workgroup (kBn2dChunk16 in csrc/batchnorm2d_h.hip); tests place shapes on either side of it
-_WS_BYTES2D16 = {}
-
-
-def _ws_bytes2d16(n, c, hw):
-    b = _WS_BYTES2D16.get((n, c, hw))
+def _ws_bytes2d(n, c, hw):
+    b = _WS_BYTES2D.get((n, c, hw))
     if b is None:
-        b = _WS_BYTES2D16[(n, c, hw)] = _nat.call("fv2p_batchnorm2d_h_ws_bytes", n, c, hw)
+        b = _WS_BYTES2D[(n, c, hw)] = _nat.call("fv2p_batchnorm2d_ws_bytes", n, c, hw)   # (the _h query returns the same)
     return b
 
 
-class _BatchNorm2dReLU16(Function):
-    """y = relu?(bn(x)) on a float16 / bfloat16 map.  Saves x, the fp32 mean / invstd and the parameters; the backward pass recomputes
-    the mask of the stored y from x."""
+class _BatchNorm2dReLU(Function):
+    """y = relu?(bn(x)) on an fp32, float16 or bfloat16 map.  Saves x, the fp32 mean / invstd and the parameters; the backward pass
+    recomputes the mask of the stored y from x.  (fp32 maps: the ctypes form of the compiled binding's BnRelu2dFn, used when
+    lib/fv2p_torch.so is absent.)"""
 
     @staticmethod
     def forward(ctx, x, weight, bias, bn, relu):
         n, c, h, w = x.shape
         hw = h * w
         dev = x.device
-        dt = _DT16[x.dtype]
-        pd = 0 if _param_dtype(bn) in (None, torch.float32) else dt
+        # the 16-bit entry points (`_h`) take the map's format and the parameters' after the outputs; the fp32 ones take neither
+        if x.dtype in _DT16:
+            dt = _DT16[x.dtype]
+            pd = 0 if _param_dtype(bn) in (None, torch.float32) else dt
+            sfx, fmt = "_h", (dt, pd)
+        else:
+            pd, sfx, fmt = 0, "", ()
         batch_stats = bn.training or bn.running_mean is None
         y = torch.empty_like(x)
         with _nat.device_guard(dev):
@@ -349,18 +267,23 @@ class _BatchNorm2dReLU16(Function):
                 stats = torch.empty((2, c), dtype=torch.float32, device=dev)
                 mean, invstd = stats[0], stats[1]
                 track = bn.training and bn.running_mean is not None
-                ws = _nat.workspace(_ws_bytes2d16(n, c, hw), dev)
-                _nat.call("fv2p_batchnorm2d_forward_h", x, n, c, hw, float(bn.eps), -1.0 if bn.momentum is None else float(bn.momentum),
+                ws = _nat.workspace(_ws_bytes2d(n, c, hw), dev)
+                _nat.call("fv2p_batchnorm2d_forward" + sfx, x, n, c, hw, float(bn.eps), -1.0 if bn.momentum is None else float(bn.momentum),
                           weight, bias, int(relu), bn.running_mean if track else None, bn.running_var if track else None,
-                          bn.num_batches_tracked if track else None, mean, invstd, y, dt, pd, ws, ws.numel(), _nat.stream())
+                          bn.num_batches_tracked if track else None, mean, invstd, y, *fmt, ws, ws.numel(), _nat.stream())
             else:
-                # [C] values: a widened copy (the buffer may move before this call's backward runs), 1 / sqrt in float64 so that invstd is
-                # the correctly rounded fp32 value
-                mean = bn.running_mean.float().clone()
-                invstd = (1.0 / torch.sqrt(bn.running_var.double() + bn.eps)).float()
-                _nat.call("fv2p_batchnorm2d_apply_h", x, n, c, hw, mean, invstd, weight, bias, int(relu), y, dt, pd, _nat.stream())
+                # [C] values.  mean is a copy: the buffer may move before this call's backward runs.  The two formats keep their own
+                # invstd because the bits differ: fp32 maps take torch's fp32 rsqrt (what the compiled binding computes), 16-bit maps
+                # widen the buffers and take 1 / sqrt in float64, so that invstd is the correctly rounded fp32 value
+                if fmt:
+                    mean = bn.running_mean.float().clone()
+                    invstd = (1.0 / torch.sqrt(bn.running_var.double() + bn.eps)).float()
+                else:
+                    mean = bn.running_mean.clone()
+                    invstd = torch.rsqrt(bn.running_var + bn.eps)
+                _nat.call("fv2p_batchnorm2d_apply" + sfx, x, n, c, hw, mean, invstd, weight, bias, int(relu), y, *fmt, _nat.stream())
         ctx.save_for_backward(x, mean, invstd, weight, bias)
-        ctx.relu, ctx.batch_stats, ctx.dt, ctx.pd = bool(relu), bool(batch_stats), dt, pd
+        ctx.relu, ctx.batch_stats, ctx.pd, ctx.sfx, ctx.fmt = bool(relu), bool(batch_stats), pd, sfx, fmt
         return y
 
     @staticmethod
@@ -374,37 +297,78 @@ class _BatchNorm2dReLU16(Function):
         dpar = torch.empty((2, c), dtype=x.dtype if ctx.pd else torch.float32, device=dev)
         dgamma, dbeta = dpar[0], dpar[1]
         with _nat.device_guard(dev):
-            ws = _nat.workspace(_ws_bytes2d16(n, c, hw), dev)
-            _nat.call("fv2p_batchnorm2d_backward_h", x, dz, n, c, hw, mean, invstd, weight, bias, int(ctx.relu), int(ctx.batch_stats),
-                      dx, dgamma, dbeta, ctx.dt, ctx.pd, ws, ws.numel(), _nat.stream())
+            ws = _nat.workspace(_ws_bytes2d(n, c, hw), dev)
+            _nat.call("fv2p_batchnorm2d_backward" + ctx.sfx, x, dz, n, c, hw, mean, invstd, weight, bias, int(ctx.relu), int(ctx.batch_stats),
+                      dx, dgamma, dbeta, *ctx.fmt, ws, ws.numel(), _nat.stream())
         return (dx if ctx.needs_input_grad[0] else None, dgamma if (weight is not None and ctx.needs_input_grad[1]) else None,
                 dbeta if (bias is not None and ctx.needs_input_grad[2]) else None, None, None)
 
 
-def fusable2d16(bn, relu_module, x):
-    """The plain case of the (BatchNorm2d, ReLU) pair on a float16 / bfloat16 map x [N, C, H, W] the 16-bit op covers."""
+class _BatchNorm2dReLU16(_BatchNorm2dReLU):
+    """The same Function under the name a 16-bit map's grad_fn shows (`_BatchNorm2dReLU16Backward`): what says that no fp32 op ran."""
+
+
+def _plain_forward(module):
+    """No hooks, and `forward` is the class's own (not replaced on the instance)."""
+    return _plain(module) and "forward" not in module.__dict__
+
+
+def _fusable2d(bn, relu_module, x, dtypes, autocast_ok, params_ok):
+    """The plain case of the (BatchNorm2d, ReLU) pair on a map x [N, C, H, W] of one of `dtypes`.  The two routes differ in what they
+    accept under autocast (`autocast_ok()`) and in the dtypes of the module's parameters and buffers (`params_ok(bn, x)`)."""
     if not _ENABLED or type(bn) is not nn.BatchNorm2d or not _plain_forward(bn):
         return False
     if relu_module is not None and (type(relu_module) is not nn.ReLU or not _plain_forward(relu_module)):
         return False
-    if not (torch.is_tensor(x) and x.is_cuda and x.dtype in _DT16 and x.dim() == 4):
+    if not (torch.is_tensor(x) and x.is_cuda and x.dtype in dtypes and x.dim() == 4):
         return False
     if not x.is_contiguous() or x.shape[1] != bn.num_features:   # (channels_last maps are not NCHW-contiguous: torch's modules run)
         return False
-    if torch.is_autocast_enabled() and not _ops.mixed_precision():   # the rule of fusable16
+    if torch.is_autocast_enabled() and not autocast_ok():
         return False
     n, _, h, w = x.shape
     if n * h * w < (2 if bn.training else 1):   # torch raises for a single value per channel in training mode: let it
         return False
     if (bn.weight is None) != (bn.bias is None):
         return False
-    pdt = _param_dtype(bn)
-    if pdt is False or pdt not in (None, torch.float32, x.dtype):
+    if not params_ok(bn, x):
         return False
     for t in (bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked):
         if t is not None and t.device != x.device:
             return False
     return True
+
+
+def _params_fp32(bn, x):
+    return all(t is None or t.dtype == torch.float32 for t in (bn.weight, bn.bias, bn.running_mean, bn.running_var))
+
+
+def _params_fp32_or_x(bn, x):
+    pdt = _param_dtype(bn)   # (False: mixed, or not on the GPU)
+    return pdt is not False and pdt in (None, torch.float32, x.dtype)
+
+
+def fusable2d(bn, relu_module, x):
+    """The plain case of the (BatchNorm2d, ReLU) pair on an fp32 map x [N, C, H, W] the fused op covers: never under autocast, fp32
+    parameters."""
+    return _fusable2d(bn, relu_module, x, (torch.float32,), lambda: False, _params_fp32)
+
+
+def fusable2d16(bn, relu_module, x):
+    """The plain case of the (BatchNorm2d, ReLU) pair on a float16 / bfloat16 map x [N, C, H, W] the 16-bit op covers: under autocast
+    only in mixed precision (the rule of fusable16), parameters all fp32 or all of x's dtype."""
+    return _fusable2d(bn, relu_module, x, _DT16, _ops.mixed_precision, _params_fp32_or_x)
+
+
+def batch_norm2d_relu(bn, x, relu_module=None):
+    """y = relu?(bn(x)) for a contiguous fp32 map x [N, C, H, W] on the GPU, or None when the fused path does not apply."""
+    if not fusable2d(bn, relu_module, x):
+        return None
+    ext = _nat.torch_ext()
+    if ext is not None:
+        return ext.batch_norm2d_relu(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked, bn.training,
+                                     -1.0 if bn.momentum is None else float(bn.momentum), float(bn.eps), relu_module is not None)
+    return _BatchNorm2dReLU.apply(x, bn.weight, bn.bias, bn, relu_module is not None)
 
 
 def batch_norm2d_relu16(bn, x, relu_module=None):

@@ -1085,8 +1085,8 @@ int fv2p_batchnorm2d_backward(const float* x, const float* dz, int64_t n, int c,
 
 /* ---- BatchNorm2d (+ReLU) on contiguous float16 / bfloat16 NCHW maps [n, c, hw] ------------------------------------------------
  * The layer above on the 16-bit volume that fv2p_sparse_to_dense_h writes and the BEV backbones' convolutions keep
- * (csrc/batchnorm2d_h.hip), with the conventions of the 16-bit row op: `dtype` (FV2P_DT_F16 / FV2P_DT_BF16) names the format of
- * x, y, dz and dx; `param_dtype` is 0 (fp32) or equal to `dtype` and names the format of gamma, beta, running_mean, running_var,
+ * (csrc/batchnorm2d.hip: the same kernels in a 16-bit format), with the conventions of the 16-bit row op: `dtype` (FV2P_DT_F16 /
+ * FV2P_DT_BF16) names the format of x, y, dz and dx; `param_dtype` is 0 (fp32) or equal to `dtype` and names the format of gamma, beta, running_mean, running_var,
  * dgamma and dbeta; mean and invstd are ALWAYS fp32.  The dtype checks come first: any other value returns FV2P_EINVAL with
  * "dtype" in the message.  Every argument check returns before anything is launched and leaves the outputs untouched
  * (FV2P_EINVAL, FV2P_ELIMIT, FV2P_EWORKSPACE).  No map is converted to fp32 in memory: the workspace holds the fp64 partials and

@@ -1,4 +1,4 @@
-"""GPU: BatchNorm2d (+ReLU) on float16 / bfloat16 NCHW maps (csrc/batchnorm2d_h.hip) through the raw C ABI and through
+"""GPU: BatchNorm2d (+ReLU) on float16 / bfloat16 NCHW maps (the 16-bit instances of csrc/batchnorm2d.hip) through the raw C ABI and through
 pcdet.ops.spconv.norm.batch_norm2d_relu16.  A map [n, c, hw] is the rows [n * hw, c] of bn_half_cases.py by a permutation, so its exact
 cases, `round64_to`, `UNIT`, `fwd_error` and `bwd_error` apply as they are: the kernel's expressions are the ones whose error terms those
 functions derive term by term.
@@ -13,7 +13,8 @@ functions derive term by term.
   3. float16 underflow: positive pre-activations below 2^-25 are stored as zeros and get zero dx;
   4. the option matrix (affine, tracking, momentum, train / eval, ReLU) by the same bound;
   5. two runs are bit-identical;  6. a non-contiguous dz gives the bits of its contiguous copy;  7. no fp32 copy of x or dz;
-  8. argument checks leave the outputs untouched;  9. what the route declines."""
+  8. argument checks leave the outputs untouched;  9. what the route declines;
+  10. on values that fp32, float16 and bfloat16 all hold, the three formats' kernels give the same bits (one kernel source)."""
 import functools
 import itertools
 
@@ -459,3 +460,51 @@ def test_what_the_16_bit_route_declines(gpu, dtype):
             assert y is not None and y.dtype == dtype
         finally:
             spconv.set_mixed_precision(False)
+
+
+# ---- 10. the three formats agree -----------------------------------------------------------------------------------------------------
+def _bits(t):
+    return t.view({torch.float32: torch.int32, torch.int64: torch.int64}.get(t.dtype, torch.int16))
+
+
+def _cross_format_call(x32, dz32, gamma, beta, dtype):
+    """Training forward (ReLU, tracked statistics), then backward with batch_stats = 0 and relu = 0 on that call's mean / invstd, through
+    the raw C ABI with fp32 parameters (param_dtype 0): the fp32 entry points for torch.float32, the _h ones otherwise."""
+    n, c, h, w = x32.shape
+    hw, gpu = h * w, x32.device
+    sfx, fmt = ("", ()) if dtype == torch.float32 else ("_h", (DT_CODE[dtype], 0))
+    x, dz = x32.to(dtype), dz32.to(dtype)
+    assert torch.equal(x.float(), x32) and torch.equal(dz.float(), dz32)   # the grid is exact in the format
+    mean, invstd, dgamma, dbeta = (torch.full((c,), FILL, device=gpu) for _ in range(4))
+    rm, rv = torch.linspace(-1.0, 1.0, c, device=gpu), torch.linspace(0.5, 2.0, c, device=gpu)
+    nbt = torch.full((), 3, dtype=torch.int64, device=gpu)
+    y, dx = torch.full_like(x, FILL), torch.full_like(x, FILL)
+    ws = nat.workspace(nat.call("fv2p_batchnorm2d%s_ws_bytes" % sfx, n, c, hw), gpu)
+    nat.call("fv2p_batchnorm2d_forward" + sfx, x, n, c, hw, 1e-3, 0.01, gamma, beta, 1, rm, rv, nbt, mean, invstd, y, *fmt, ws, ws.numel(), nat.stream())
+    nat.call("fv2p_batchnorm2d_backward" + sfx, x, dz, n, c, hw, mean, invstd, gamma, beta, 0, 0, dx, dgamma, dbeta, *fmt, ws, ws.numel(),
+             nat.stream())
+    torch.cuda.synchronize()
+    return dict(mean=mean, invstd=invstd, running_mean=rm, running_var=rv, num_batches_tracked=nbt, dbeta=dbeta, y=y, dx=dx)
+
+
+@pytest.mark.parametrize("shape", [(2, 3, 5, 7), (2, 4, 1, C16 + 8)], ids=lambda s: "x".join(str(v) for v in s))
+def test_the_three_formats_agree_bit_for_bit_on_values_all_of_them_hold(gpu, shape):
+    """x and dz on the grid k / 8, |k| <= 64: exact in fp32, float16 and bfloat16 (7 significant bits).  Their sums and sums of squares
+    are multiples of 1 / 64 below 2^36 units: exact in fp64 in any order, so the per-thread orders of the width-4 and width-8 kernels
+    cannot show.  (2, 3, 5, 7) takes the element path in every format, (2, 4, 1, chunk + 8) the vector path with two chunks per plane
+    and a short tail.  The statistics are then the same fp64 values, y the same fp32 expression rounded once, and with batch_stats = 0
+    and relu = 0 (c1 = c2 = 0, no mask: float16 underflow cannot enter) so is dx; dbeta is the exact sum of dz.  Nothing is a tolerance."""
+    n, c, h, w = shape
+    rng = np.random.default_rng(n * 1009 + c * 17 + h * w)
+    grid = lambda: torch.from_numpy(rng.integers(-64, 65, size=shape).astype(np.float32) / 8).to(gpu)
+    x32, dz32 = grid(), grid()
+    gamma = torch.from_numpy(rng.uniform(0.5, 1.5, size=c).astype(np.float32)).to(gpu)
+    beta = torch.from_numpy(rng.uniform(-0.75, 0.75, size=c).astype(np.float32)).to(gpu)
+    ref = _cross_format_call(x32, dz32, gamma, beta, torch.float32)
+    assert int(ref["num_batches_tracked"].item()) == 4 and not bool((ref["y"] == FILL).any())
+    for dtype in DTYPES:
+        got = _cross_format_call(x32, dz32, gamma, beta, dtype)
+        for k in ("mean", "invstd", "running_mean", "running_var", "num_batches_tracked", "dbeta"):
+            assert torch.equal(_bits(got[k]), _bits(ref[k])), (dtype, k)
+        for k in ("y", "dx"):
+            assert got[k].dtype == dtype and torch.equal(_bits(got[k]), _bits(ref[k].to(dtype))), (dtype, k)

@@ -942,7 +942,7 @@ def _write(lines, out_path):
 
 
 def bn2d16(out_path=None):
-    """BatchNorm2d(eps=1e-3, momentum=0.01) + ReLU on the BEV maps in 16-bit storage (csrc/batchnorm2d_h.hip), forward and forward +
+    """BatchNorm2d(eps=1e-3, momentum=0.01) + ReLU on the BEV maps in 16-bit storage (the 16-bit instances of csrc/batchnorm2d.hip), forward and forward +
     backward: the 16-bit op, the fp32 op on fp32 tensors of the same shape, and nn.BatchNorm2d + nn.ReLU on the same 16-bit tensors.
     From bytes alone the 16-bit op should take half the fp32 op's time; the measured ratio stands next to that.  Each figure: the median
     of ROUNDS windows of REPS calls, the routes taken alternately in one process; +- is half the range of the windows."""
