@@ -35,6 +35,7 @@ from pcdet.ops.roiaware_pool3d import roiaware_pool3d_utils
 from pcdet.ops.roipoint_pool3d import roipoint_pool3d_utils
 from pcdet.models.backbones_3d.pfe import bev_grid_pooling
 from pcdet.ops.spconv import norm as _norm
+from pcdet.ops.spconv import head as _head
 
 import fv2p_native as _nat
 
@@ -501,9 +502,15 @@ class AnchorHead(nn.Module):
     def forward(self, feat, gt):
         cfg = self.cfg
         b = feat.shape[0]
-        cls = self.conv_cls(feat).permute(0, 2, 3, 1).reshape(b, -1, 1)
-        box = self.conv_box(feat).permute(0, 2, 3, 1).reshape(b, -1, 7)
-        dirs = self.conv_dir_cls(feat).permute(0, 2, 3, 1).reshape(b, -1, cfg.num_dir_bins)
+        if KERNEL_GLUE:
+            # the three 1x1 convs as one kernel per direction that reads the NCHW map as it stands and writes the position-major outputs
+            # (csrc/head1x1.hip); whenever the situation is not the plain one run_heads calls the modules, as below
+            cls, box, dirs = _head.run_heads((self.conv_cls, self.conv_box, self.conv_dir_cls), feat)
+            cls, box, dirs = cls.reshape(b, -1, 1), box.reshape(b, -1, 7), dirs.reshape(b, -1, cfg.num_dir_bins)
+        else:
+            cls = self.conv_cls(feat).permute(0, 2, 3, 1).reshape(b, -1, 1)
+            box = self.conv_box(feat).permute(0, 2, 3, 1).reshape(b, -1, 7)
+            dirs = self.conv_dir_cls(feat).permute(0, 2, 3, 1).reshape(b, -1, cfg.num_dir_bins)
         labels, reg_t = self.assign(gt)
         if cls.is_cuda and cfg.num_dir_bins == 2 and KERNEL_GLUE:
             # the three losses and their logit gradients in one pass (csrc/targets.hip); anchor_losses_tensor_ops states the same

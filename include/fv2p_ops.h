@@ -1117,6 +1117,32 @@ int fv2p_batchnorm2d_backward_h(const void* x, const void* dz, int64_t n, int c,
                                 void* dgamma, void* dbeta, int dtype, int param_dtype, void* ws, size_t ws_bytes,
                                 fv2p_stream_t stream);
 
+/* ---- Multi-head 1x1 convolution over a contiguous fp32 NCHW map, outputs position-major ---------------------------------------
+ * The three 1x1 nn.Conv2d of the reference's anchor head (conv_cls, conv_box, conv_dir_cls: pcdet/models/dense_heads/
+ * anchor_head_single.py:21-37) and the `permute(0, 2, 3, 1).contiguous()` its forward() applies to each output (:48-60), as one
+ * kernel per direction (csrc/head1x1.hip; forward and backward data on v_mfma_f32_16x16x4_f32).  x is [b, cin, hw] (hw = H * W) and is read as it stands, once
+ * per direction; head k has the module's own weight w_k [c_k, cin] and bias_k [c_k] (NULL: no bias) - nothing is repacked or kept
+ * between calls; y_k, dy_k are [b * hw, c_k].  One to three heads, packed to the front (c1 == 0: one head; c2 == 0: two), with
+ * c0 + c1 + c2 <= 64 and b * hw < 2^30 (FV2P_ELIMIT otherwise); absent heads pass NULL pointers.  Any cin >= 1 and any hw: maps
+ * with hw % 4 == 0 and a 16-byte aligned base move 16 bytes per lane, others one element.
+ *   fv2p_head1x1_forward          : y_k[g][j] = sum_c x[n][c][p] * w_k[j][c] + bias_k[j], g = n * hw + p.
+ *   fv2p_head1x1_backward_data    : dx[n][c][p] = sum_k sum_j w_k[j][c] * dy_k[g][j], written once.
+ *   fv2p_head1x1_backward_weights : dw_k[j][c] = sum_g dy_k[g][j] * x[n][c][p] and db_k[j] = sum_g dy_k[g][j] (db_k NULL: not
+ *                                   wanted).  Two launches: partial tiles over a fixed split of the positions, accumulated on
+ *                                   v_mfma_f64_16x16x4_f64 (exact products, fp64 sums), then a fold of the fp64 partials in split
+ *                                   order with one rounding to fp32.  No atomics: bit-identical from run to run.
+ * Workspace for _backward_weights: fv2p_head1x1_ws_bytes(b, cin, hw, c0, c1, c2) (a pure host function; 0 for a shape the op does
+ * not take). */
+size_t fv2p_head1x1_ws_bytes(int64_t b, int cin, int64_t hw, int c0, int c1, int c2);
+int fv2p_head1x1_forward(const float* x, int64_t b, int cin, int64_t hw, const float* w0, const float* w1, const float* w2,
+                         const float* bias0, const float* bias1, const float* bias2, int c0, int c1, int c2, float* y0, float* y1,
+                         float* y2, fv2p_stream_t stream);
+int fv2p_head1x1_backward_data(const float* dy0, const float* dy1, const float* dy2, int64_t b, int cin, int64_t hw, const float* w0,
+                               const float* w1, const float* w2, int c0, int c1, int c2, float* dx, fv2p_stream_t stream);
+int fv2p_head1x1_backward_weights(const float* x, const float* dy0, const float* dy1, const float* dy2, int64_t b, int cin,
+                                  int64_t hw, int c0, int c1, int c2, float* dw0, float* dw1, float* dw2, float* db0, float* db1,
+                                  float* db2, void* ws, size_t ws_bytes, fv2p_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
