@@ -1906,7 +1906,9 @@ __global__ __launch_bounds__(256) void conv_wgrad_pairs(WgradPairArgs a, float* 
 // (four MFMAs, output columns 4m + {0..3}), for the feature side component w of wave w (output rows 4m + w): one
 // ds_read_b128 + one ds_read_b32 per four MFMAs instead of five ds_read_b32.  A lane therefore owns runs of four
 // adjacent dW columns and the partial tile is written with float4 stores.
-template <int AS, int BS, int ST>
+// FINE (fv2p_sparse_conv_wgrad_pairs_fine): the MFMA accumulators hold the products of 16 pairs only and are folded into float64 running
+// sums, so the error of a chunk is that of its 16-term FMA chains and not of one chain over all its (up to 512) pairs.
+template <int AS, int BS, int ST, bool FINE = false>
 __global__ __launch_bounds__(256) void conv_wgrad_pairs_dma(WgradPairArgs a, float* __restrict__ partial) {
   constexpr int CS = AS * 64, CG = BS * 64;             // ST = pairs per stage
   constexpr int ROWF = CS, ROWG = CG;                   // floats per staged row
@@ -1953,6 +1955,13 @@ __global__ __launch_bounds__(256) void conv_wgrad_pairs_dma(WgradPairArgs a, flo
   for (int i = 0; i < AS; ++i)
 #pragma unroll
     for (int j = 0; j < BS * 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  double tot[FINE ? AS : 1][FINE ? BS * 4 : 1][4];
+#pragma unroll
+  for (int i = 0; i < (FINE ? AS : 1); ++i)
+#pragma unroll
+    for (int j = 0; j < (FINE ? BS * 4 : 1); ++j)
+#pragma unroll
+      for (int reg = 0; reg < 4; ++reg) tot[i][j][reg] = 0.0;
   PreNorm1 pn[AS];
   const bool pre = a.pre_mean != nullptr;   // uniform
 #pragma unroll
@@ -1983,6 +1992,18 @@ __global__ __launch_bounds__(256) void conv_wgrad_pairs_dma(WgradPairArgs a, flo
           acc[i][j * 4 + 2] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[i], bv[j].z, acc[i][j * 4 + 2], 0, 0, 0);
           acc[i][j * 4 + 3] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[i], bv[j].w, acc[i][j * 4 + 3], 0, 0, 0);
         }
+      if constexpr (FINE) {
+        if ((sl & 3) == 3 || (sl + 1) * 4 >= npair) {   // uniform: 16 pairs multiplied, or the stage's last ones
+#pragma unroll
+          for (int i = 0; i < AS; ++i)
+#pragma unroll
+            for (int j = 0; j < BS * 4; ++j) {
+#pragma unroll
+              for (int reg = 0; reg < 4; ++reg) tot[i][j][reg] += static_cast<double>(acc[i][j][reg]);
+              acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+            }
+        }
+      }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
@@ -1997,7 +2018,9 @@ __global__ __launch_bounds__(256) void conv_wgrad_pairs_dma(WgradPairArgs a, flo
 #pragma unroll
       for (int j = 0; j < BS; ++j)
         *reinterpret_cast<float4*>(&out[static_cast<long long>(cin) * CG + 4 * (m + 16 * j)]) =
-            make_float4(acc[i][j * 4 + 0][reg], acc[i][j * 4 + 1][reg], acc[i][j * 4 + 2][reg], acc[i][j * 4 + 3][reg]);
+            FINE ? make_float4(static_cast<float>(tot[FINE ? i : 0][FINE ? j * 4 + 0 : 0][reg]), static_cast<float>(tot[FINE ? i : 0][FINE ? j * 4 + 1 : 0][reg]),
+                               static_cast<float>(tot[FINE ? i : 0][FINE ? j * 4 + 2 : 0][reg]), static_cast<float>(tot[FINE ? i : 0][FINE ? j * 4 + 3 : 0][reg]))
+                 : make_float4(acc[i][j * 4 + 0][reg], acc[i][j * 4 + 1][reg], acc[i][j * 4 + 2][reg], acc[i][j * 4 + 3][reg]);
     }
 }
 
@@ -2979,10 +3002,10 @@ extern "C" int fv2p_sparse_conv_wgrad_pairs(const float* src, int64_t n_src, int
                                           nullptr, nullptr, 0, ws, ws_bytes, stream_);
 }
 
-extern "C" int fv2p_sparse_conv_wgrad_pairs_pre(const float* src, int64_t n_src, int c_src, const float* grad, int64_t n_grad, int c_dst,
-                                                const int* pairs, const int* pair_num, int kvol, int64_t pair_len, int side_src,
-                                                float* dweight, const float* pre_mean, const float* pre_invstd, const float* pre_gamma,
-                                                const float* pre_beta, int pre_relu, void* ws, size_t ws_bytes, fv2p_stream_t stream_) {
+static int wgrad_pairs_impl(const float* src, int64_t n_src, int c_src, const float* grad, int64_t n_grad, int c_dst,
+                            const int* pairs, const int* pair_num, int kvol, int64_t pair_len, int side_src,
+                            float* dweight, const float* pre_mean, const float* pre_invstd, const float* pre_gamma,
+                            const float* pre_beta, int pre_relu, void* ws, size_t ws_bytes, fv2p_stream_t stream_, bool fine) {
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   FV2P_REQUIRE((pre_mean == nullptr) == (pre_invstd == nullptr), FV2P_EINVAL, "sparse_conv_wgrad_pairs: pre_mean and pre_invstd come together");
   FV2P_REQUIRE(c_src >= 1 && c_dst >= 1 && kvol >= 1 && pair_len >= 0 && (side_src == 0 || side_src == 1), FV2P_EINVAL,
@@ -3019,9 +3042,14 @@ extern "C" int fv2p_sparse_conv_wgrad_pairs_pre(const float* src, int64_t n_src,
         static int st_env = -1;
         if (st_env < 0) { const char* e = FV2P_DEV_ENV("FV2P_WGRAD_ST"); st_env = e ? atoi(e) : 0; }
         const int st64 = st_env ? st_env : (static_cast<long long>(chunks) * kvol > 1200 ? 32 : 64);
-        const int st = (as + bs <= 2) ? st64 : 32;
+        const int st = (as + bs <= 2 && !fine) ? st64 : 32;
         const size_t lds = static_cast<size_t>(2) * st * (cs + cd) * sizeof(float) + 2 * kPairsMax * sizeof(int);
-        if (as == 1 && bs == 1 && st == 64) hipLaunchKernelGGL((conv_wgrad_pairs_dma<1, 1, 64>), grid, block, lds, stream, a, partial);
+        if (fine) {   // the 16-pair chains folded in float64 (fv2p_sparse_conv_wgrad_pairs_fine)
+          if (as == 1 && bs == 1) hipLaunchKernelGGL((conv_wgrad_pairs_dma<1, 1, 32, true>), grid, block, lds, stream, a, partial);
+          else if (as == 2 && bs == 1) hipLaunchKernelGGL((conv_wgrad_pairs_dma<2, 1, 32, true>), grid, block, lds, stream, a, partial);
+          else if (as == 1 && bs == 2) hipLaunchKernelGGL((conv_wgrad_pairs_dma<1, 2, 32, true>), grid, block, lds, stream, a, partial);
+          else hipLaunchKernelGGL((conv_wgrad_pairs_dma<2, 2, 32, true>), grid, block, lds, stream, a, partial);
+        } else if (as == 1 && bs == 1 && st == 64) hipLaunchKernelGGL((conv_wgrad_pairs_dma<1, 1, 64>), grid, block, lds, stream, a, partial);
         else if (as == 1 && bs == 1) hipLaunchKernelGGL((conv_wgrad_pairs_dma<1, 1, 32>), grid, block, lds, stream, a, partial);
         else if (as == 2 && bs == 1) hipLaunchKernelGGL((conv_wgrad_pairs_dma<2, 1, 32>), grid, block, lds, stream, a, partial);
         else if (as == 1 && bs == 2) hipLaunchKernelGGL((conv_wgrad_pairs_dma<1, 2, 32>), grid, block, lds, stream, a, partial);
@@ -3036,4 +3064,19 @@ extern "C" int fv2p_sparse_conv_wgrad_pairs_pre(const float* src, int64_t n_src,
   }
   FV2P_LAUNCH_CHECK();
   return 0;
+}
+
+extern "C" int fv2p_sparse_conv_wgrad_pairs_pre(const float* src, int64_t n_src, int c_src, const float* grad, int64_t n_grad, int c_dst,
+                                                const int* pairs, const int* pair_num, int kvol, int64_t pair_len, int side_src,
+                                                float* dweight, const float* pre_mean, const float* pre_invstd, const float* pre_gamma,
+                                                const float* pre_beta, int pre_relu, void* ws, size_t ws_bytes, fv2p_stream_t stream_) {
+  return wgrad_pairs_impl(src, n_src, c_src, grad, n_grad, c_dst, pairs, pair_num, kvol, pair_len, side_src, dweight, pre_mean, pre_invstd, pre_gamma,
+                          pre_beta, pre_relu, ws, ws_bytes, stream_, false);
+}
+
+extern "C" int fv2p_sparse_conv_wgrad_pairs_fine(const float* src, int64_t n_src, int c_src, const float* grad, int64_t n_grad, int c_dst,
+                                                 const int* pairs, const int* pair_num, int kvol, int64_t pair_len, int side_src,
+                                                 float* dweight, void* ws, size_t ws_bytes, fv2p_stream_t stream_) {
+  return wgrad_pairs_impl(src, n_src, c_src, grad, n_grad, c_dst, pairs, pair_num, kvol, pair_len, side_src, dweight, nullptr, nullptr, nullptr,
+                          nullptr, 0, ws, ws_bytes, stream_, true);
 }

@@ -1109,6 +1109,35 @@ std::vector<std::vector<at::Tensor>> build_rulebook_chain(const at::Tensor& root
   return out;
 }
 
+// Tables of the first BEV convolution over the sparse rows (fv2p_bev_entry_tables) -> [tab_out, tab_in, pairs, pair_num]; tab_out with room
+// for a tiling plan behind it, built here when `plan`; pairs / pair_num undefined unless `want_pairs` (and n > 0).
+std::vector<at::Tensor> bev_entry_tables(const at::Tensor& indices, int64_t batch, int64_t depth, int64_t height, int64_t width, bool want_pairs,
+                                         bool plan) {
+  TORCH_CHECK(indices.is_cuda() && indices.scalar_type() == at::kInt && indices.dim() == 2 && indices.size(1) == 4 && indices.is_contiguous(),
+              "bev_entry_tables: indices must be a contiguous CUDA int32 [N, 4] tensor");
+  c10::DeviceGuard guard(indices.device());
+  void* stream = cur_stream(indices);
+  const int64_t n = indices.size(0), kvol = 9 * depth, n_dst = batch * height * width;
+  const auto iopt = indices.options();
+  at::Tensor tab_out = at::empty({kvol * n_dst + fv2p_conv_plan_ints(n_dst)}, iopt).narrow(0, 0, kvol * n_dst).view({kvol, n_dst});
+  at::Tensor tab_in = at::empty({kvol, n}, iopt), pairs, pnum;
+  if (want_pairs && n > 0) {
+    pairs = at::empty({kvol, 2, n}, iopt);
+    pnum = at::empty({kvol}, iopt);
+  }
+  at::Tensor ws = workspace(fv2p_bev_entry_tables_ws_bytes(n, static_cast<int>(depth)), indices, stream);
+  check(fv2p_bev_entry_tables(indices.data_ptr<int>(), n, static_cast<int>(batch), static_cast<int>(depth), static_cast<int>(height),
+                              static_cast<int>(width), tab_out.data_ptr<int>(), tab_in.data_ptr<int>(), pairs.defined() ? pairs.data_ptr<int>() : nullptr,
+                              pnum.defined() ? pnum.data_ptr<int>() : nullptr, ws.data_ptr(), static_cast<size_t>(ws.numel()), stream),
+        "fv2p_bev_entry_tables");
+  if (plan && n_dst > 0) {
+    at::Tensor pws = workspace(fv2p_conv_plan_ws_bytes(n_dst), indices, stream);
+    check(fv2p_conv_plan_build(tab_out.data_ptr<int>(), static_cast<int>(kvol), n_dst, pws.data_ptr(), static_cast<size_t>(pws.numel()), stream),
+          "fv2p_conv_plan_build");
+  }
+  return {tab_out, tab_in, pairs, pnum};
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -1124,7 +1153,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "voxelise a batch of clouds + MeanVFE + collate, without the GIL");
   m.def("build_rulebook_chain", &build_rulebook_chain, py::call_guard<py::gil_scoped_release>(),
         "build a chain of rulebooks (and pair lists) from root coordinates, without the GIL");
-  m.def("conv_fin", &conv_fin, "sparse conv with its BatchNorm statistics finalised by the launch (and optionally the source rows' BatchNorm + ReLU on the gather) -> [y, saved]");
+  m.def("bev_entry_tables", &bev_entry_tables, "tables (and pair lists, tiling plan) of the first BEV conv over the sparse rows -> [tab_out, tab_in, pairs, pair_num]");
+  m.def("conv_fin", &conv_fin,"sparse conv with its BatchNorm statistics finalised by the launch (and optionally the source rows' BatchNorm + ReLU on the gather) -> [y, saved]");
   m.def("bn_apply", &bn_apply, "relu?((x - mean) * invstd * gamma + beta [+ residual]) with finalised statistics, one launch");
   m.def("prenorm_supported", &prenorm_supported, "the conv kernel of this shape can normalise its source rows on the gather");
   m.def("set_bn_fold", &set_bn_fold, "round-6 arrangement of conv / BatchNorm / residual blocks on (default) or off (the round-5 one)");

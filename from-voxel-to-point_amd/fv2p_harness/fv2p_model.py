@@ -36,6 +36,7 @@ from pcdet.ops.roipoint_pool3d import roipoint_pool3d_utils
 from pcdet.models.backbones_3d.pfe import bev_grid_pooling
 from pcdet.ops.spconv import norm as _norm
 from pcdet.ops.spconv import head as _head
+from pcdet.ops.spconv import bev_entry as _bev_entry
 
 import fv2p_native as _nat
 
@@ -267,6 +268,7 @@ class BEVBackbone(nn.Module):
         self.num_bev_features = sum(cfg.bev_up_filters)
 
     def forward(self, x):
+        """x: the dense map [B, C * D, H, W], or the SparseConvTensor HeightCompression would make it from (height_compression.py:10-26)."""
         ups = []
         for blk, de in zip(self.blocks, self.deblocks):
             x = self._block(blk, x)
@@ -274,13 +276,27 @@ class BEVBackbone(nn.Module):
         return torch.cat(ups, dim=1)
 
     @staticmethod
+    def height_compression(sp):
+        dense = sp.dense()
+        return dense.view(dense.shape[0], dense.shape[1] * dense.shape[2], dense.shape[3], dense.shape[4])
+
+    @staticmethod
     def _block(blk, x):
         """blk(x) with the leading ZeroPad2d(1) + Conv2d(padding=0) pair of the reference's block (base_bev_backbone.py:27-33) issued as
         one zero-padded convolution: the same sums, without the padded copy of the map (108 MB written and read again at the FV2P size,
-        and its slice copy in the backward pass).  The module list keeps the reference's layout (state dicts load unchanged)."""
+        and its slice copy in the backward pass).  The module list keeps the reference's layout (state dicts load unchanged).
+        A SparseConvTensor x (the first block) goes through that pair as a sparse convolution over its rows while its fill allows
+        (pcdet.ops.spconv.bev_entry: no dense map, no products with its zeros), and through HeightCompression otherwise."""
         mods = list(blk)
-        if (KERNEL_GLUE and len(mods) >= 2 and isinstance(mods[0], nn.ZeroPad2d) and type(mods[1]) is nn.Conv2d and "forward" not in mods[1].__dict__
-                and tuple(mods[0].padding) == (1, 1, 1, 1) and tuple(mods[1].padding) == (0, 0) and mods[1].padding_mode == "zeros"):
+        pair = (KERNEL_GLUE and len(mods) >= 2 and isinstance(mods[0], nn.ZeroPad2d) and type(mods[1]) is nn.Conv2d and "forward" not in mods[1].__dict__
+                and tuple(mods[0].padding) == (1, 1, 1, 1) and tuple(mods[1].padding) == (0, 0) and mods[1].padding_mode == "zeros")
+        if not torch.is_tensor(x):
+            c = mods[1] if pair else None
+            if (pair and c.bias is None and tuple(c.stride) == (1, 1) and tuple(c.dilation) == (1, 1) and c.groups == 1
+                    and _bev_entry.route(x, c.weight) == "sparse"):
+                return _norm.run_maps(mods[2:], _bev_entry.bev_entry_conv(x, c.weight))
+            x = BEVBackbone.height_compression(x)
+        if pair:
             c = mods[1]
             x = F.conv2d(x, c.weight, c.bias, c.stride, (1, 1), c.dilation, c.groups)
             mods = mods[2:]
@@ -1119,10 +1135,10 @@ class FV2PDetector(nn.Module):
         return loss_rpn + loss_point + loss_rcnn
 
     def dense_branch(self, out, b, gt_boxes):
-        dense = out.dense()                                                      # HeightCompression (height_compression.py:10-26)
-        spatial = dense.view(b, dense.shape[1] * dense.shape[2], dense.shape[3], dense.shape[4])
         if getattr(self, "bev_channels_last", False):
-            spatial = spatial.contiguous(memory_format=torch.channels_last)
+            spatial = BEVBackbone.height_compression(out).contiguous(memory_format=torch.channels_last)
+        else:
+            spatial = out   # HeightCompression (height_compression.py:10-26) is the BEV backbone's: its first conv may not need the map
         bev = self.backbone_2d(spatial)
         loss_rpn, prop_scores, prop_boxes = self.dense_head(bev, gt_boxes)
         return bev, loss_rpn, prop_scores, prop_boxes

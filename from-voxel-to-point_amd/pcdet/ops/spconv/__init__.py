@@ -1,5 +1,6 @@
 """pcdet.ops.spconv — drop-in for the reference's vendored spconv 1.x package (pcdet/ops/spconv/__init__.py:15-40): the same public
 names, on the HIP kernels of libfv2p_ops.  Additions of this package sit at the end of `__all__`."""
+from . import bev_entry as _bev_entry
 from . import conv as _conv
 from . import group as _group
 from . import modules as _modules
@@ -17,7 +18,7 @@ _REFERENCE_NAMES = {
     _group: ("SparseGroup3d", "SubMGroup3d"),
 }
 _OWN_NAMES = {_prefetch: ("rulebook_recipe", "build_rulebooks", "attach_rulebooks"), _conv: ("defer_weight_gradients", "conv_bn_fold", "materialise_pending", "set_bn_fold", "fold_enabled"),
-              _ops: ("set_mixed_precision", "mixed_precision")}
+              _ops: ("set_mixed_precision", "mixed_precision"), _bev_entry: ("bev_entry_conv",)}
 
 __all__ = []
 for _table in (_REFERENCE_NAMES, _OWN_NAMES):

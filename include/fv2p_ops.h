@@ -297,6 +297,35 @@ int fv2p_sparse_conv_wgrad_pairs(const float* src, int64_t n_src, int c_src, con
                                  int c_dst, const int* pairs, const int* pair_num, int kvol, int64_t pair_len,
                                  int side_src, float* dweight, void* ws, size_t ws_bytes, fv2p_stream_t stream);
 
+/* fv2p_sparse_conv_wgrad_pairs with short summation chains: on 64 / 128 channels on both sides (the LDS-DMA kernel's shapes) the MFMA
+ * accumulators take the products of 16 pairs and are folded into float64 running sums, rounded to fp32 once per chunk, so a chunk's
+ * error is that of its 16-term fp32 chains instead of one chain over its up to 512 pairs (dW of a 3 x 3 conv with 150 pairs per offset:
+ * 3.2 x the error of MIOpen's blocked sums with the plain form).  Other shapes run the plain kernels.  Same arguments, same
+ * workspace (fv2p_sparse_conv_wgrad_pairs_ws_bytes), fixed order, no atomics. */
+int fv2p_sparse_conv_wgrad_pairs_fine(const float* src, int64_t n_src, int c_src, const float* grad, int64_t n_grad,
+                                      int c_dst, const int* pairs, const int* pair_num, int kvol, int64_t pair_len,
+                                      int side_src, float* dweight, void* ws, size_t ws_bytes, fv2p_stream_t stream);
+
+/* ---- the first BEV convolution as a sparse convolution with dense output rows ------------------------------------
+ * Replaces HeightCompression's dense map (height_compression.py:10-26: spconv_tensor.dense().view(B, C * D, H, W)) in front of the
+ * first ZeroPad2d(1) + Conv2d(C * D -> Cout, 3 x 3) of BaseBEVBackbone (base_bev_backbone.py:27-33): the tables below drive
+ * fv2p_sparse_conv_rows / fv2p_sparse_conv_wgrad_pairs(_fine) over the sparse rows themselves, so neither the map nor the products with
+ * its zeros exist.  indices [n, 4] (batch, z, y, x) of a tensor with spatial shape (depth, height, width), rows unique per cell;
+ * kvol = 9 * depth offsets k = z * 9 + ky * 3 + kx (depth <= 3); destination rows = all batch * height * width BEV cells,
+ * cell = (b * height + oy) * width + ox.
+ *   tab_out [kvol][batch * height * width]  row at (b, z, oy + ky - 1, ox + kx - 1), the (z, ky, kx) tap of the cell under padding 1,
+ *                                           stride 1; -1 where there is none.  Filled here (also when n == 0).  A caller that passes
+ *                                           FV2P_TAB_PLANNED allocates fv2p_conv_plan_ints(batch * height * width) ints behind it.
+ *   tab_in  [kvol][n]                       the cell a row reaches through offset k; -1 for a cell outside the map and for the
+ *                                           offsets of the other z planes
+ *   pairs [kvol][2][n], pair_num [kvol]     (both may be NULL) the lists of fv2p_rulebook_pairs(tab_in, pad = 0) for
+ *                                           fv2p_sparse_conv_wgrad_pairs: ascending input row inside every offset
+ * No hash, no sort, nothing read back by the host; every table and list is the same from run to run.  A row whose coordinates lie
+ * outside the grid pairs with nothing.  Workspace (for the pair lists only): fv2p_bev_entry_tables_ws_bytes. */
+size_t fv2p_bev_entry_tables_ws_bytes(int64_t n, int depth);
+int fv2p_bev_entry_tables(const int* indices, int64_t n, int batch, int depth, int height, int width, int* tab_out, int* tab_in,
+                          int* pairs, int* pair_num, void* ws, size_t ws_bytes, fv2p_stream_t stream);
+
 /* ---- fused sparse convolution on 16-bit operands ----------------------------------------------
  * What the reference binds as indice_conv_half / indice_conv_backward_half / fused_indice_conv_half (all.cc:36-51), plus
  * bfloat16, which it does not have.  `dtype` names the 16-bit format of EVERY operand and result of a call (features,

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Per-kernel timings on one GPU (events on the launch stream). Not part of the product or of bench.py; used to
-iterate on kernel variants:  python tools/microbench.py [conv|conv16|amp16|bn16|bn2d|bn2d16|bev16|exit16|batch16|dcn|dcn16|dcn16bwd|fps|voxel|nms|all]"""
+iterate on kernel variants:  python tools/microbench.py [conv|conv16|amp16|bn16|bn2d|bn2d16|bev16|beventry|exit16|batch16|dcn|dcn16|dcn16bwd|fps|voxel|nms|all]"""
 import os
 import sys
 import time
@@ -990,6 +990,54 @@ def bn2d16(out_path=None):
     _write(lines, out_path)
 
 
+def beventry(out_path=None):
+    """The first BEV convolution, forward + backward (dX at the rows, dW), on its two routes at the benchmark's map [3, 128 * 2, 200, 176]:
+    `sparse` = pcdet.ops.spconv.bev_entry on the rows (tables, fused conv kernels, two layout copies), `dense` = dense() + F.conv2d (MIOpen)
+    and dense()'s gather.  Rows are clustered (the cells with the highest values of a smooth random field), fill = N / (B * D * H * W).
+    Each figure: the median of ROUNDS windows of REPS calls, the routes taken alternately in one process; +- is half the range of the
+    windows.  The crossover is where the two medians meet (linear between the measured fills); bev_entry.TAU is 0.8 x that."""
+    import torch.nn.functional as F
+    import pcdet.ops.spconv as spconv
+    from pcdet.ops.spconv import bev_entry
+    dev = torch.device("cuda:0")
+    ROUNDS, REPS = 5, 10
+    b, d, h, w, c, cout = 3, 2, 200, 176, 128, 128
+    fills = (0.02, 0.045, 0.1, 0.2, 0.4, 0.8)
+    lines = ["first BEV conv [%d, %d * %d, %d, %d] -> %d, forward + backward, us per call: median of %d windows of %d calls, +- half the range"
+             % (b, c, d, h, w, cout, ROUNDS, REPS), "%-6s %-8s %-16s %-16s %-12s" % ("fill", "rows", "sparse", "dense", "sparse/dense")]
+    torch.manual_seed(0)
+    weight = (torch.randn(cout, c * d, 3, 3, device=dev) / 48).requires_grad_(True)
+    g = torch.randn(b, cout, h, w, device=dev)
+    field = F.interpolate(torch.randn(b * d, 1, h // 8, w // 8, device=dev), size=(h, w), mode="bilinear", align_corners=False).reshape(-1)
+    field = field + 0.05 * torch.randn_like(field)
+    meds = []
+    for fill in fills:
+        n = int(round(fill * b * d * h * w))
+        cells = field.topk(n).indices.sort().values
+        ind = torch.stack([cells // (d * h * w), cells // (h * w) % d, cells // w % h, cells % w], 1).int().contiguous()
+        feats = torch.randn(n, c, device=dev).requires_grad_(True)
+        sp = spconv.SparseConvTensor(feats, ind, [d, h, w], b)
+
+        def both(fn):
+            fn(sp, weight).backward(g)
+            feats.grad = weight.grad = None
+        t = _windows({"sparse": lambda: both(lambda s, wt: bev_entry.bev_entry_conv(s, wt, tau=1.0)), "dense": lambda: both(bev_entry.dense_route)}, ROUNDS, REPS)
+        meds.append((fill, float(np.median(t["sparse"])), float(np.median(t["dense"]))))
+        lines.append("%-6.3f %-8d %-16s %-16s %-12.2f" % (fill, n, _cell(t["sparse"]), _cell(t["dense"]), meds[-1][1] / meds[-1][2]))
+        print(lines[-1], flush=True)
+    cross = None
+    for (f0, s0, d0), (f1, s1, d1) in zip(meds, meds[1:]):
+        if s0 <= d0 and s1 > d1:
+            cross = f0 + (f1 - f0) * (d0 - s0) / ((s1 - d1) + (d0 - s0))
+    if cross is None:
+        ahead = meds[0][1] <= meds[0][2]
+        lines.append("no crossover between the measured fills: sparse %s at all of them%s (bev_entry.TAU = %.3f)"
+                     % ("faster" if ahead else "slower", "; 0.8 x the largest measured fill = %.3f" % (0.8 * fills[-1]) if ahead else "", bev_entry.TAU))
+    else:
+        lines.append("crossover at fill %.3f; 0.8 x crossover = %.3f (bev_entry.TAU = %.3f)" % (cross, 0.8 * cross, bev_entry.TAU))
+    _write(lines, out_path)
+
+
 def bev16(out_path=None):
     """The bilinear gather and its gradient at 3 x 2048 key points on a [3, 256, 200, 176] map in 16-bit storage (fv2p_bev_interp_fwd_h /
     _bwd_h) against the fp32 op on an fp32 map (gradient in the fixed-order form, the only one the 16-bit op has) and against the route
@@ -1324,6 +1372,9 @@ if __name__ == "__main__":
         sys.exit(0)
     if which == "bn2d16":   # python tools/microbench.py bn2d16 [profiles/bn2d_half.txt]
         bn2d16(sys.argv[2] if len(sys.argv) > 2 else None)
+        sys.exit(0)
+    if which == "beventry":   # python tools/microbench.py beventry [profiles/bev_entry.txt]
+        beventry(sys.argv[2] if len(sys.argv) > 2 else None)
         sys.exit(0)
     if which == "bev16":   # python tools/microbench.py bev16 [profiles/bev_half.txt]
         bev16(sys.argv[2] if len(sys.argv) > 2 else None)
