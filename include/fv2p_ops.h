@@ -814,6 +814,31 @@ size_t fv2p_sa_grid_bwd_gather_ws_bytes(int rois, int m, int s);
 int fv2p_sa_grid_bwd_gather(const float* per_point, const float* per_centre, const int* idx, const float* w2, const unsigned char* arg,
                             const float* grad_out, int rois, int n, int m, int s, int c, float* grad_point, float* grad_centre,
                             float* grad_w2, void* ws, size_t ws_bytes, fv2p_stream_t stream);
+/* The fused grid set-abstraction on float16 / bfloat16 rows (csrc/sa_fused_h.hip; dtype = FV2P_DT_F16 / FV2P_DT_BF16): per_point,
+ * per_centre, out, grad_out and the row gradients are 16-bit elements of that one format, idx / arg as above.  w2 [c, c] is in the rows'
+ * format (wd != 0: wd == dtype) or fp32 (wd == 0, the convention of `pd` above: the master weight beside autocast rows); an fp32 w2 is
+ * rounded to nearest even on its way into LDS - the result has the bits of the call on w2.to(dtype), no 16-bit copy is made - and
+ * grad_w2 has w2's format.  No fp32 image of a row tensor exists anywhere.
+ *   forward : h1 = RNE(max(float(P) - float(Q), 0)) is the operand of v_mfma_f32_16x16x32_{f16,bf16}; the maximum over the samples is
+ *     taken over the fp32 accumulators and rounded ONCE at the store; arg is fv2p_sa_grid_fwd's (first sample in sample order whose
+ *     accumulator equals the maximum, 255 where the maximum is 0).
+ *   backward: h1 recomputed as in forward, dh1 = (W2r^T dh2) [h1 > 0] in fp32 accumulators; grad_centre = -sum_s dh1 rounded once;
+ *     grad_point in the fixed-order form only (no atomic form exists, the deterministic switch changes nothing): the dh1 rows are staged
+ *     in the workspace IN 16 BITS (one rounding per addend) and summed per point in fp32 - in ascending sample order inside one workgroup
+ *     per RoI up to m * s = 8192, in the association of fv2p_scatter_add beyond - the total rounded once; grad_point is WRITTEN (rows no sample names are zero); grad_w2 from fp32 partial tiles folded in a fixed order, one rounding
+ *     for a 16-bit w2, none for fp32.  All results are bit-identical from run to run and on any stream.
+ *   An index outside [0, n) reads as a row of zeros and its grad_point entry is dropped; it is never dereferenced.
+ *   c = 64, s in {16, 32}, any n (there is no dP tile in LDS: the fp32 backward's n <= 884 does not apply), rois <= 65535; every pointer
+ *   16-byte aligned.  FV2P_EINVAL before any launch for another dtype or wd, a null pointer, an unsupported shape or alignment;
+ *   FV2P_EWORKSPACE for a workspace below fv2p_sa_grid_bwd_h_ws_bytes (a pure host function: the partial tiles, the entry list, the 16-bit
+ *   dh1 rows [rois * m * s][64] and the workspace of the scatter-add); FV2P_ELIMIT from 2^31 samples or point rows on. */
+int fv2p_sa_grid_supported_h(int n, int m, int s, int c);
+int fv2p_sa_grid_fwd_h(const void* per_point, const void* per_centre, const int* idx, const void* w2, int wd, int rois, int n, int m,
+                       int s, int c, void* out, unsigned char* arg, int dtype, fv2p_stream_t stream);
+size_t fv2p_sa_grid_bwd_h_ws_bytes(int rois, int m, int s);
+int fv2p_sa_grid_bwd_h(const void* per_point, const void* per_centre, const int* idx, const void* w2, int wd, const unsigned char* arg,
+                       const void* grad_out, int rois, int n, int m, int s, int c, void* grad_point, void* grad_centre, void* grad_w2,
+                       int dtype, void* ws, size_t ws_bytes, fv2p_stream_t stream);
 
 /* ---- A13: modulated deformable convolution (DCNv2; DCNv1 = mask of ones) -------------------------
  * Replace DCN.modulated_deform_conv_forward / _backward and DCN.deform_conv_forward / _backward

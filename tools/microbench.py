@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Per-kernel timings on one GPU (events on the launch stream). Not part of the product or of bench.py; used to
-iterate on kernel variants:  python tools/microbench.py [conv|conv16|amp16|bn16|bn2d|bn2d16|bev16|beventry|exit16|batch16|dcn|dcn16|dcn16bwd|fps|voxel|nms|all]"""
+iterate on kernel variants:  python tools/microbench.py [conv|conv16|amp16|bn16|bn2d|bn2d16|bev16|beventry|exit16|batch16|sa16|dcn|dcn16|dcn16bwd|fps|voxel|nms|all]"""
 import os
 import sys
 import time
@@ -1141,6 +1141,60 @@ def dcn16(out_path=None):
     _write(lines, out_path)
 
 
+def sa16(out_path=None):
+    """The fused grid set-abstraction at the RoI head's two shapes (R = 384, N = 512, M = 216, S = 16 / 32) on 16-bit rows, forward and
+    forward + backward.  h16: fv2p_sa_grid_fwd_h / _bwd_h (16-bit weight); f32: the fp32 op on fp32 tensors; grouped: the route 16-bit
+    rows took before - grouping_operation into (R, 64, M, S), 1x1 product, ReLU, amax on the same 16-bit tensors.  Alternating windows
+    as in bn2d16."""
+    from pcdet.ops.pointnet2.pointnet2_batch import fused, pointnet2_utils as bu
+    dev = torch.device("cuda:0")
+    ROUNDS, REPS = 7, 5
+    r, n, m = 384, 512, 216
+    lines = ["fused grid set-abstraction, us per call: median of %d windows of %d calls, +- half the range.  h16: fv2p_sa_grid_fwd_h / _bwd_h; f32: the "
+             "fp32 op on fp32 tensors; grouped: grouping_operation + 1x1 product + ReLU + amax on the same 16-bit tensors" % (ROUNDS, REPS),
+             "%-20s %-9s %-5s %-16s %-16s %-18s %-8s %-11s" % ("(R, N, M, S)", "dtype", "leg", "h16", "f32", "grouped", "h16/f32", "h16/grouped")]
+    g = torch.Generator().manual_seed(0)
+    xyz = (torch.rand(r, n, 3, generator=g) * torch.tensor([7.0, 5.0, 4.0]) - torch.tensor([3.5, 2.5, 2.0])).to(dev)
+    ctr = (torch.rand(r, m, 3, generator=g) * torch.tensor([4.0, 1.6, 1.5]) - torch.tensor([2.0, 0.8, 0.75])).to(dev)
+    p32 = torch.randn(r, n, 64, generator=g).to(dev).requires_grad_(True)
+    q32 = torch.randn(r, m, 64, generator=g).to(dev).requires_grad_(True)
+    w32 = (torch.randn(64, 64, generator=g) * 0.1).to(dev).requires_grad_(True)
+    g32 = torch.randn(r, m, 64, generator=g).to(dev)
+    for radius, s in ((0.8, 16), (1.6, 32)):
+        idx = bu.ball_query(radius, s, xyz, ctr)
+        for dt in (torch.float16, torch.bfloat16):
+            p16, q16, w16 = (t.detach().to(dt).requires_grad_(True) for t in (p32, q32, w32))
+            g16 = g32.to(dt)
+
+            def grouped(p=p16, q=q16, w=w16):
+                gpt = bu.grouping_operation(p.transpose(1, 2).contiguous(), idx)
+                h2 = torch.relu(torch.einsum("oc,rcms->roms", w, torch.relu(gpt - q.transpose(1, 2).unsqueeze(-1))))
+                return h2.amax(dim=-1).transpose(1, 2)
+            fwd, both = {}, {}
+            for name, f, leaves, go in (("h16", lambda: fused.sa_grid_max(p16, q16, idx, w16), (p16, q16, w16), g16),
+                                        ("f32", lambda: fused.sa_grid_max(p32, q32, idx, w32), (p32, q32, w32), g32),
+                                        ("grouped", grouped, (p16, q16, w16), g16)):
+                def fn_fwd(f=f):
+                    with torch.no_grad():
+                        f()
+
+                def fn_both(f=f, leaves=leaves, go=go):
+                    f().backward(go)
+                    for t in leaves:
+                        t.grad = None
+                fwd[name], both[name] = fn_fwd, fn_both
+            for leg, routes in (("fwd", fwd), ("f+b", both)):
+                t = _windows(routes, ROUNDS, REPS)
+                med = {k: np.median(v) for k, v in t.items()}
+                lines.append("%-20s %-9s %-5s %-16s %-16s %-18s %-8.2f %-11.2f" % (str((r, n, m, s)), str(dt).replace("torch.", ""), leg, _cell(t["h16"]),
+                                                                               _cell(t["f32"]), _cell(t["grouped"]), med["h16"] / med["f32"],
+                                                                               med["h16"] / med["grouped"]))
+                print(lines[-1], flush=True)
+            del p16, q16, w16, g16, fwd, both
+            torch.cuda.empty_cache()
+    _write(lines, out_path)
+
+
 def dcn16bwd(out_path=None):
     """ModulatedDeformConv 3 x 3 on 16-bit maps, forward + backward through the module (layout copies included), the forward on
     fv2p_dcn_forward_h on both 16-bit routes.  on: DCN.NATIVE_16BIT_BACKWARD = True (fv2p_dcn_backward_h); off: the default, the fp32
@@ -1390,6 +1444,9 @@ if __name__ == "__main__":
         sys.exit(0)
     if which == "exit16":   # python tools/microbench.py exit16 [profiles/exit_half.txt]
         exit16(sys.argv[2] if len(sys.argv) > 2 else None)
+        sys.exit(0)
+    if which == "sa16":   # python tools/microbench.py sa16 [profiles/sa_half.txt]
+        sa16(sys.argv[2] if len(sys.argv) > 2 else None)
         sys.exit(0)
     if which == "batch16":   # python tools/microbench.py batch16 [profiles/batch_half.txt]
         batch16(sys.argv[2] if len(sys.argv) > 2 else None)
