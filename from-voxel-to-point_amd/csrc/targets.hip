@@ -216,6 +216,11 @@ extern "C" int fv2p_anchor_assign(const float* anchor_bev, const float* anchors,
 // direction-bin cross entropy (two bins), normalised per sample by max(#positive anchors, 1) and divided by the batch size: the
 // reference composes ~45 element-wise torch ops over [B, A, .] tensors (and autograd ~70 more in the backward pass); here one
 // kernel leaves the three weighted loss sums and the gradients with respect to the three logit tensors.
+// Every float expression follows the tensor formulation (AnchorHead.anchor_losses_tensor_ops under autograd), its corner cases included:
+// the focal loss's cross entropy is clamp(x, min=0) - x t + log1p(exp(-|x|)), whose derivative is sigmoid(x) - t everywhere but at a
+// logit of exactly 0, where autograd passes the clamp's gradient and takes sgn(0) = 0: 1 - t, not 0.5 - t; `n < beta` strictly in the
+// smooth-L1 and sgn(0) = 0 in its linear branch; the direction bin floor((v - floor(v / 2 pi) 2 pi) / pi) of v = target heading +
+// anchor heading - dir_offset in float32 in that order, clamped to {0, 1} (a v just below 0 is lost in 2 pi and lands in bin 2).
 namespace fv2p {
 
 __global__ __launch_bounds__(256) void anchor_pos_count_k(int n_anchor, const int* __restrict__ labels, int* __restrict__ pos) {
@@ -252,7 +257,8 @@ __global__ __launch_bounds__(256) void anchor_loss_k(AnchorLossArgs p) {
     const float bce = fmaxf(x, 0.f) - (t ? x : 0.f) + log1pf(expf(-fabsf(x)));
     l_cls = static_cast<double>(aw * pt * pt * bce * w);
     const float dpt = t ? -pr * (1.f - pr) : pr * (1.f - pr);
-    p.dcls[o] = aw * w * (2.f * pt * dpt * bce + pt * pt * (pr - (t ? 1.f : 0.f))) * inv_b * p.w_cls;
+    const float dbce = (x == 0.f ? 1.f : pr) - (t ? 1.f : 0.f);   // at x == 0: clamp(min=0) passes its gradient and sgn(0) = 0
+    p.dcls[o] = aw * w * (2.f * pt * dpt * bce + pt * pt * dbce) * inv_b * p.w_cls;
     // localisation and direction: positive anchors only
     float db[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, dd[2] = {0.f, 0.f};
     if (t) {
@@ -556,6 +562,8 @@ __global__ __launch_bounds__(kRoiLossThreads) void roi_loss_k(RoiLossArgs p) {
 // PointHeadSimple's foreground loss (point_head_template.py:47-142): sigmoid focal loss (alpha 0.25, gamma 2) of one logit per point
 // against labels in {-1 ignored, 0, 1}, every counted point weighted by 1 / max(#positive, 1); the score sigmoid(logit) the RoI head
 // pools comes out of the same pass.  Same three launches as the first-stage loss: positive count, loss + gradient, ordered reduce.
+// The same corner case as there: at a logit of exactly 0 the cross entropy's derivative is 1 - t, as autograd gives over the tensor
+// formulation (sigmoid_focal: the gradient of clamp(min=0) passes at 0 and sgn(0) = 0), sigmoid(x) - t everywhere else.
 __global__ __launch_bounds__(256) void point_pos_count_k(int n, const int64_t* __restrict__ labels, int* __restrict__ pos) {
   const int a = blockIdx.x * blockDim.x + threadIdx.x;
   const bool t = a < n && labels[a] > 0;
@@ -580,7 +588,8 @@ __global__ __launch_bounds__(256) void point_loss_k(int n, const float* __restri
     const float bce = fmaxf(x, 0.f) - (t ? x : 0.f) + log1pf(expf(-fabsf(x)));
     l = static_cast<double>(aw * pt * pt * bce * w);
     const float dpt = t ? -pr * (1.f - pr) : pr * (1.f - pr);
-    dlogits[a] = aw * w * (2.f * pt * dpt * bce + pt * pt * (pr - (t ? 1.f : 0.f))) * weight;
+    const float dbce = (x == 0.f ? 1.f : pr) - (t ? 1.f : 0.f);   // at x == 0: 1 - t, as in anchor_loss_k
+    dlogits[a] = aw * w * (2.f * pt * dpt * bce + pt * pt * dbce) * weight;
     score[a] = pr;
   }
   __shared__ double s_red[4];

@@ -317,6 +317,56 @@ def test_roi_target_sampling_kernel_equals_its_tensor_formulation(gpu):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("r,n,g,batch", [(1, 1, 1, 1), (64, 64, 3, 2), (100, 32, 1, 3), (1000, 128, 5, 2), (1024, 128, 12, 1)])
+def test_roi_target_sampling_kernel_at_the_edges_of_its_shapes(gpu, r, n, g, batch):
+    """The same comparison over what the entry point accepts: one RoI, n == r, one box, r off a multiple of 64 (the launch rounds the
+    workgroup up to whole waves) and the maximum of 1024; the six overlap patterns for every shape.  Pick uniforms of 0.0 and
+    nextafter(1, 0) (u * count rounds up to count: the clamp), permutation keys in eighths on the even RoIs (equal keys inside the
+    foreground set: a stable sort).  RoI i carries i in its first column, so s_index - never read by the step - is held too: it is the
+    sampled RoI's row, and the sampled box is the first best box of that row."""
+    from fv2p_harness.fv2p_model import IoUGuidedRoIHead
+    import fv2p_native
+    cfg = type("SampleCfg", (SmallFV2P,), dict(roi_per_image=n))
+    head = IoUGuidedRoIHead.__new__(IoUGuidedRoIHead)          # sample_targets_tensor_ops reads cfg only
+    torch.nn.Module.__init__(head)
+    head.cfg = cfg
+    rng = np.random.default_rng(1000 * r + n)
+    base = rng.uniform(0, 1, size=(batch, r, g)).astype(np.float32) ** 3
+    cases = [base, np.minimum(base, 0.5).astype(np.float32), (0.6 + 0.4 * base).astype(np.float32), np.where(base < 0.1, 0.2, base).astype(np.float32),
+             np.where((base >= 0.1) & (base < 0.55), 0.05, base).astype(np.float32), np.zeros_like(base)]
+    last = np.nextafter(np.float32(1), np.float32(0))
+    equal_keys = 0
+    for iou_np in cases:
+        rois_np = rng.standard_normal((batch, r, 7)).astype(np.float32)
+        rois_np[..., 0] = np.arange(r)
+        gt_np = rng.standard_normal((batch, g, 8)).astype(np.float32)
+        u_np = rng.uniform(0, 1, size=(batch, r + n)).astype(np.float32)
+        u_np[:, 0:r:2] = np.floor(u_np[:, 0:r:2] * 8) / 8
+        u_np[:, r], u_np[:, r + n - 1] = 0.0, last
+        if n > 3:
+            u_np[:, r + n // 2], u_np[:, r + n // 2 + 1] = last, 0.0
+        u_np[1::2, r] = last
+        fg = iou_np.max(2) >= min(cfg.reg_fg, cfg.cls_fg)
+        equal_keys += sum(len(np.unique(u_np[b, :r][fg[b]])) < int(fg[b].sum()) for b in range(batch))
+        iou, rois, gt, u = (torch.from_numpy(x).to(gpu) for x in (iou_np, rois_np, gt_np, u_np))
+        want = head.sample_targets_tensor_ops(iou, rois, gt, u)
+        s_rois, s_gt = rois.new_full((batch, n, 7), -7.0), gt.new_full((batch, n, 8), -7.0)
+        s_iou, s_index = rois.new_full((batch, n), -7.0), torch.full((batch, n), -7, dtype=torch.int32, device=gpu)
+        fv2p_native.call("fv2p_roi_sample_targets", iou, rois, gt, u, batch, r, g, n, 8, float(min(cfg.reg_fg, cfg.cls_fg)), float(cfg.cls_bg_lo),
+                         float(cfg.reg_fg), int(round(cfg.fg_ratio * n)), float(cfg.hard_bg_ratio), s_rois, s_gt, s_iou, s_index, fv2p_native.stream())
+        assert torch.equal(s_rois, want[0]) and torch.equal(s_iou, want[2])
+        assert torch.equal(s_gt, want[1])
+        idx = s_index.cpu().numpy()
+        assert idx.min() >= 0 and idx.max() < r
+        assert np.array_equal(idx, s_rois[..., 0].cpu().numpy().astype(np.int64)), "s_index is not the sampled RoI's row"
+        for b in range(batch):
+            assert np.array_equal(rois_np[b, idx[b]], s_rois[b].cpu().numpy())
+            assert np.array_equal(gt_np[b, np.argmax(iou_np[b, idx[b]], axis=1)], s_gt[b].cpu().numpy())      # numpy's argmax: the first maximum
+            assert np.array_equal(iou_np[b, idx[b]].max(1), s_iou[b].cpu().numpy())
+    assert equal_keys > 0 or r == 1, "no case had equal keys inside its foreground set"
+
+
+@pytest.mark.gpu
 def test_stream_arrangements_give_the_same_step(gpu):
     """The schedules of the forward pass — dense branch on a side stream (bench.py's choice), point branch on a side stream after the
     RoI preparation (the default), everything on one stream — are the same computation.  The child runs under deterministic library settings (MIOpen deterministic

@@ -17,6 +17,8 @@ import torch
 import fv2p_native as _nat
 from fv2p_harness import fv2p_model as fm
 
+from glue_util import hold, tensor_ops
+
 pytestmark = pytest.mark.gpu
 CFG = fm.FV2PConfig
 PI = math.pi
@@ -24,16 +26,6 @@ PI = math.pi
 
 def load(golden_dir, name):
     return np.load(os.path.join(golden_dir, f"pyref_{name}.npz"))
-
-
-class tensor_ops:
-    """KERNEL_GLUE off: the tensor formulations on whatever device the tensors live on."""
-
-    def __enter__(self):
-        self.was, fm.KERNEL_GLUE = fm.KERNEL_GLUE, False
-
-    def __exit__(self, *a):
-        fm.KERNEL_GLUE = self.was
 
 
 def roi_head():
@@ -151,15 +143,6 @@ def kernel_form(case, device):
     loss = roi_head().losses(t["rois"], t["gt"], None, t["iou"], cls, reg8, None)
     dcls, dreg = torch.autograd.grad(loss, (cls, reg8))
     return float(loss), dcls.double().cpu().numpy(), dreg.double().cpu().numpy()
-
-
-def hold(name, got, want, base):
-    """got against the yardstick `want`, where the fp32 tensor form `base` is E away from it."""
-    e = np.abs(base - want).max()
-    err = np.abs(got - want).max()
-    bound = 2 * e + 1e-7 * np.abs(want).max()
-    print(f"{name}: E {e:.3e}  kernel error {err:.3e}  bound {bound:.3e}  max|grad| {np.abs(want).max():.3e}")
-    assert np.isfinite(got).all() and err <= bound, name
 
 
 @pytest.mark.parametrize("name", sorted(LOSS_CASES))
@@ -316,7 +299,10 @@ def test_pool_in_frame_against_the_tensor_route(gpu):
 def point_case(n, kind, seed):
     rng = np.random.default_rng(seed)
     logits = rng.normal(0, 2, (n, 1)).astype(np.float32)
-    labels = {"mixed": rng.integers(-1, 2, n), "no_positives": rng.integers(-1, 1, n), "all_ignored": np.full(n, -1)}[kind].astype(np.int64)
+    labels = {"mixed": rng.integers(-1, 2, n), "zero_logits": rng.integers(-1, 2, n), "no_positives": rng.integers(-1, 1, n),
+              "all_ignored": np.full(n, -1)}[kind].astype(np.int64)
+    if kind == "zero_logits":   # a logit of exactly 0 on a positive, a negative and an ignored point: autograd's clamp(min=0) and sgn(0) = 0 there
+        logits[:3, 0], labels[:3] = 0.0, (1, 0, -1)
     return logits, labels
 
 
@@ -330,7 +316,8 @@ def point_tensor_form(logits, labels, device, dtype):
     return float(loss), grad.double().cpu().numpy(), torch.sigmoid(x.detach()).view(-1).double().cpu().numpy()
 
 
-@pytest.mark.parametrize("n,kind", [(1, "mixed"), (63, "mixed"), (65, "mixed"), (1000, "mixed"), (65, "no_positives"), (63, "all_ignored"), (1000, "no_positives")])
+@pytest.mark.parametrize("n,kind", [(1, "mixed"), (63, "mixed"), (65, "mixed"), (1000, "mixed"), (65, "no_positives"), (63, "all_ignored"), (1000, "no_positives"),
+                                    (65, "zero_logits")])
 def test_point_loss_against_float64(gpu, n, kind):
     logits, labels = point_case(n, kind, 100 + n)
     l64, g64, s64 = point_tensor_form(logits, labels, "cpu", torch.float64)
