@@ -36,6 +36,7 @@ from pcdet.ops.roipoint_pool3d import roipoint_pool3d_utils
 from pcdet.models.backbones_3d.pfe import bev_grid_pooling
 from pcdet.ops.spconv import norm as _norm
 from pcdet.ops.spconv import head as _head
+from pcdet.ops.spconv import linear as _linear
 from pcdet.ops.spconv import bev_entry as _bev_entry
 
 import fv2p_native as _nat
@@ -227,6 +228,13 @@ def run_rows(seq, x):
     i = 0
     while i < len(mods):
         m = mods[i]
+        if KERNEL_GLUE and type(m) is nn.Linear and i + 1 < len(mods) and type(mods[i + 1]) is nn.BatchNorm1d:
+            # Linear -> BatchNorm1d [-> ReLU] as one op (csrc/linear_bn.hip) where it applies and measured faster at this shape
+            relu = mods[i + 2] if i + 2 < len(mods) and type(mods[i + 2]) is nn.ReLU else None
+            if _linear.fusable(m, mods[i + 1], relu, x) and _linear.pays(x.shape[0], m.in_features, m.out_features):
+                x = _linear.linear_bn_relu(m, mods[i + 1], x, relu)
+                i += 2 + (relu is not None)
+                continue
         if isinstance(m, nn.BatchNorm1d) and x.dim() == 2:
             relu = mods[i + 1] if i + 1 < len(mods) and isinstance(mods[i + 1], nn.ReLU) else None
             x = bn_act(m, x, relu)

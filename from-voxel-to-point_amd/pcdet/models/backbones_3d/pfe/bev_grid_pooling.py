@@ -103,8 +103,13 @@ class BEVGridPooling(nn.Module):
         feats = feats.view(batch_size * num_keypoints, -1)
         mods = list(self.point_bev_feature_compress)
         if len(mods) == 3:   # Linear -> BatchNorm1d -> ReLU: the pair after the GEMM as one fused op where it applies
+            from pcdet.ops.spconv import linear as _linear
             from pcdet.ops.spconv.norm import batch_norm_relu
-            feats = mods[0](feats)
-            fused = batch_norm_relu(mods[1], feats, mods[2])
+            fused = None
+            if _linear.fusable(*mods, feats) and _linear.pays(feats.shape[0], mods[0].in_features, mods[0].out_features):
+                fused = _linear.linear_bn_relu(mods[0], mods[1], feats, mods[2])   # the GEMM as well (csrc/linear_bn.hip)
+            if fused is None:
+                feats = mods[0](feats)
+                fused = batch_norm_relu(mods[1], feats, mods[2])
             feats = fused if fused is not None else mods[2](mods[1](feats))
         return feats.view(batch_size, num_keypoints, -1)

@@ -1,0 +1,162 @@
+"""nn.Linear(bias=False) -> nn.BatchNorm1d [-> nn.ReLU] on fp32 point rows as one op (kernels in csrc/linear_bn.hip).
+
+The voxel-to-point decoder is thirteen such triples over the key-point rows (fv2p_harness/fv2p_model.py: LateralBlock.net /
+.downsample, V2PDecoder.decode_block_out) and ``BEVGridPooling.point_bev_feature_compress`` is one more.  ``linear_bn_relu`` is what
+their callers try for the three modules instead: the product runs on this library's fp32 MFMA kernels, the BatchNorm statistics come
+out of the GEMM's epilogue, and the weight gradient is folded in a fixed order - so the output, every gradient and the running
+statistics are bit-identical from run to run without any library determinism setting.  Same parameters (the modules' own tensors,
+nothing repacked or cached), the same running-statistics update, torch's result within fp32 rounding.  It returns None whenever the
+situation is not the plain one (`fusable`) and the caller then runs the modules, so everything else - a Linear with bias, 16-bit rows,
+autocast, CPU tensors, hooks, subclasses, a single row in training mode - stays torch's, errors included.
+"""
+import os
+
+import torch
+from torch import nn
+from torch.autograd import Function
+
+import fv2p_native as _nat
+
+from .norm import _plain_forward
+
+_ENABLED = os.environ.get("FV2P_FUSED_LINEAR", "1") != "0"
+
+MAX_IN = 1024     # kMaxCin / kMaxCout of csrc/linear_bn.hip
+MAX_OUT = 512
+_WS_BYTES = {}
+_PAYS = {}
+
+
+def _ws_bytes(n, cin, cout):
+    key = (n, cin, cout)
+    v = _WS_BYTES.get(key)
+    if v is None:
+        v = _WS_BYTES[key] = _nat.call("fv2p_linear_bn_ws_bytes", n, cin, cout)
+    return v
+
+
+def pays(n, cin, cout):
+    """Whether the op measured faster than the library route at this shape (fv2p_linear_bn_pays): what `run_rows` and
+    BEVGridPooling ask before they use it.  `linear_bn_relu` itself does not ask."""
+    key = (n, cin, cout)
+    v = _PAYS.get(key)
+    if v is None:
+        v = _PAYS[key] = bool(_nat.call("fv2p_linear_bn_pays", n, cin, cout))
+    return v
+
+
+class _LinearBatchNormReLU(Function):
+    """(x [n, cin], w [cout, cin], gamma, beta) -> y [n, cout].  Saves x, the pre-activation z, mean / invstd and the parameters; the
+    backward pass recomputes the ReLU mask from z."""
+
+    @staticmethod
+    def forward(ctx, x, w, gamma, beta, bn, relu, keep_z):
+        n, cin = x.shape
+        cout = w.shape[0]
+        dev = x.device
+        batch_stats = bn.training or bn.running_mean is None
+        y = x.new_empty((n, cout))
+        with _nat.device_guard(dev):
+            if batch_stats:
+                z = x.new_empty((n, cout))
+                stats = x.new_empty((2, cout))
+                mean, invstd = stats[0], stats[1]
+                track = bn.training and bn.running_mean is not None
+                ws = _nat.workspace(_ws_bytes(n, cin, cout), dev)
+                _nat.call("fv2p_linear_bn_forward", x, n, cin, w, cout, float(bn.eps), -1.0 if bn.momentum is None else float(bn.momentum),
+                          gamma, beta, int(relu), bn.running_mean if track else None, bn.running_var if track else None,
+                          bn.num_batches_tracked if track else None, z, mean, invstd, y, ws, ws.numel(), _nat.stream())
+            else:
+                # [cout] values.  mean is a copy: the buffer may move before this call's backward runs.  z is kept only when a
+                # gradient can be asked for (the backward pass through the frozen BatchNorm reads it)
+                z = x.new_empty((n, cout)) if keep_z else None
+                mean = bn.running_mean.clone()
+                invstd = torch.rsqrt(bn.running_var + bn.eps)
+                _nat.call("fv2p_linear_bn_forward_eval", x, n, cin, w, cout, mean, invstd, gamma, beta, int(relu), z, y, _nat.stream())
+        ctx.save_for_backward(x, z, mean, invstd, w, gamma, beta)
+        ctx.relu, ctx.batch_stats = bool(relu), bool(batch_stats)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, z, mean, invstd, w, gamma, beta = ctx.saved_tensors
+        n, cin = x.shape
+        cout = w.shape[0]
+        dev = x.device
+        dy = dy.contiguous()
+        need = ctx.needs_input_grad
+        du = torch.empty_like(z)
+        dx = torch.empty_like(x) if need[0] else None
+        dw = torch.empty_like(w) if need[1] else None
+        dpar = x.new_empty((2, cout))
+        dgamma, dbeta = dpar[0], dpar[1]
+        with _nat.device_guard(dev):
+            ws = _nat.workspace(_ws_bytes(n, cin, cout), dev)
+            _nat.call("fv2p_linear_bn_backward", x, z, dy, n, cin, w, cout, mean, invstd, gamma, beta, int(ctx.relu), int(ctx.batch_stats),
+                      du, dx, dw, dgamma, dbeta, ws, ws.numel(), _nat.stream())
+        return (dx, dw, dgamma if (gamma is not None and need[2]) else None, dbeta if (beta is not None and need[3]) else None, None, None, None)
+
+
+def _fp32_here(t, x):
+    return t is None or (torch.is_tensor(t) and t.dtype == torch.float32 and t.device == x.device and t.is_contiguous())
+
+
+def fusable(linear, bn, relu_module, x):
+    """The plain case of the (Linear, BatchNorm1d[, ReLU]) triple on rows x [n, cin] the fused op covers."""
+    if not _ENABLED or type(linear) is not nn.Linear or linear.bias is not None or not _plain_forward(linear):
+        return False
+    if type(bn) is not nn.BatchNorm1d or not _plain_forward(bn) or bn.num_features != linear.out_features:
+        return False
+    if relu_module is not None and (type(relu_module) is not nn.ReLU or not _plain_forward(relu_module)):
+        return False
+    if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.is_contiguous()):
+        return False
+    if torch.is_autocast_enabled():
+        return False
+    n, cin = x.shape
+    if cin != linear.in_features or not 1 <= cin <= MAX_IN or not 1 <= linear.out_features <= MAX_OUT:
+        return False
+    if n < (2 if bn.training else 1):   # torch raises for a single row in training mode: let it
+        return False
+    if (bn.weight is None) != (bn.bias is None) or (bn.running_mean is None) != (bn.running_var is None):
+        return False
+    if not all(_fp32_here(t, x) for t in (linear.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var)):
+        return False
+    t = bn.num_batches_tracked
+    if t is not None and (t.dtype != torch.int64 or t.device != x.device):
+        return False
+    return True
+
+
+def linear_bn_relu(linear, bn, x, relu_module=None):
+    """y = relu?(bn(linear(x))) for contiguous fp32 rows x [n, cin] on the GPU, or None when the fused path does not apply."""
+    if not fusable(linear, bn, relu_module, x):
+        return None
+    keep_z = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, linear.weight, bn.weight, bn.bias))
+    return _LinearBatchNormReLU.apply(x, linear.weight, bn.weight, bn.bias, bn, relu_module is not None, keep_z)
+
+
+def run_rows(mods, x):
+    """The modules `mods` (a Sequential of Linear / BatchNorm1d / ReLU / ...) applied to the rows x in order, with every
+    (Linear, BatchNorm1d[, ReLU]) run that `fusable` accepts and that pays at its shape (`pays`) as one call.  Every other module runs
+    as itself."""
+    mods = list(mods)
+    i = 0
+    while i < len(mods):
+        m = mods[i]
+        if type(m) is nn.Linear and i + 1 < len(mods) and type(mods[i + 1]) is nn.BatchNorm1d:
+            bn = mods[i + 1]
+            relu = mods[i + 2] if i + 2 < len(mods) and type(mods[i + 2]) is nn.ReLU else None
+            y = None
+            if fusable(m, bn, relu, x) and pays(x.shape[0], m.in_features, m.out_features):
+                y = linear_bn_relu(m, bn, x, relu)
+            elif relu is not None and fusable(m, bn, None, x) and pays(x.shape[0], m.in_features, m.out_features):
+                relu = None   # the ReLU module is not a plain one: the pair alone, then the module
+                y = linear_bn_relu(m, bn, x, None)
+            if y is not None:
+                x = y
+                i += 2 + (relu is not None)
+                continue
+        x = m(x)
+        i += 1
+    return x

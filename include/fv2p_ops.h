@@ -1197,6 +1197,43 @@ int fv2p_head1x1_backward_weights(const float* x, const float* dy0, const float*
                                   int64_t hw, int c0, int c1, int c2, float* dw0, float* dw1, float* dw2, float* db0, float* db1,
                                   float* db2, void* ws, size_t ws_bytes, fv2p_stream_t stream);
 
+/* ---- nn.Linear(bias=False) -> nn.BatchNorm1d [-> nn.ReLU] over fp32 point rows as one op --------------------------------------
+ * The triple of the voxel-to-point decoder and of BEVGridPooling.point_bev_feature_compress (csrc/linear_bn.hip; every product on
+ * v_mfma_f32_16x16x4_f32: fp32 in, fp32 accumulate).  Everything is fp32 and row-major: x [n][cin], w [cout][cin] (the module's own
+ * weight: nothing is repacked or kept between calls), z = x * w^T [n][cout], y and dy [n][cout].  n >= 1, cin 1 .. 1024 and
+ * cout 1 .. 512, any value (FV2P_EINVAL outside); 16-byte loads where the row lengths are multiples of 4 and the bases 16-byte
+ * aligned, element by element otherwise.  gamma, beta, running_mean and running_var may be NULL as in fv2p_batchnorm_forward;
+ * momentum < 0 is momentum=None.  No float atomics and no workgroup waits for another: every sum across workgroups is a row of
+ * partials in the workspace that a LATER launch of the same call folds in a fixed order, so statistics, running statistics and every
+ * gradient are bit-identical from run to run.  Every call enqueues all of its launches on `stream` and returns.
+ *   fv2p_linear_bn_forward      : training mode (n >= 2).  GEMM that stores z and leaves sum z / sum z^2 per workgroup (formed in fp64
+ *                                 from the fp32 accumulators); fold -> mean, invstd (biased variance), running statistics with
+ *                                 torch's semantics (unbiased running_var, num_batches_tracked += 1); apply ->
+ *                                 y = relu?((z - mean) * invstd * gamma + beta).  Three launches.
+ *   fv2p_linear_bn_forward_eval : given mean / invstd; scale, shift and the ReLU in the GEMM's epilogue.  One launch; z is stored
+ *                                 only when a buffer is passed (a backward pass through the frozen BatchNorm needs it).
+ *   fv2p_linear_bn_backward     : dz = dy * [y > 0] recomputed from z; dgamma = sum dz * xhat, dbeta = sum dz;
+ *                                 du = gamma * invstd * (dz - mean(dz) - xhat * mean(dz * xhat)) (batch_stats = 0: gamma * invstd * dz)
+ *                                 into the caller's du [n][cout]; dx = du * w (dx NULL: skipped); dw = du^T * x over a fixed split of
+ *                                 the rows, fp64 partial tiles folded in split order (dw NULL: GEMM and fold skipped).
+ * Workspace: fv2p_linear_bn_ws_bytes(n, cin, cout), enough for either direction (0 for a shape the op does not take);
+ * fv2p_linear_bn_splits: the row chunks of the weight-gradient pass; fv2p_linear_bn_pays: 1 where the op measured faster, forward +
+ * backward, than rocBLAS + fv2p_batchnorm_* (profiles/linear_bn.txt).  All three are pure host functions. */
+size_t fv2p_linear_bn_ws_bytes(int64_t n, int cin, int cout);
+int fv2p_linear_bn_splits(int64_t n, int cin, int cout);
+int fv2p_linear_bn_pays(int64_t n, int cin, int cout);
+int fv2p_linear_bn_forward(const float* x, int64_t n, int cin, const float* w, int cout, float eps, float momentum,
+                           const float* gamma, const float* beta, int relu, float* running_mean, float* running_var,
+                           int64_t* num_batches_tracked, float* z, float* mean, float* invstd, float* y, void* ws, size_t ws_bytes,
+                           fv2p_stream_t stream);
+int fv2p_linear_bn_forward_eval(const float* x, int64_t n, int cin, const float* w, int cout, const float* mean,
+                                const float* invstd, const float* gamma, const float* beta, int relu, float* z, float* y,
+                                fv2p_stream_t stream);
+int fv2p_linear_bn_backward(const float* x, const float* z, const float* dy, int64_t n, int cin, const float* w, int cout,
+                            const float* mean, const float* invstd, const float* gamma, const float* beta, int relu,
+                            int batch_stats, float* du, float* dx, float* dw, float* dgamma, float* dbeta, void* ws,
+                            size_t ws_bytes, fv2p_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

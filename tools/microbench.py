@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Per-kernel timings on one GPU (events on the launch stream). Not part of the product or of bench.py; used to
-iterate on kernel variants:  python tools/microbench.py [conv|conv16|amp16|bn16|bn2d|bn2d16|bev16|beventry|exit16|batch16|sa16|dcn|dcn16|dcn16bwd|fps|voxel|nms|all]"""
+iterate on kernel variants:  python tools/microbench.py [conv|conv16|amp16|bn16|bn2d|bn2d16|linbn|bev16|beventry|exit16|batch16|sa16|dcn|dcn16|dcn16bwd|fps|voxel|nms|all]"""
 import os
 import sys
 import time
@@ -941,6 +941,112 @@ def _write(lines, out_path):
             fh.write(text)
 
 
+LINBN_LAYERS = [   # (name, cin, cout, relu): the thirteen Linear -> BatchNorm1d [-> ReLU] layers of the decoder, then BEVGridPooling's compression
+    ("lat1.net0", 128, 256, True), ("lat1.net1", 256, 256, False), ("lat1.down", 128, 256, False),
+    ("lat2.net0", 64, 192, True), ("lat2.net1", 192, 192, False), ("lat2.down", 256, 192, False),
+    ("lat3.net0", 32, 160, True), ("lat3.net1", 160, 160, False), ("lat3.down", 192, 160, False),
+    ("lat4.net0", 16, 128, True), ("lat4.net1", 128, 128, False), ("lat4.down", 160, 128, False),
+    ("decode_out", 128, 128, True), ("bev_compress", 512, 128, True)]
+
+
+def linbn(out_path=None):
+    """Linear(bias=False) -> BatchNorm1d(eps=1e-3, momentum=0.01) [-> ReLU] on 49 152 key-point rows (3 x 16 384), every layer of
+    LINBN_LAYERS, forward and forward + backward, three routes: (a) the fused op (pcdet.ops.spconv.linear, csrc/linear_bn.hip);
+    (b) the harness route without it: the chunked rocBLAS product of run_rows (rows_linear) + batch_norm_relu; (c) the plain modules.
+    Each figure: the median of ROUNDS windows of REPS calls, the routes taken alternately in one process, +- half the range of the
+    windows.  Then, per layer, the pieces of (a) timed through the C entry points, with the FLOP/s and bytes/s their shapes imply:
+    the GEMMs at 2 n cin cout FLOP, the BatchNorm passes at their algorithmic traffic."""
+    import fv2p_native as nat
+    from torch import nn
+    from fv2p_harness import fv2p_model
+    from pcdet.ops.spconv import linear
+    dev = torch.device("cuda:0")
+    ROUNDS, REPS, N = 7, 10, 49152
+    lines = ["Linear + BatchNorm1d (+ReLU), n = %d rows, us per call: median of %d windows of %d calls, +- half the range" % (N, ROUNDS, REPS),
+             "(a) fused op   (b) chunked rocBLAS product + fused BatchNorm (the harness route without the op)   (c) plain modules",
+             "%-13s %-9s | %-15s %-15s %-15s | %-15s %-15s %-15s | %s" % ("layer", "cin>cout", "fwd (a)", "fwd (b)", "fwd (c)", "fwd+bwd (a)",
+                                                                        "fwd+bwd (b)", "fwd+bwd (c)", "(a) beats (b) fwd+bwd by more than the larger spread")]
+    pieces = ["", "pieces of (a) through the C entry points, us (median of %d windows) with the rate the shape implies" % ROUNDS,
+              "%-13s %-9s | %-22s %-22s %-22s %-22s %-22s" % ("layer", "cin>cout", "eval fwd GEMM TFLOP/s", "train fwd-GEMM TB/s", "bwd BN passes TB/s",
+                                                          "dx GEMM TFLOP/s", "dw GEMM+fold TFLOP/s")]
+    no_pay = lambda n, cin, cout: False
+    for name, cin, cout, relu in LINBN_LAYERS:
+        torch.manual_seed(0)
+        x = torch.randn(N, cin, device=dev, requires_grad=True)
+        g = torch.randn(N, cout, device=dev)
+
+        def mods():
+            m = [nn.Linear(cin, cout, bias=False), nn.BatchNorm1d(cout, eps=1e-3, momentum=0.01)] + ([nn.ReLU()] if relu else [])
+            return nn.Sequential(*m).to(dev)
+        sa, sb, sc = mods(), mods(), mods()
+
+        def route_a():
+            y = linear.linear_bn_relu(sa[0], sa[1], x, sa[2] if relu else None)
+            assert y is not None
+            return y
+
+        def route_b():
+            saved, linear.pays = linear.pays, no_pay
+            try:
+                return fv2p_model.run_rows(sb, x)
+            finally:
+                linear.pays = saved
+        fwd = {"a": route_a, "b": route_b, "c": lambda: sc(x)}
+
+        def both(f, seq):
+            def run():
+                f().backward(g)
+                x.grad = None
+                for p in seq.parameters():
+                    p.grad = None
+            return run
+        tf = _windows(fwd, ROUNDS, REPS)
+        tb = _windows({"a": both(route_a, sa), "b": both(route_b, sb), "c": both(fwd["c"], sc)}, ROUNDS, REPS)
+        spread = lambda t: (max(t) - min(t)) / 2
+        wins = np.median(tb["b"]) - np.median(tb["a"]) > max(spread(tb["a"]), spread(tb["b"]))
+        lines.append("%-13s %-9s | %s %s %s | %s %s %s | %s" % (name, "%d>%d" % (cin, cout), _cell(tf["a"]), _cell(tf["b"]), _cell(tf["c"]),
+                                                              _cell(tb["a"]), _cell(tb["b"]), _cell(tb["c"]), "yes" if wins else "no"))
+        print(lines[-1], flush=True)
+        # the pieces, through the C entry points on detached buffers
+        with torch.no_grad():
+            xd, w = x.detach(), sa[0].weight.detach()
+            gamma, beta = sa[1].weight.detach(), sa[1].bias.detach()
+            z, y, du = (torch.empty(N, cout, device=dev) for _ in range(3))
+            dx = torch.empty(N, cin, device=dev)
+            dw, stats, dpar = torch.empty_like(w), torch.empty(2, cout, device=dev), torch.empty(2, cout, device=dev)
+            ws = nat.workspace(nat.call("fv2p_linear_bn_ws_bytes", N, cin, cout), dev)
+            st = nat.stream()
+            fwd_train = lambda: nat.call("fv2p_linear_bn_forward", xd, N, cin, w, cout, 1e-3, 0.01, gamma, beta, int(relu), None, None, None, z,
+                                         stats[0], stats[1], y, ws, ws.numel(), st)
+            fwd_eval = lambda: nat.call("fv2p_linear_bn_forward_eval", xd, N, cin, w, cout, stats[0], stats[1], gamma, beta, int(relu), None, y, st)
+            bwd = lambda a, b: (lambda: nat.call("fv2p_linear_bn_backward", xd, z, g, N, cin, w, cout, stats[0], stats[1], gamma, beta, int(relu), 1,
+                                                 du, a, b, dpar[0], dpar[1], ws, ws.numel(), st))
+            fwd_train()
+            tp = _windows({"eval": fwd_eval, "train": fwd_train, "bn": bwd(None, None), "dx": bwd(dx, None), "dw": bwd(None, dw)}, ROUNDS, REPS)
+        med = {k: np.median(v) for k, v in tp.items()}
+        flop, nz = 2.0 * N * cin * cout, 4.0 * N * cout
+        rate = lambda us, work, unit: "%8.1f  %6.2f" % (us, work / (max(us, 1e-3) * 1e-6) / unit)
+        pieces.append("%-13s %-9s | %-22s %-22s %-22s %-22s %-22s" % (
+            name, "%d>%d" % (cin, cout), rate(med["eval"], flop, 1e12),
+            rate(med["train"], 4.0 * N * cin + 3.0 * nz, 1e12),          # x read, z written; z read and y written by the apply pass
+            rate(med["bn"], 5.0 * nz, 1e12),                              # z, dy read twice, du written
+            rate(med["dx"] - med["bn"], flop, 1e12), rate(med["dw"] - med["bn"], flop, 1e12)))
+    _write(lines + pieces, out_path)
+
+
+def linbn_once():
+    """One forward + backward of the fused op per layer of LINBN_LAYERS, for `rocprofv3 --kernel-trace --stats -- python tools/microbench.py linbn_once`."""
+    from torch import nn
+    from pcdet.ops.spconv import linear
+    dev = torch.device("cuda:0")
+    for _ in range(3):
+        for name, cin, cout, relu in LINBN_LAYERS:
+            x = torch.randn(49152, cin, device=dev, requires_grad=True)
+            lin, bn = nn.Linear(cin, cout, bias=False).to(dev), nn.BatchNorm1d(cout, eps=1e-3, momentum=0.01).to(dev)
+            linear.linear_bn_relu(lin, bn, x, nn.ReLU() if relu else None).sum().backward()
+    torch.cuda.synchronize()
+
+
 def bn2d16(out_path=None):
     """BatchNorm2d(eps=1e-3, momentum=0.01) + ReLU on the BEV maps in 16-bit storage (the 16-bit instances of csrc/batchnorm2d.hip), forward and forward +
     backward: the 16-bit op, the fp32 op on fp32 tensors of the same shape, and nn.BatchNorm2d + nn.ReLU on the same 16-bit tensors.
@@ -1423,6 +1529,12 @@ if __name__ == "__main__":
         sys.exit(0)
     if which == "bn2d":   # python tools/microbench.py bn2d [profiles/bn2d.txt]
         bn2d(sys.argv[2] if len(sys.argv) > 2 else None)
+        sys.exit(0)
+    if which == "linbn":   # python tools/microbench.py linbn [profiles/linear_bn.txt]
+        linbn(sys.argv[2] if len(sys.argv) > 2 else None)
+        sys.exit(0)
+    if which == "linbn_once":   # rocprofv3 --kernel-trace --stats -- python tools/microbench.py linbn_once
+        linbn_once()
         sys.exit(0)
     if which == "bn2d16":   # python tools/microbench.py bn2d16 [profiles/bn2d_half.txt]
         bn2d16(sys.argv[2] if len(sys.argv) > 2 else None)
