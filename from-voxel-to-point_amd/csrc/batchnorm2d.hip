@@ -18,7 +18,7 @@
 // num_batches_tracked (momentum < 0: cumulative average) is read by every channel's finalising workgroup; the reduce launch copies it
 // into the workspace and the apply launch reads that copy, so the bump (by channel 0's finalising workgroup) cannot overtake a reader.
 //
-// The kernels are written once and instantiated per storage format F (F32, Fmt16<H16>, Fmt16<B16>).  A format supplies the element
+// The kernels are written once and instantiated per storage format F (bn_fmt.hpp: F32, Fmt16<H16>, Fmt16<B16>).  A format supplies the element
 // type, the vector width, the unit of V elements that one access moves (widened to fp32 on load, rounded to nearest even ONCE on
 // store), `stored` (the fp32 value of y as memory holds it) and how a parameter is read and written.  Everything else - the arithmetic
 // in fp32, the sums in fp64, the grid, the fold, the finalisation - is the same code.  A thread moves one 16-byte unit (4 fp32 or 8
@@ -29,7 +29,7 @@
 // stored as 0 and gets no gradient, as threshold_backward on the stored tensor gives none.  (fp32: stored(t) = t.)
 #include <type_traits>
 #include "common.hpp"
-#include "dt16.hpp"
+#include "bn_fmt.hpp"
 
 namespace fv2p {
 namespace {
@@ -93,37 +93,6 @@ __device__ __forceinline__ void bn2d_fold(const double* __restrict__ partial, co
   bn2d_block_sum(a, b, red);
   *a_out = a; *b_out = b;
 }
-
-// ---- the storage formats ----------------------------------------------------------------------------------------------------------------
-struct F32 {   // fp32 maps; the parameters are fp32 (pd is not looked at)
-  using elem = float;
-  static constexpr int kVec = 4;
-  template <int V>
-  struct Unit {
-    float v[V];
-    __device__ __forceinline__ void load(const float* p) {
-      if constexpr (V == 4) { const float4 q = *reinterpret_cast<const float4*>(p); v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w; }
-      else v[0] = *p;
-    }
-    __device__ __forceinline__ void store(float* p) const {
-      if constexpr (V == 4) *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-      else *p = v[0];
-    }
-  };
-  static __device__ __forceinline__ float stored(float y) { return y; }
-  static __device__ __forceinline__ float par_load(const void* p, int e, int, float dflt) { return p ? static_cast<const float*>(p)[e] : dflt; }
-  static __device__ __forceinline__ void par_store(void* p, int e, int, double v) { static_cast<float*>(p)[e] = static_cast<float>(v); }
-};
-template <class T>
-struct Fmt16 {   // float16 (T = H16) or bfloat16 (B16) maps; the parameters are fp32 or T (pd)
-  using elem = u16;
-  static constexpr int kVec = 8;
-  template <int V>
-  using Unit = Row16<T, V>;
-  static __device__ __forceinline__ float stored(float y) { return T::widen(T::round(y)); }
-  static __device__ __forceinline__ float par_load(const void* p, int e, int pd, float dflt) { return fv2p::par_load<T>(p, e, pd, dflt); }
-  static __device__ __forceinline__ void par_store(void* p, int e, int pd, double v) { fv2p::par_store<T>(p, e, pd, v); }
-};
 
 template <class F, int V>
 struct Chunk {   // a workgroup's chunk, as fp32, in registers: thread t holds the V-element units t, t + 256, ...

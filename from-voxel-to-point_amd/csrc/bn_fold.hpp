@@ -9,6 +9,7 @@
 // The fold order is the one the apply kernels always used (fold_chunk), so the statistics are bit-identical whoever folds.
 #pragma once
 #include "common.hpp"
+#include "bn_fmt.hpp"
 
 namespace fv2p {
 
@@ -72,26 +73,48 @@ __device__ __forceinline__ void fold_chunk(int nblk, int c, const double* __rest
   *a_out = a; *b_out = b;
 }
 
-// forward: batch mean / invstd of channel e from its folded sums (a = sum x, b = sum x^2 over n rows); `write` (one workgroup of the
-// launch) also stores them and moves the running statistics.  Same arithmetic wherever it runs.
-__device__ __forceinline__ void bn_fwd_channel(double a, double b, long long n_rows, const BnFwdFin& ff, int e, bool write, float* mu_f, float* is_f) {
+// batch mean and biased variance of a channel, in fp64, from its folded sums (a = sum x, b = sum x^2 over n rows)
+__device__ __forceinline__ void bn_moments(double a, double b, long long n_rows, double* mu, double* var) {
   const double n = static_cast<double>(n_rows);
-  const double mu = a / n;
-  double var = b / n - mu * mu;
-  if (var < 0.0) var = 0.0;
+  *mu = a / n;
+  *var = b / n - *mu * *mu;
+  if (*var < 0.0) *var = 0.0;
+}
+
+// The running-statistics update of channel e, written once for every storage format F (bn_fmt.hpp): the old values are read through
+// F::par_load, the new ones computed in fp64 and written through F::par_store with ONE rounding (pd: the buffers are fp32 or F's own
+// 16-bit format).  momentum < 0: the cumulative average over num_batches_tracked + 1 batches - the caller advances the counter AFTER
+// every channel has been here.
+template <class F>
+__device__ __forceinline__ void bn_move_running(double mu, double var, long long n_rows, void* running_mean, void* running_var, int pd,
+                                                float momentum, const long long* num_batches_tracked, int e) {
+  const double n = static_cast<double>(n_rows);
+  double f = momentum;
+  if (momentum < 0.f) f = 1.0 / static_cast<double>(num_batches_tracked ? (*num_batches_tracked + 1) : 1);
+  const double unbiased = n_rows > 1 ? var * n / (n - 1.0) : var;
+  const double rm = F::par_load(running_mean, e, pd, 0.f), rv = F::par_load(running_var, e, pd, 0.f);
+  F::par_store(running_mean, e, pd, (1.0 - f) * rm + f * mu);
+  F::par_store(running_var, e, pd, (1.0 - f) * rv + f * unbiased);
+}
+
+// forward: batch mean / invstd of channel e from its folded sums; `write` (one workgroup of the launch) also stores them (ff.mean,
+// ff.invstd: always fp32) and moves the running statistics, which are in F's parameter format.  Same arithmetic wherever it runs.
+template <class F>
+__device__ __forceinline__ void bn_fwd_channel(double a, double b, long long n_rows, const BnFwdFin& ff, void* running_mean, void* running_var,
+                                               int pd, int e, bool write, float* mu_f, float* is_f) {
+  double mu, var;
+  bn_moments(a, b, n_rows, &mu, &var);
   *mu_f = static_cast<float>(mu);
   *is_f = static_cast<float>(1.0 / sqrt(var + static_cast<double>(ff.eps)));
   if (write) {
     ff.mean[e] = *mu_f;
     ff.invstd[e] = *is_f;
-    if (ff.running_mean) {
-      double f = ff.momentum;
-      if (ff.momentum < 0.f) f = 1.0 / static_cast<double>(ff.num_batches_tracked ? (*ff.num_batches_tracked + 1) : 1);
-      const double unbiased = n_rows > 1 ? var * n / (n - 1.0) : var;
-      ff.running_mean[e] = static_cast<float>((1.0 - f) * ff.running_mean[e] + f * mu);
-      ff.running_var[e] = static_cast<float>((1.0 - f) * ff.running_var[e] + f * unbiased);
-    }
+    if (running_mean) bn_move_running<F>(mu, var, n_rows, running_mean, running_var, pd, ff.momentum, ff.num_batches_tracked, e);
   }
+}
+// ... with the fp32 running statistics of ff itself
+__device__ __forceinline__ void bn_fwd_channel(double a, double b, long long n_rows, const BnFwdFin& ff, int e, bool write, float* mu_f, float* is_f) {
+  bn_fwd_channel<F32>(a, b, n_rows, ff, ff.running_mean, ff.running_var, 0, e, write, mu_f, is_f);
 }
 
 // ---- finalisation of per-tile rows by the launch's last workgroups (conv_stats_done in sparse_conv.hip, bn_reduce_fin_k in batchnorm.hip) ------

@@ -1,4 +1,4 @@
-// 16-bit storage formats of the element-wise kernels (batchnorm_h.hip, the Fmt16 instances of batchnorm2d.hip, the *_h max-pool of sparse_aux.hip): widen to fp32 on load,
+// 16-bit storage formats of the element-wise kernels (the Fmt16 instances of batchnorm.hip and batchnorm2d.hip: bn_fmt.hpp; the *_h max-pool of sparse_aux.hip): widen to fp32 on load,
 // round to nearest even ONCE on store.  8 elements travel as one 16-byte access (uint4).
 #pragma once
 #include "common.hpp"

@@ -454,8 +454,6 @@ size_t ws_bytes_of(const Geom& g) {
   return s.bytes();
 }
 
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 unsigned stream_blocks(long long units) {   // grid-stride element-wise passes: ~4 units per thread, at most 2048 workgroups
   const int64_t b = ceil_div(units, 256 * 4);
   return static_cast<unsigned>(b > 2048 ? 2048 : (b < 1 ? 1 : b));

@@ -9,7 +9,7 @@ the modules, autocast, CPU tensors, a single row in training mode ...) and the c
 modules one by one, so error behaviour stays torch's.  (`spconv.set_mixed_precision(True)` lifts the autocast rule for the 16-bit
 route below, and for it alone.)
 
-float16 / bfloat16 features take a route of their own (`fusable16`, `_BatchNormReLU16`, kernels in csrc/batchnorm_h.hip): x, y and
+float16 / bfloat16 features take a route of their own (`fusable16`, `_BatchNormReLU16`, the Fmt16 instances of the kernels in csrc/batchnorm.hip): x, y and
 the gradients stay in 16 bits, the arithmetic is fp32 with one rounding at the store, and the module's parameters and buffers are
 either all fp32 or all of x's dtype.  Nothing is cast on the way.  That route also takes the `residual` of a residual block's tail,
 y = relu(bn(x) + residual).

@@ -1,4 +1,4 @@
-"""GPU: BatchNorm1d (+residual, +ReLU) on float16 / bfloat16 rows (csrc/batchnorm_h.hip) through the raw C ABI, pcdet.ops.spconv.norm
+"""GPU: BatchNorm1d (+residual, +ReLU) on float16 / bfloat16 rows (the Fmt16 instances of csrc/batchnorm.hip) through the raw C ABI, pcdet.ops.spconv.norm
 and SparseSequential.  Cases and the float64 oracle results come from bn_half_cases.py (oracle/bn_oracle.py on rounded operands).
 
   1. exact cases: training forward (y, saved mean / invstd, running statistics after one and two steps, num_batches_tracked), eval
@@ -321,3 +321,59 @@ def test_what_the_16_bit_route_declines(gpu, dtype):
     assert norm.batch_norm_relu(nn.BatchNorm1d(c + 1).to(gpu).to(dtype), x, None) is None
     assert norm.batch_norm_relu(bn, x, None, residual=x.float()) is None           # a residual of another dtype
     assert not norm.fusable(bn, None, x, c)                                        # the fp32 predicate keeps its meaning
+
+
+def _bits(t):
+    return t.view({torch.float32: torch.int32, torch.int64: torch.int64}.get(t.dtype, torch.int16))
+
+
+def _cross_format_call(x32, dy32, res32, gamma, beta, dtype):
+    """Training forward (ReLU, tracked statistics, momentum None from num_batches_tracked 3), the eval-style apply with a residual on
+    that call's mean / invstd, then backward with batch_stats = 0 and relu = 0, through the raw C ABI with fp32 parameters: the fp32
+    entry points (forward, apply_res, backward) for torch.float32, the _h ones (param_dtype 0) otherwise."""
+    n, c = x32.shape
+    gpu = x32.device
+    x, dy, res = x32.to(dtype), dy32.to(dtype), res32.to(dtype)
+    assert all(torch.equal(a.float(), b) for a, b in ((x, x32), (dy, dy32), (res, res32)))   # the grid is exact in the format
+    mean, invstd, dgamma, dbeta = (torch.full((c,), FILL, device=gpu) for _ in range(4))
+    rm, rv = torch.linspace(-1.0, 1.0, c, device=gpu), torch.linspace(0.5, 2.0, c, device=gpu)
+    nbt = torch.full((), 3, dtype=torch.int64, device=gpu)
+    y, y_res, dx = (torch.full_like(x, FILL) for _ in range(3))
+    s = nat.stream()
+    if dtype == torch.float32:
+        ws = nat.workspace(nat.call("fv2p_batchnorm_ws_bytes", n, c), gpu)
+        nat.call("fv2p_batchnorm_forward", x, n, c, 1e-3, -1.0, gamma, beta, 1, rm, rv, nbt, mean, invstd, y, ws, ws.numel(), s)
+        nat.call("fv2p_batchnorm_apply_res", x, n, c, mean, invstd, gamma, beta, 1, res, y_res, s)
+        nat.call("fv2p_batchnorm_backward", x, dy, n, c, mean, invstd, gamma, beta, 0, 0, dx, dgamma, dbeta, ws, ws.numel(), s)
+    else:
+        ws, code = _ws(c, gpu), DT_CODE[dtype]
+        nat.call("fv2p_batchnorm_forward_h", x, n, c, 1e-3, -1.0, gamma, beta, 1, None, rm, rv, nbt, mean, invstd, y, code, 0, ws, ws.numel(), s)
+        nat.call("fv2p_batchnorm_apply_h", x, n, c, mean, invstd, gamma, beta, 1, res, y_res, code, 0, s)
+        nat.call("fv2p_batchnorm_backward_h", x, dy, n, c, mean, invstd, gamma, beta, 0, 0, None, dx, None, dgamma, dbeta, code, 0, ws, ws.numel(), s)
+    torch.cuda.synchronize()
+    return dict(mean=mean, invstd=invstd, running_mean=rm, running_var=rv, num_batches_tracked=nbt, dbeta=dbeta, y=y, y_res=y_res, dx=dx)
+
+
+@pytest.mark.parametrize("shape", [(37, 5), (700, 12), (700, 24)], ids=lambda s: "x".join(str(v) for v in s))
+def test_the_three_formats_agree_bit_for_bit_on_values_all_of_them_hold(gpu, shape):
+    """x, dy and the residual on the grid k / 8, |k| <= 64: exact in fp32, float16 and bfloat16 (7 significant bits).  Their sums and sums
+    of squares are multiples of 1 / 64 far below 2^53 units: exact in fp64 in any order, so the different geometries of the width-4 and
+    width-8 reductions cannot show.  (37, 5) takes the element path in every format; (700, 12) the vector path in fp32 and the element
+    path in 16 bits; (700, 24) the vector path everywhere, on 3 partials in fp32 and 2 in 16 bits.  The statistics are then the same fp64
+    values (momentum None: the factor 1 / 4 from num_batches_tracked 3), y the same fp32 expression rounded once, and with
+    batch_stats = 0 and relu = 0 (c1 = c2 = 0, no mask: float16 underflow cannot enter) so is dx; dbeta is the exact sum of dy.  dgamma
+    is left out: its terms dy * xhat are not exact.  Nothing is a tolerance."""
+    n, c = shape
+    rng = np.random.default_rng(n * 1009 + c * 17)
+    grid = lambda: torch.from_numpy(rng.integers(-64, 65, size=shape).astype(np.float32) / 8).to(gpu)
+    x32, dy32, res32 = grid(), grid(), grid()
+    gamma = torch.from_numpy(rng.uniform(0.5, 1.5, size=c).astype(np.float32)).to(gpu)
+    beta = torch.from_numpy(rng.uniform(-0.75, 0.75, size=c).astype(np.float32)).to(gpu)
+    ref = _cross_format_call(x32, dy32, res32, gamma, beta, torch.float32)
+    assert int(ref["num_batches_tracked"].item()) == 4 and not any(bool((ref[k] == FILL).any()) for k in ("y", "y_res", "dx"))
+    for dtype in DTYPES:
+        got = _cross_format_call(x32, dy32, res32, gamma, beta, dtype)
+        for k in ("mean", "invstd", "running_mean", "running_var", "num_batches_tracked", "dbeta"):
+            assert torch.equal(_bits(got[k]), _bits(ref[k])), (dtype, k)
+        for k in ("y", "y_res", "dx"):
+            assert got[k].dtype == dtype and torch.equal(_bits(got[k]), _bits(ref[k].to(dtype))), (dtype, k)

@@ -439,7 +439,7 @@ def amp16(out_path=None):
 
 def bn16(out_path=None):
     """BatchNorm1d(eps=1e-3, momentum=0.01) + ReLU on [N, C] rows at the backbone's shapes, forward and forward + backward, three routes:
-      fp16 / bf16 op : the 16-bit op (csrc/batchnorm_h.hip) on float16 / bfloat16 tensors, module in the same dtype;
+      fp16 / bf16 op : the 16-bit op (the Fmt16 instances of csrc/batchnorm.hip) on float16 / bfloat16 tensors, module in the same dtype;
       torch 16       : nn.BatchNorm1d then nn.ReLU, one by one, on the same 16-bit tensors - what ran before the 16-bit op existed;
       fp32 op        : the fp32 fused op on fp32 tensors of the same shape.
     Each figure: the median of ROUNDS windows of REPS calls (events on the stream, after a warm-up), the routes taken alternately
