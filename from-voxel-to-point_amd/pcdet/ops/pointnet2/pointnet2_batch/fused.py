@@ -1,4 +1,4 @@
-"""Fused grid set-abstraction (csrc/sa_fused.hip, csrc/sa_fused_h.hip): what PointnetSAModuleMSG.forward (pointnet2_modules.py:30-62)
+"""Fused grid set-abstraction (csrc/sa_fused.hip): what PointnetSAModuleMSG.forward (pointnet2_modules.py:30-62)
 does after its ball query, for the bn=False shared MLP of the RoI head, without the grouped (R, C, M, S) tensor:
 
     sa_grid_max(per_point, per_centre, idx, w2)[r, i, :] = max_s relu(w2 @ relu(per_point[r, idx[r, i, s]] - per_centre[r, i]))

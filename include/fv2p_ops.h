@@ -814,7 +814,7 @@ size_t fv2p_sa_grid_bwd_gather_ws_bytes(int rois, int m, int s);
 int fv2p_sa_grid_bwd_gather(const float* per_point, const float* per_centre, const int* idx, const float* w2, const unsigned char* arg,
                             const float* grad_out, int rois, int n, int m, int s, int c, float* grad_point, float* grad_centre,
                             float* grad_w2, void* ws, size_t ws_bytes, fv2p_stream_t stream);
-/* The fused grid set-abstraction on float16 / bfloat16 rows (csrc/sa_fused_h.hip; dtype = FV2P_DT_F16 / FV2P_DT_BF16): per_point,
+/* The fused grid set-abstraction on float16 / bfloat16 rows (csrc/sa_fused.hip; dtype = FV2P_DT_F16 / FV2P_DT_BF16): per_point,
  * per_centre, out, grad_out and the row gradients are 16-bit elements of that one format, idx / arg as above.  w2 [c, c] is in the rows'
  * format (wd != 0: wd == dtype) or fp32 (wd == 0, the convention of `pd` above: the master weight beside autocast rows); an fp32 w2 is
  * rounded to nearest even on its way into LDS - the result has the bits of the call on w2.to(dtype), no 16-bit copy is made - and

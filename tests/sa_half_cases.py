@@ -1,4 +1,4 @@
-"""Cases of the 16-bit fused grid set-abstraction (csrc/sa_fused_h.hip) with their float64 references.  Host only; not a test module.
+"""Cases of the 16-bit fused grid set-abstraction (csrc/sa_fused.hip) with their float64 references.  Host only; not a test module.
 
 Random cases: the generators, shapes, padded tails and single-neighbour centres of tests/test_pointnet2_gpu.py's fused cases, the
 operands cast to float16 / bfloat16.  The reference is the kernel's stated arithmetic in float64:

@@ -1,4 +1,4 @@
-"""CPU: the 16-bit fused grid set-abstraction (csrc/sa_fused_h.hip) exists in header and library, sizes its workspace on the host,
+"""CPU: the 16-bit fused grid set-abstraction (csrc/sa_fused.hip) exists in header and library, sizes its workspace on the host,
 rejects bad arguments before anything touches a device, and pcdet.ops.pointnet2.pointnet2_batch.fused reaches it for float16 /
 bfloat16 rows - whatever the deterministic switch says - while float32 rows keep their three entry points.  The library calls are
 recorded, not executed."""

@@ -1,4 +1,4 @@
-"""The fused grid set-abstraction on float16 / bfloat16 rows (csrc/sa_fused_h.hip) on the GPU, against the kernel's stated arithmetic
+"""The fused grid set-abstraction on float16 / bfloat16 rows (csrc/sa_fused.hip) on the GPU, against the kernel's stated arithmetic
 in float64 (tests/sa_half_cases.py): a derived forward bound, the arg-max byte, the three gradients routed by that byte, exact-integer
 cases bit for bit, a centre whose maximum is 0, run-to-run and side-stream bit equality, the untouched float32 route, and the harness's
 sa_msg_grid under autocast.  Every bound comes from the number formats; the figures are printed before they are asserted."""
@@ -108,6 +108,20 @@ def test_exact_integer_case_is_bit_equal(gpu, s, dt, w32):
     for name in ("out", "grad_point", "grad_centre"):
         assert got[name].dtype == dt and torch.equal(got[name], c[name].to(dt)), name
     assert torch.equal(got["grad_w2"], c["grad_w2"].to(torch.float32 if w32 else dt))
+
+
+@pytest.mark.parametrize("on", [False, True], ids=["switch-off", "switch-on"])
+@pytest.mark.parametrize("s", [16, 32])
+def test_exact_integer_case_is_bit_equal_in_float32(gpu, s, on):
+    """The float32 leg of the case above: the float32 kernels on the same operands, with the LDS-atomic backward (fv2p_sa_grid_bwd, switch
+    off) and the fixed-order one (fv2p_sa_grid_bwd_gather, switch on) - integer sums are exact in any order -, held to the values the two
+    16-bit formats are held to."""
+    c = cases.exact_case(s)
+    with mode(on):
+        got = run(c, True, gpu)
+    assert torch.equal(got["arg"].long(), c["arg"])
+    for name in ("out", "grad_point", "grad_centre", "grad_w2"):
+        assert got[name].dtype == torch.float32 and torch.equal(got[name], c[name].float()), name
 
 
 @pytest.mark.parametrize("dt", cases.DTYPES, ids=cases.dtype_id)
