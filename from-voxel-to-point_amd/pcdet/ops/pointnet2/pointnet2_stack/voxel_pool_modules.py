@@ -6,10 +6,13 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import voxel_query_utils
+from . import voxel_pool_fused, voxel_query_utils
 
 
 class NeighborVoxelSAModuleMSG(nn.Module):
+    # max_pool groupers on float32 GPU rows run as one fused op (voxel_pool_fused: no grouped (M, C, S) tensor); False keeps every
+    # call on the torch composition below
+    FUSED = True
 
     def __init__(self, *, query_ranges: List[List[int]], radii: List[float], nsamples: List[int], mlps: List[List[int]],
                  use_xyz: bool = True, pool_method='max_pool'):
@@ -39,6 +42,23 @@ class NeighborVoxelSAModuleMSG(nn.Module):
                 nn.init.constant_(m.weight, 1.0)
                 nn.init.constant_(m.bias, 0)
 
+    def _fused_pool(self, k, new_coords, xyz, xyz_batch_cnt, new_xyz, new_xyz_batch_cnt, f_in, voxel2point_indices):
+        """Grouper k between mlps_in and mlps_out as one voxel_pool_max call -> (M, C), or None: the torch route below runs
+        (FUSED off, avg_pool, host or 16-bit tensors, autocast, a shape or a module the op does not take)."""
+        if not self.FUSED or self.pool_method != 'max_pool':
+            return None
+        grouper, pos = self.groupers[k], self.mlps_pos[k]
+        if type(pos) is not nn.Sequential or len(pos) != 2 or not voxel_pool_fused._plain_forward(pos) or not hasattr(grouper, "query"):
+            return None
+        conv, bn = pos[0], pos[1]
+        if not voxel_pool_fused.supported(f_in, None, conv, bn, xyz, new_xyz, m=new_xyz.shape[0], s=getattr(grouper, "nsample", None)):
+            return None
+        idx, empty = grouper.query(new_coords, xyz, xyz_batch_cnt, new_xyz, new_xyz_batch_cnt, voxel2point_indices)
+        pooled = voxel_pool_fused.voxel_pool_max(f_in, xyz, new_xyz, idx, empty, conv, bn)
+        if pooled is None:
+            raise RuntimeError("voxel_pool_max declined a call that supported() had accepted")
+        return pooled
+
     def forward(self, xyz, xyz_batch_cnt, new_xyz, new_xyz_batch_cnt, new_coords, features, voxel2point_indices):
         """-> new_features (M, sum_k mlps[k][-1])."""
         new_coords = new_coords[:, [0, 3, 2, 1]].contiguous()
@@ -46,6 +66,10 @@ class NeighborVoxelSAModuleMSG(nn.Module):
         for k in range(len(self.groupers)):
             f_in = self.mlps_in[k](features.permute(1, 0).unsqueeze(0)).permute(0, 2, 1).contiguous()
             f_in = f_in.view(-1, f_in.shape[-1])
+            pooled = self._fused_pool(k, new_coords, xyz, xyz_batch_cnt, new_xyz, new_xyz_batch_cnt, f_in, voxel2point_indices)
+            if pooled is not None:
+                outs.append(self.mlps_out[k](pooled.permute(1, 0).unsqueeze(0)).squeeze(dim=0).permute(1, 0))
+                continue
             gf, gxyz, empty = self.groupers[k](new_coords, xyz, xyz_batch_cnt, new_xyz, new_xyz_batch_cnt, f_in,
                                                voxel2point_indices)
             gf[empty] = 0

@@ -25,26 +25,36 @@ VoxelQuery = G.autograd_op("VoxelQuery", _voxel_query)
 voxel_query = VoxelQuery.apply
 
 
+def local_rows(idx, empty, starts, batch_ids):
+    """Global point rows (M, S) of the voxel query -> rows local to each query's own sample, as grouping_operation wants them:
+    the start row of the query's sample is subtracted ONCE (starts (B) first row of every sample, batch_ids (M) sample of every
+    query), empty queries come back as row 0.  Plain torch, on whatever device the tensors live."""
+    idx = idx - starts.to(idx.device)[batch_ids.long()].view(-1, 1).to(idx.dtype)
+    idx[empty] = 0
+    return idx
+
+
 class VoxelQueryAndGrouping(nn.Module):
     def __init__(self, max_range: int, radius: float, nsample: int):
         super().__init__()
         self.max_range, self.radius, self.nsample = max_range, radius, nsample
 
+    def query(self, new_coords, xyz, xyz_batch_cnt, new_xyz, new_xyz_batch_cnt, voxel2point_indices):
+        """-> (idx (M, S) GLOBAL point rows, empty_ball_mask (M)): the voxel query alone (empty queries hold row 0)."""
+        if xyz.shape[0] != int(xyz_batch_cnt.sum()) or new_coords.shape[0] != int(new_xyz_batch_cnt.sum()):
+            raise AssertionError("rows and batch counts disagree")
+        return voxel_query(self.max_range, self.radius, self.nsample, xyz, new_xyz, new_coords, voxel2point_indices)
+
     def forward(self, new_coords, xyz, xyz_batch_cnt, new_xyz, new_xyz_batch_cnt, features, voxel2point_indices):
         """-> (grouped_features (M, C, S), grouped_xyz (M, 3, S), empty_ball_mask (M)).
 
-        The query returns global rows; grouping wants rows local to the sample.  The reference converts twice in a row
-        (:84-99: once per sample block of a (B, M/B, S) view, once per batch-index mask) — with one sample per batch, the only
-        case its configs reach, both are no-ops; both are kept so that multi-sample results stay what the reference gives."""
-        if xyz.shape[0] != int(xyz_batch_cnt.sum()) or new_coords.shape[0] != int(new_xyz_batch_cnt.sum()):
-            raise AssertionError("rows and batch counts disagree")
-        idx, empty = voxel_query(self.max_range, self.radius, self.nsample, xyz, new_xyz, new_coords, voxel2point_indices)
+        The query returns global rows; grouping wants rows local to the sample.  The reference's live conversion (:97-102) subtracts
+        the start of the query's own sample, once, per batch-index mask; the per-block loop above it (:85-93) sits inside a string
+        literal and never runs.  local_rows is that one conversion.  (Converting twice - what this class did before - is a no-op
+        with one sample only: from the second sample on it gave global - 2 * start, rows of another sample or negative ones.)"""
+        idx, empty = self.query(new_coords, xyz, xyz_batch_cnt, new_xyz, new_xyz_batch_cnt, voxel2point_indices)
         starts = torch.cumsum(xyz_batch_cnt, 0) - xyz_batch_cnt                                   # first row of every sample
-        b = xyz_batch_cnt.shape[0]
-        idx = (idx.view(b, -1, self.nsample) - starts.view(b, 1, 1).to(idx.dtype)).view(-1, self.nsample)
-        idx[empty] = 0
-        idx = idx - starts[new_coords[:, 0].long()].view(-1, 1).to(idx.dtype)
-        idx[empty] = 0
-        grouped_xyz = pointnet2_utils.grouping_operation(xyz, xyz_batch_cnt, idx.contiguous(), new_xyz_batch_cnt)
-        grouped_features = pointnet2_utils.grouping_operation(features, xyz_batch_cnt, idx.contiguous(), new_xyz_batch_cnt)
+        idx = local_rows(idx, empty, starts, new_coords[:, 0]).contiguous()
+        grouped_xyz = pointnet2_utils.grouping_operation(xyz, xyz_batch_cnt, idx, new_xyz_batch_cnt)
+        grouped_features = pointnet2_utils.grouping_operation(features, xyz_batch_cnt, idx, new_xyz_batch_cnt)
         return grouped_features, grouped_xyz, empty

@@ -1234,6 +1234,48 @@ int fv2p_linear_bn_backward(const float* x, const float* z, const float* dy, int
                             int batch_stats, float* du, float* dx, float* dw, float* dgamma, float* dbeta, void* ws,
                             size_t ws_bytes, fv2p_stream_t stream);
 
+/* ---- Voxel R-CNN RoI-grid pooling: NeighborVoxelSAModuleMSG between mlps_in and mlps_out as one op ----------------------------
+ * What a grouper of the module does after its voxel query with pool_method 'max_pool' (csrc/voxel_pool.hip), fp32 only, without a
+ * tensor proportional to m * c * s.  f [n][c] the mlps_in rows, xyz [n][3], new_xyz [m][3], idx [m][s] GLOBAL rows of the voxel
+ * query (int32), empty [m] one byte per query (non-zero: the query found nothing), w [c][3] the Conv2d(3, c, 1, bias=False)
+ * weight, gamma / beta / running_mean / running_var [c] and num_batches_tracked of its BatchNorm2d.  With
+ * d[i][j] = xyz[idx[i][j]] - new_xyz[i] (formed in fp32; zero for an empty query):
+ *     out[i][ch] = max_j relu(f[idx[i][j]][ch] + BN(w d[i][j])[ch])        (empty query: relu of the BatchNorm of zero)
+ * BN with batch statistics over the m * s positions (training != 0: biased variance, running statistics moved with torch's
+ * semantics - unbiased running_var, momentum < 0 is momentum=None, num_batches_tracked += 1 - when running_mean is not NULL) or
+ * with the running statistics (training == 0: nothing but out / arg / saved is written).  The statistics follow in fp64 from nine
+ * sums over d (sum d, sum d d^T), never from the c-channel tensor.  arg [m][c] (NULL: no backward will follow) receives the winning
+ * sample: the lowest j on ties, as max_pool2d scans; a NaN candidate makes the output NaN.  saved: fv2p_voxel_pool_saved_bytes(c)
+ * bytes the backward reads (the nine sums, mean and invstd per channel, all fp64).
+ * An idx entry outside [0, n) in a non-empty query reads as a zero row of f AND of xyz and receives no gradient: no input makes a
+ * kernel leave its buffers.
+ *   fv2p_voxel_pool_supported : 1 when c % 4 == 0, 4 <= c <= 128, 1 <= s <= 64, m >= 1 and m * s < 2^31 (FV2P_ELIMIT otherwise)
+ *   fv2p_voxel_pool_blocks    : the fixed query blocks of the two partial-sum passes; depends on m only, 0 for m < 1
+ *   fv2p_voxel_pool_ws_bytes / _backward_ws_bytes : pure host functions, 0 outside the limits (backward: also from m * c or n * c
+ *                               = 2^31 on, the 32-bit entry numbers of fv2p_scatter_add), never decreasing in m
+ *   fv2p_voxel_pool_forward   : moments (training) -> fold -> pool: three launches
+ *   fv2p_voxel_pool_backward  : g = grad_out * [out > 0]; grad_f [n][c] is WRITTEN (zero fill, then fv2p_scatter_add with one
+ *                               channel per entry: fixed order); grad_w [c][3], grad_gamma, grad_beta [c] from per-block fp64
+ *                               partials folded in block order and the closed forms of DESIGN "Voxel pooling".  Any of the four may
+ *                               be NULL and is then not computed.  `training` as in the forward call that wrote `saved`.
+ * f, out and grad_out must be 16-byte aligned.  No float atomics, no workgroup waits for another: every output is bit-identical
+ * from run to run.  Every call enqueues all of its launches on `stream` and returns. */
+int fv2p_voxel_pool_supported(int64_t m, int s, int c);
+int fv2p_voxel_pool_blocks(int64_t m);
+size_t fv2p_voxel_pool_saved_bytes(int c);
+size_t fv2p_voxel_pool_ws_bytes(int64_t m, int s, int c);
+size_t fv2p_voxel_pool_backward_ws_bytes(int64_t m, int s, int c, int64_t n);
+int fv2p_voxel_pool_forward(const float* f, const float* xyz, const float* new_xyz, const int* idx, const unsigned char* empty,
+                            int64_t n, int64_t m, int s, int c, const float* w, const float* gamma, const float* beta,
+                            float* running_mean, float* running_var, int64_t* num_batches_tracked, float momentum, float eps,
+                            int training, float* out, unsigned char* arg, double* saved, void* ws, size_t ws_bytes,
+                            fv2p_stream_t stream);
+int fv2p_voxel_pool_backward(const float* xyz, const float* new_xyz, const int* idx, const unsigned char* empty, int64_t n,
+                             int64_t m, int s, int c, const float* w, const float* gamma, const float* out,
+                             const unsigned char* arg, const double* saved, const float* grad_out, int training, float* grad_f,
+                             float* grad_w, float* grad_gamma, float* grad_beta, void* ws, size_t ws_bytes,
+                             fv2p_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Per-kernel timings on one GPU (events on the launch stream). Not part of the product or of bench.py; used to
-iterate on kernel variants:  python tools/microbench.py [conv|conv16|amp16|bn16|bn2d|bn2d16|linbn|bev16|beventry|exit16|batch16|sa16|dcn|dcn16|dcn16bwd|fps|voxel|nms|all]"""
+iterate on kernel variants:  python tools/microbench.py [conv|conv16|amp16|bn16|bn2d|bn2d16|linbn|voxelpool|bev16|beventry|exit16|batch16|sa16|dcn|dcn16|dcn16bwd|fps|voxel|nms|all]"""
 import os
 import sys
 import time
@@ -1034,6 +1034,123 @@ def linbn(out_path=None):
     _write(lines + pieces, out_path)
 
 
+VOXELPOOL_GROUPERS = [   # (name, stride of the source, query range, radius): the car config's ROI_GRID_POOL, nsample 16, MLPS [32, 32]
+    ("x_conv3 r2", 4, [2, 2, 2], 0.4), ("x_conv3 r4", 4, [4, 4, 4], 0.8), ("x_conv4 r2", 8, [2, 2, 2], 0.8), ("x_conv4 r4", 8, [4, 4, 4], 1.6)]
+
+
+def _voxelpool_scene(stride, batch=2, rois=128, grid=6):
+    """Occupied voxels of `batch` synthetic KITTI-like clouds at `stride` x the base voxel, and rois x grid^3 RoI-grid points per
+    sample around car-sized boxes on the clouds -> CPU tensors in the layout NeighborVoxelSAModuleMSG.forward takes."""
+    from fv2p_harness import synth
+    vs = synth.KITTI_VOXEL * stride
+    dims = np.ceil((synth.KITTI_RANGE[3:] - synth.KITTI_RANGE[:3]) / vs - 1e-6).astype(np.int64)   # x, y, z
+    vol = -np.ones((batch, dims[2], dims[1], dims[0]), np.int32)
+    xyz, new_xyz, new_coords, cnt = [], [], [], []
+    lo = 0
+    for b in range(batch):
+        rng = np.random.default_rng(100 + b)
+        pts = synth.lidar_cloud(b, 16384)[:, :3]
+        c = np.unique(np.floor((pts - synth.KITTI_RANGE[:3]) / vs).astype(np.int64).clip(0, dims - 1), axis=0)
+        vol[b, c[:, 2], c[:, 1], c[:, 0]] = lo + np.arange(len(c))
+        xyz.append(((c + 0.5) * vs + synth.KITTI_RANGE[:3]).astype(np.float32))
+        centre = pts[rng.integers(0, len(pts), rois)] + rng.normal(0, 0.3, (rois, 3))
+        yaw = rng.uniform(-np.pi, np.pi, rois)
+        size = np.array([3.9, 1.6, 1.56]) * rng.uniform(0.8, 1.2, (rois, 3))
+        t = (np.stack(np.meshgrid(*[np.arange(grid)] * 3, indexing="ij"), -1).reshape(-1, 3) + 0.5) / grid - 0.5        # (216, 3)
+        loc = t[None] * size[:, None]
+        cs, sn = np.cos(yaw)[:, None], np.sin(yaw)[:, None]
+        g = np.stack([loc[..., 0] * cs - loc[..., 1] * sn, loc[..., 0] * sn + loc[..., 1] * cs, loc[..., 2]], -1) + centre[:, None]
+        g = g.reshape(-1, 3).astype(np.float32)
+        qc = np.floor((g - synth.KITTI_RANGE[:3]) / vs).astype(np.int64).clip(0, dims - 1)   # (grid points outside the range query its border voxel)
+        new_xyz.append(g)
+        new_coords.append(np.concatenate([np.full((len(g), 1), b), qc], 1).astype(np.int32))
+        cnt.append(len(c))
+        lo += len(c)
+    return dict(xyz=torch.from_numpy(np.concatenate(xyz)), xyz_batch_cnt=torch.tensor(cnt, dtype=torch.int32),
+                new_xyz=torch.from_numpy(np.concatenate(new_xyz)), new_xyz_batch_cnt=torch.tensor([rois * grid ** 3] * batch, dtype=torch.int32),
+                new_coords=torch.from_numpy(np.concatenate(new_coords)), vol=torch.from_numpy(vol))
+
+
+def voxelpool(out_path=None):
+    """NeighborVoxelSAModuleMSG with one grouper, the four groupers of the car config's RoI-grid pooling at batch 2 (M = 2 x 128 x 216
+    queries, S = 16, C = 32, 64 input channels), forward and forward + backward of the whole module, two routes on copies of the same
+    weights: FUSED = True (csrc/voxel_pool.hip between mlps_in and mlps_out) and FUSED = False (the grouped torch composition).  Each
+    figure: the median of ROUNDS windows of REPS calls, the routes taken alternately in one process, +- half the range of the windows."""
+    import copy
+    from pcdet.ops.pointnet2.pointnet2_stack.voxel_pool_modules import NeighborVoxelSAModuleMSG
+    dev = torch.device("cuda:0")
+    ROUNDS, REPS, S, C, CIN = 7, 10, 16, 32, 64
+    lines = ["Voxel R-CNN RoI-grid pooling (car config, batch 2), one grouper per row, us per module call: median of %d windows of %d calls, +- half the range" % (ROUNDS, REPS),
+             "%-11s %7s %7s %6s | %-15s %-15s | %-15s %-15s | %s" % ("grouper", "N", "M", "empty", "fwd fused", "fwd grouped", "fwd+bwd fused", "fwd+bwd grouped",
+                                                                   "fused ahead fwd+bwd by more than the larger spread")]
+    scenes, ops = {}, []
+    for name, stride, qrange, radius in VOXELPOOL_GROUPERS:
+        if stride not in scenes:
+            scenes[stride] = {k: v.to(dev) for k, v in _voxelpool_scene(stride).items()}
+        t = scenes[stride]
+        n, m = t["xyz"].shape[0], t["new_xyz"].shape[0]
+        torch.manual_seed(0)
+        feats = torch.randn(n, CIN, device=dev, requires_grad=True)
+        g = torch.randn(m, C, device=dev)
+        mods = {}
+        base = NeighborVoxelSAModuleMSG(query_ranges=[qrange], radii=[radius], nsamples=[S], mlps=[[CIN, C, C]]).to(dev)
+        for route, fused in (("fused", True), ("grouped", False)):
+            mods[route] = copy.deepcopy(base)
+            mods[route].FUSED = fused
+        coords = t["new_coords"][:, [0, 3, 2, 1]].contiguous()
+        _, empty = base.groupers[0].query(coords, t["xyz"], t["xyz_batch_cnt"], t["new_xyz"], t["new_xyz_batch_cnt"], t["vol"])
+
+        def fwd(mod):
+            return lambda: mod(t["xyz"], t["xyz_batch_cnt"], t["new_xyz"], t["new_xyz_batch_cnt"], t["new_coords"], feats, t["vol"])
+
+        def both(mod):
+            f = fwd(mod)
+
+            def run():
+                f().backward(g)
+                feats.grad = None
+                for p in mod.parameters():
+                    p.grad = None
+            return run
+        tf = _windows({k: fwd(v) for k, v in mods.items()}, ROUNDS, REPS)
+        tb = _windows({k: both(v) for k, v in mods.items()}, ROUNDS, REPS)
+        spread = lambda x: (max(x) - min(x)) / 2
+        wins = np.median(tb["grouped"]) - np.median(tb["fused"]) > max(spread(tb["fused"]), spread(tb["grouped"]))
+        lines.append("%-11s %7d %7d %5.0f%% | %s %s | %s %s | %s" % (name, n, m, 100.0 * float(empty.float().mean()), _cell(tf["fused"]), _cell(tf["grouped"]),
+                                                                   _cell(tb["fused"]), _cell(tb["grouped"]), "yes" if wins else "no"))
+        print(lines[-1], flush=True)
+        # the op alone through the C entry points, on the grouper's own index lists
+        import fv2p_native as nat
+        with torch.no_grad():
+            idx, _ = base.groupers[0].query(coords, t["xyz"], t["xyz_batch_cnt"], t["new_xyz"], t["new_xyz_batch_cnt"], t["vol"])
+            f_in = torch.randn(n, C, device=dev)
+            conv, bn = base.mlps_pos[0][0], base.mlps_pos[0][1]
+            w, em = conv.weight.detach().view(C, 3).contiguous(), empty.view(torch.uint8)
+            rm, rv, nbt = bn.running_mean.clone(), bn.running_var.clone(), bn.num_batches_tracked.clone()
+            out, arg = torch.empty(m, C, device=dev), torch.empty(m, C, dtype=torch.uint8, device=dev)
+            keep = torch.empty(nat.lib().fv2p_voxel_pool_saved_bytes(C) // 8, dtype=torch.float64, device=dev)
+            gf, gw, gg, gb = torch.empty(n, C, device=dev), torch.empty(C, 3, device=dev), torch.empty(C, device=dev), torch.empty(C, device=dev)
+            ws = nat.workspace(max(nat.lib().fv2p_voxel_pool_ws_bytes(m, S, C), nat.lib().fv2p_voxel_pool_backward_ws_bytes(m, S, C, n)), dev)
+            st = nat.stream()
+            op_f = lambda: nat.call("fv2p_voxel_pool_forward", f_in, t["xyz"], t["new_xyz"], idx, em, n, m, S, C, w, bn.weight, bn.bias, rm, rv, nbt,
+                                    0.1, 1e-5, 1, out, arg, keep, ws, ws.numel(), st)
+            op_b = lambda a: (lambda: nat.call("fv2p_voxel_pool_backward", t["xyz"], t["new_xyz"], idx, em, n, m, S, C, w, bn.weight, out, arg, keep, g, 1,
+                                               a, gw, gg, gb, ws, ws.numel(), st))
+            op_f()
+            tp = _windows({"fwd": op_f, "bwd_par": op_b(None), "bwd_all": op_b(gf)}, ROUNDS, REPS)
+        ops.append("%-11s | %s | %s | %s" % (name, _cell(tp["fwd"]), _cell(tp["bwd_par"]), _cell(tp["bwd_all"])))
+    lines += ["", "the op alone through the C entry points (training mode), us: forward (moments, fold, pool) | backward without grad_F (route, fold) | "
+              "backward with grad_F (+ zero fill and the fixed-order scatter-add of M C single-channel entries)"] + ops
+    m = 2 * 128 * 216
+    lines += ["", "algorithmic bytes per grouper at M = %d, S = %d, C = %d (from the shapes):" % (m, S, C),
+              "  grouped (M, C, S) float32 tensor, written or read by every step of the torch chain: %.1f MB" % (m * C * S * 4 / 1e6),
+              "  fused forward: %.1f MB gathered F rows + %.1f MB (idx, xyz rows: moments and pool) + %.1f MB (out, arg)" % (
+                  m * S * C * 4 / 1e6, 2 * m * S * 16 / 1e6, m * C * 5 / 1e6),
+              "  fused backward: %.1f MB (out, grad_out, arg read; g and destinations written) + the scatter-add of %d single-channel entries" % (
+                  m * C * (4 + 4 + 1 + 4 + 4) / 1e6, m * C)]
+    _write(lines, out_path)
+
+
 def linbn_once():
     """One forward + backward of the fused op per layer of LINBN_LAYERS, for `rocprofv3 --kernel-trace --stats -- python tools/microbench.py linbn_once`."""
     from torch import nn
@@ -1532,6 +1649,9 @@ if __name__ == "__main__":
         sys.exit(0)
     if which == "linbn":   # python tools/microbench.py linbn [profiles/linear_bn.txt]
         linbn(sys.argv[2] if len(sys.argv) > 2 else None)
+        sys.exit(0)
+    if which == "voxelpool":   # python tools/microbench.py voxelpool [profiles/voxel_pool.txt]
+        voxelpool(sys.argv[2] if len(sys.argv) > 2 else None)
         sys.exit(0)
     if which == "linbn_once":   # rocprofv3 --kernel-trace --stats -- python tools/microbench.py linbn_once
         linbn_once()
