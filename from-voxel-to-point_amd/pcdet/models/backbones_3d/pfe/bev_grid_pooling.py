@@ -105,9 +105,8 @@ class BEVGridPooling(nn.Module):
         if len(mods) == 3:   # Linear -> BatchNorm1d -> ReLU: the pair after the GEMM as one fused op where it applies
             from pcdet.ops.spconv import linear as _linear
             from pcdet.ops.spconv.norm import batch_norm_relu
-            fused = None
-            if _linear.fusable(*mods, feats) and _linear.pays(feats.shape[0], mods[0].in_features, mods[0].out_features):
-                fused = _linear.linear_bn_relu(mods[0], mods[1], feats, mods[2])   # the GEMM as well (csrc/linear_bn.hip)
+            # the GEMM as well (csrc/linear_bn.hip; behind the 16-bit gather csrc/linear_bn_h.hip) where it pays at this shape
+            fused = _linear.try_rows(mods[0], mods[1], mods[2], feats)
             if fused is None:
                 feats = mods[0](feats)
                 fused = batch_norm_relu(mods[1], feats, mods[2])

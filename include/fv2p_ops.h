@@ -1234,6 +1234,50 @@ int fv2p_linear_bn_backward(const float* x, const float* z, const float* dy, int
                             int batch_stats, float* du, float* dx, float* dw, float* dgamma, float* dbeta, void* ws,
                             size_t ws_bytes, fv2p_stream_t stream);
 
+/* ---- The same triple on float16 / bfloat16 point rows (csrc/linear_bn_h.hip; every product on v_mfma_f32_16x16x32_{f16,bf16}) ----
+ * `dt` (FV2P_DT_F16 / FV2P_DT_BF16) names the format T of x [n][cin], z, y, dy, du [n][cout] and dx; `wd` is 0 (w and dw are fp32: a
+ * master weight, rounded ONCE to T on its way into LDS - the bits of w.to(T), no 16-bit copy in memory) or equal to dt; `pd` is 0
+ * (fp32) or equal to dt and names the format of gamma, beta, running_mean, running_var, dgamma and dbeta.  Any other value returns
+ * FV2P_EINVAL with "dtype" in the message.  mean and invstd are fp32.  Limits as the fp32 op: n >= 1 (training mode: n >= 2),
+ * cin 1 .. 1024, cout 1 .. 512, FV2P_EINVAL outside, judged before any pointer is touched; 16-byte accesses where the row lengths
+ * are multiples of 8 and the bases 16-byte aligned, element by element otherwise.  With u the unit roundoff of T:
+ *   1. pre-activation  acc = sum_k x * w: products of two T values are exact, fp32 accumulators in a fixed order;
+ *                      z = round_T(acc), stored [n][cout] in T, IS the op's pre-activation everywhere: everything downstream reads
+ *                      the stored 16-bit z, widened (torch's bn(linear(x)) on 16-bit rows), so the forward pass and the ReLU mask the
+ *                      backward pass recomputes agree by construction.
+ *   2. training mode   sum z / sum z^2 of the ROUNDED z per channel from the GEMM's epilogue, fp64 partials per row tile folded in
+ *                      a fixed order of the tiles by a later launch; mean / invstd fp32; running statistics (momentum, momentum < 0 = None, unbiased
+ *                      variance) and num_batches_tracked in the parameters' format with one rounding;
+ *                      y = round_T(relu?((z - mean) * invstd * gamma + beta)) in fp32.  Three launches.
+ *   3. eval mode       one launch; z is stored only when a buffer is passed; y from the widened z with the caller's fp32 mean / invstd.
+ *   4. backward        the ReLU mask from z with the forward's expression; dgamma, dbeta, c1, c2 from fp64 sums in a fixed order;
+ *                      du = gamma * invstd * (dz - c1 - xhat * c2) in fp32, rounded ONCE to T into the caller's du (the staging
+ *                      buffer and the MFMA operand); dx = du * w, fp32 accumulators, one rounding to T (dx NULL: skipped);
+ *                      dw = du^T * x over a fixed split of the rows: at most 128 rows per fp32 accumulator chain, chains summed in
+ *                      fp64, partial tiles folded in split order, ONE rounding into a T weight or an fp32 store for wd = 0 (dw NULL:
+ *                      skipped); dgamma / dbeta in the parameters' format.
+ *   5. determinism     no float atomics, no workgroup waits for another, no fp32 copy of any [n, .] tensor: bit-identical results
+ *                      from run to run.
+ * Host-only queries (no device needed): fv2p_linear_bn_h_supported: 1 for a shape inside the limits with valid dt / wd / pd, else 0;
+ * fv2p_linear_bn_h_ws_bytes: the workspace of either direction (0 outside the limits); fv2p_linear_bn_h_splits: the row chunks of
+ * the weight-gradient pass; fv2p_linear_bn_h_pays: 1 where the op measured faster, forward + backward, than the library's 16-bit
+ * product + fv2p_batchnorm_*_h (profiles/linear_bn_half.txt). */
+int fv2p_linear_bn_h_supported(int64_t n, int cin, int cout, int dt, int wd, int pd);
+size_t fv2p_linear_bn_h_ws_bytes(int64_t n, int cin, int cout);
+int fv2p_linear_bn_h_splits(int64_t n, int cin, int cout);
+int fv2p_linear_bn_h_pays(int64_t n, int cin, int cout, int dt);
+int fv2p_linear_bn_forward_h(const void* x, int64_t n, int cin, const void* w, int cout, float eps, float momentum,
+                             const void* gamma, const void* beta, int relu, void* running_mean, void* running_var,
+                             int64_t* num_batches_tracked, void* z, float* mean, float* invstd, void* y, int dt, int wd, int pd,
+                             void* ws, size_t ws_bytes, fv2p_stream_t stream);
+int fv2p_linear_bn_forward_eval_h(const void* x, int64_t n, int cin, const void* w, int cout, const float* mean,
+                                  const float* invstd, const void* gamma, const void* beta, int relu, void* z, void* y, int dt,
+                                  int wd, int pd, fv2p_stream_t stream);
+int fv2p_linear_bn_backward_h(const void* x, const void* z, const void* dy, int64_t n, int cin, const void* w, int cout,
+                              const float* mean, const float* invstd, const void* gamma, const void* beta, int relu,
+                              int batch_stats, void* du, void* dx, void* dw, void* dgamma, void* dbeta, int dt, int wd, int pd,
+                              void* ws, size_t ws_bytes, fv2p_stream_t stream);
+
 /* ---- Voxel R-CNN RoI-grid pooling: NeighborVoxelSAModuleMSG between mlps_in and mlps_out as one op ----------------------------
  * What a grouper of the module does after its voxel query with pool_method 'max_pool' (csrc/voxel_pool.hip), fp32 only, without a
  * tensor proportional to m * c * s.  f [n][c] the mlps_in rows, xyz [n][3], new_xyz [m][3], idx [m][s] GLOBAL rows of the voxel

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Per-kernel timings on one GPU (events on the launch stream). Not part of the product or of bench.py; used to
-iterate on kernel variants:  python tools/microbench.py [conv|conv16|amp16|bn16|bn2d|bn2d16|linbn|voxelpool|bev16|beventry|exit16|batch16|sa16|dcn|dcn16|dcn16bwd|fps|voxel|nms|all]"""
+iterate on kernel variants:  python tools/microbench.py [conv|conv16|amp16|bn16|bn2d|bn2d16|linbn|linbn16|voxelpool|bev16|beventry|exit16|batch16|sa16|dcn|dcn16|dcn16bwd|fps|voxel|nms|all]"""
 import os
 import sys
 import time
@@ -1034,6 +1034,71 @@ def linbn(out_path=None):
     _write(lines + pieces, out_path)
 
 
+def linbn16(out_path=None):
+    """The same layers on float16 / bfloat16 rows (49 152 key-point rows, every channel pair of LINBN_LAYERS, both dtypes), forward and
+    forward + backward, three routes: (a) the 16-bit fused op (pcdet.ops.spconv.linear.linear_bn_relu16, csrc/linear_bn_h.hip);
+    (b) the route 16-bit rows take without it: fv2p_model.run_rows on the same 16-bit modules and tensors with pays16 off (the library's
+    16-bit product, then the 16-bit BatchNorm op); (c) the fp32 fused op on fp32 copies.  Each figure: the median of ROUNDS windows of
+    REPS calls, the routes taken alternately in one process, +- half the range of the windows.  fv2p_linear_bn_h_pays is filled from the
+    last column: (a) below (b), forward + backward, by more than the larger spread."""
+    from torch import nn
+    from fv2p_harness import fv2p_model
+    from pcdet.ops.spconv import linear
+    dev = torch.device("cuda:0")
+    ROUNDS, REPS, N = 7, 10, 49152
+    lines = ["Linear + BatchNorm1d (+ReLU) on 16-bit rows, n = %d rows, us per call: median of %d windows of %d calls, +- half the range" % (N, ROUNDS, REPS),
+             "(a) 16-bit fused op   (b) run_rows without it: the library's 16-bit product + the 16-bit BatchNorm op   (c) the fp32 fused op on fp32 copies",
+             "%-9s %-13s %-9s | %-15s %-15s %-15s | %-15s %-15s %-15s | %s" % ("dtype", "layer", "cin>cout", "fwd (a)", "fwd (b)", "fwd (c)", "fwd+bwd (a)",
+                                                                             "fwd+bwd (b)", "fwd+bwd (c)", "(a) beats (b) fwd+bwd by more than the larger spread")]
+    no_pay = lambda n, cin, cout, dt: False
+    for dtype in (torch.float16, torch.bfloat16):
+        for name, cin, cout, relu in LINBN_LAYERS:
+            torch.manual_seed(0)
+            x32 = torch.randn(N, cin, device=dev, requires_grad=True)
+            g32 = torch.randn(N, cout, device=dev)
+            x = x32.detach().to(dtype).requires_grad_(True)
+            g = g32.to(dtype)
+
+            def mods(dt):
+                m = [nn.Linear(cin, cout, bias=False), nn.BatchNorm1d(cout, eps=1e-3, momentum=0.01)] + ([nn.ReLU()] if relu else [])
+                return nn.Sequential(*m).to(dev).to(dt)
+            sa, sb, sc = mods(dtype), mods(dtype), mods(torch.float32)
+
+            def route_a():
+                y = linear.linear_bn_relu16(sa[0], sa[1], x, sa[2] if relu else None)
+                assert y is not None
+                return y
+
+            def route_b():
+                saved, linear.pays16 = linear.pays16, no_pay
+                try:
+                    return fv2p_model.run_rows(sb, x)
+                finally:
+                    linear.pays16 = saved
+
+            def route_c():
+                y = linear.linear_bn_relu(sc[0], sc[1], x32, sc[2] if relu else None)
+                assert y is not None
+                return y
+
+            def both(f, seq, xin, gin):
+                def run():
+                    f().backward(gin)
+                    xin.grad = None
+                    for p in seq.parameters():
+                        p.grad = None
+                return run
+            tf = _windows({"a": route_a, "b": route_b, "c": route_c}, ROUNDS, REPS)
+            tb = _windows({"a": both(route_a, sa, x, g), "b": both(route_b, sb, x, g), "c": both(route_c, sc, x32, g32)}, ROUNDS, REPS)
+            spread = lambda t: (max(t) - min(t)) / 2
+            wins = np.median(tb["b"]) - np.median(tb["a"]) > max(spread(tb["a"]), spread(tb["b"]))
+            lines.append("%-9s %-13s %-9s | %s %s %s | %s %s %s | %s" % (str(dtype).replace("torch.", ""), name, "%d>%d" % (cin, cout), _cell(tf["a"]),
+                                                                       _cell(tf["b"]), _cell(tf["c"]), _cell(tb["a"]), _cell(tb["b"]), _cell(tb["c"]),
+                                                                       "yes" if wins else "no"))
+            print(lines[-1], flush=True)
+    _write(lines, out_path)
+
+
 VOXELPOOL_GROUPERS = [   # (name, stride of the source, query range, radius): the car config's ROI_GRID_POOL, nsample 16, MLPS [32, 32]
     ("x_conv3 r2", 4, [2, 2, 2], 0.4), ("x_conv3 r4", 4, [4, 4, 4], 0.8), ("x_conv4 r2", 8, [2, 2, 2], 0.8), ("x_conv4 r4", 8, [4, 4, 4], 1.6)]
 
@@ -1161,6 +1226,21 @@ def linbn_once():
             x = torch.randn(49152, cin, device=dev, requires_grad=True)
             lin, bn = nn.Linear(cin, cout, bias=False).to(dev), nn.BatchNorm1d(cout, eps=1e-3, momentum=0.01).to(dev)
             linear.linear_bn_relu(lin, bn, x, nn.ReLU() if relu else None).sum().backward()
+    torch.cuda.synchronize()
+
+
+def linbn16_once():
+    """One forward + backward of the 16-bit fused op per layer of LINBN_LAYERS and dtype, for
+    `rocprofv3 --kernel-trace --stats -- python tools/microbench.py linbn16_once`."""
+    from torch import nn
+    from pcdet.ops.spconv import linear
+    dev = torch.device("cuda:0")
+    for _ in range(3):
+        for dtype in (torch.float16, torch.bfloat16):
+            for name, cin, cout, relu in LINBN_LAYERS:
+                x = torch.randn(49152, cin, device=dev).to(dtype).requires_grad_(True)
+                lin, bn = nn.Linear(cin, cout, bias=False).to(dev).to(dtype), nn.BatchNorm1d(cout, eps=1e-3, momentum=0.01).to(dev).to(dtype)
+                linear.linear_bn_relu16(lin, bn, x, nn.ReLU() if relu else None).backward(torch.ones(49152, cout, device=dev, dtype=dtype))
     torch.cuda.synchronize()
 
 
@@ -1649,6 +1729,12 @@ if __name__ == "__main__":
         sys.exit(0)
     if which == "linbn":   # python tools/microbench.py linbn [profiles/linear_bn.txt]
         linbn(sys.argv[2] if len(sys.argv) > 2 else None)
+        sys.exit(0)
+    if which == "linbn16":   # python tools/microbench.py linbn16 [profiles/linear_bn_half.txt]
+        linbn16(sys.argv[2] if len(sys.argv) > 2 else None)
+        sys.exit(0)
+    if which == "linbn16_once":   # rocprofv3 --kernel-trace --stats -- python tools/microbench.py linbn16_once
+        linbn16_once()
         sys.exit(0)
     if which == "voxelpool":   # python tools/microbench.py voxelpool [profiles/voxel_pool.txt]
         voxelpool(sys.argv[2] if len(sys.argv) > 2 else None)
