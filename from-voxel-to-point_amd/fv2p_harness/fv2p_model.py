@@ -231,7 +231,7 @@ def run_rows(seq, x):
         if KERNEL_GLUE and type(m) is nn.Linear and i + 1 < len(mods) and type(mods[i + 1]) is nn.BatchNorm1d:
             # Linear -> BatchNorm1d [-> ReLU] as one op (csrc/linear_bn.hip) where it applies and measured faster at this shape
             relu = mods[i + 2] if i + 2 < len(mods) and type(mods[i + 2]) is nn.ReLU else None
-            # (float16 / bfloat16 rows: the 16-bit op of csrc/linear_bn_h.hip, by fusable16 and pays16)
+            # (float16 / bfloat16 rows: the 16-bit formats of the same kernel source, by fusable16 and pays16)
             y = _linear.try_rows(m, mods[i + 1], relu, x)
             if y is not None:
                 x = y

@@ -105,7 +105,7 @@ class BEVGridPooling(nn.Module):
         if len(mods) == 3:   # Linear -> BatchNorm1d -> ReLU: the pair after the GEMM as one fused op where it applies
             from pcdet.ops.spconv import linear as _linear
             from pcdet.ops.spconv.norm import batch_norm_relu
-            # the GEMM as well (csrc/linear_bn.hip; behind the 16-bit gather csrc/linear_bn_h.hip) where it pays at this shape
+            # the GEMM as well (csrc/linear_bn.hip; behind the 16-bit gather its 16-bit formats) where it pays at this shape
             fused = _linear.try_rows(mods[0], mods[1], mods[2], feats)
             if fused is None:
                 feats = mods[0](feats)

@@ -1234,7 +1234,7 @@ int fv2p_linear_bn_backward(const float* x, const float* z, const float* dy, int
                             int batch_stats, float* du, float* dx, float* dw, float* dgamma, float* dbeta, void* ws,
                             size_t ws_bytes, fv2p_stream_t stream);
 
-/* ---- The same triple on float16 / bfloat16 point rows (csrc/linear_bn_h.hip; every product on v_mfma_f32_16x16x32_{f16,bf16}) ----
+/* ---- The same triple on float16 / bfloat16 point rows (the 16-bit formats of csrc/linear_bn.hip; every product on v_mfma_f32_16x16x32_{f16,bf16}) ----
  * `dt` (FV2P_DT_F16 / FV2P_DT_BF16) names the format T of x [n][cin], z, y, dy, du [n][cout] and dx; `wd` is 0 (w and dw are fp32: a
  * master weight, rounded ONCE to T on its way into LDS - the bits of w.to(T), no 16-bit copy in memory) or equal to dt; `pd` is 0
  * (fp32) or equal to dt and names the format of gamma, beta, running_mean, running_var, dgamma and dbeta.  Any other value returns

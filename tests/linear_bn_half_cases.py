@@ -1,5 +1,5 @@
 """Cases of the 16-bit Linear + BatchNorm1d (+ReLU) tests (test_linear_bn_half_cpu.py, test_linear_bn_half_gpu.py).  Host only, not a
-test module: operands ALREADY ROUNDED to the case's formats, references = the arithmetic contract of csrc/linear_bn_h.hip in float64,
+test module: operands ALREADY ROUNDED to the case's formats, references = the arithmetic contract of csrc/linear_bn.hip's 16-bit formats in float64,
 and bounds derived from the number formats alone - nothing in here is measured.
 
 T is float16 or bfloat16, u = 2^-11 / 2^-8 its unit roundoff; an fp32 accumulation costs 2^-24 per addition; 2^-24 absolute covers the

@@ -1,4 +1,4 @@
-"""CPU: the 16-bit Linear + BatchNorm1d (+ReLU) entry points (csrc/linear_bn_h.hip) exist and are declared, their host-side queries run
+"""CPU: the 16-bit Linear + BatchNorm1d (+ReLU) entry points (the 16-bit formats of csrc/linear_bn.hip) exist and are declared, their host-side queries run
 without a device, the Python side (pcdet.ops.spconv.linear: fusable16, linear_bn_relu16, run_rows) declines on host tensors, and the
 cases file keeps its own conditions: the ReLU kink, the range of z, and a host emulation of the arithmetic contract that stays inside
 every derived bound of linear_bn_half_cases.py."""

@@ -1,5 +1,5 @@
 """GPU: Linear(bias=False) -> BatchNorm1d [-> ReLU] on float16 / bfloat16 point rows as one op (pcdet.ops.spconv.linear: fusable16,
-linear_bn_relu16, _LinearBatchNormReLU16; csrc/linear_bn_h.hip) against the float64 references and the derived bounds of
+linear_bn_relu16, _LinearBatchNormReLU16; the 16-bit formats of csrc/linear_bn.hip) against the float64 references and the derived bounds of
 linear_bn_half_cases.py - nothing in a bound is measured:
 
   stage A  the op's stored 16-bit pre-activation z (read from the saved tensors) against x64 w64^T;
@@ -61,8 +61,10 @@ def _modules(ops, wdtype, pdtype, relu, affine, track, gpu, momentum=0.01, eps=c
 
 
 def _forward(mods, x):
-    y = linear.linear_bn_relu16(mods[0], mods[1], x, mods[2])
-    assert y is not None and y.dtype == x.dtype and type(y.grad_fn).__name__ == NODE
+    """Through linear_bn_relu16; fp32 rows (the exact case) through linear_bn_relu, the fp32 instance of the same kernel source."""
+    op, node = (linear.linear_bn_relu, "_LinearBatchNormReLUBackward") if x.dtype == torch.float32 else (linear.linear_bn_relu16, NODE)
+    y = op(mods[0], mods[1], x, mods[2])
+    assert y is not None and y.dtype == x.dtype and type(y.grad_fn).__name__ == node
     saved = y.grad_fn.saved_tensors   # x, z, mean, invstd, w, gamma, beta
     assert saved[1].dtype == x.dtype and saved[2].dtype == saved[3].dtype == torch.float32
     return y, saved[1].clone(), saved[2].clone(), saved[3].clone()
@@ -197,11 +199,15 @@ def test_eval_mode_without_grad_keeps_no_pre_activation(gpu):
 
 
 @pytest.mark.parametrize("n,cin,cout", [(130, 6, 20), (64, 32, 16)])
-@pytest.mark.parametrize("dtype", DTYPES, ids=dtype_id)
+@pytest.mark.parametrize("dtype", DTYPES + [torch.float32], ids=dtype_id)
 def test_exact_case_equals_the_oracle_bit_for_bit(gpu, dtype, n, cin, cout):
     """x in {-2, 2} balanced per column and one +-1 per weight row: z is a signed copy of a column, so mean = 0, var = 4, invstd = 0.5 with
     eps = 0 and integer gamma / beta give integer y.  Training-mode y, eval-mode y and the eval-mode dx (dz ternary, du a multiple of
-    0.5) must equal the oracle bit for bit; dw too (integers below 256)."""
+    0.5) must equal the oracle bit for bit; dw too (integers below 256).  float32 rows (linear_bn_relu) are held to the same oracle
+    values: the three formats of the one kernel source are pinned against each other.  Their eval route takes invstd from torch.rsqrt,
+    which has to give exactly 0.5 for 4.0 on the device."""
+    if dtype == torch.float32:
+        assert torch.rsqrt(torch.full((cout,), 4.0, device=gpu)).eq(0.5).all(), "torch.rsqrt(4.0) on the device is not exactly 0.5"
     rng = np.random.default_rng(n + cin)
     x = np.stack([rng.permutation(np.repeat([-2.0, 2.0], n // 2)) for _ in range(cin)], axis=1)
     w = np.zeros((cout, cin))
@@ -209,7 +215,7 @@ def test_exact_case_equals_the_oracle_bit_for_bit(gpu, dtype, n, cin, cout):
     gamma, beta = rng.integers(-2, 3, cout).astype(np.float64), rng.integers(-3, 4, cout).astype(np.float64)
     dy = ((rng.integers(0, 2, (n, cout)) * 2 - 1) * (rng.random((n, cout)) < 0.25)).astype(np.float64)
     z = x @ w.T
-    for pdtype in (dtype, torch.float32):
+    for pdtype in dict.fromkeys((dtype, torch.float32)):
         ops = dict(n=n, cin=cin, cout=cout, w=w, gamma=gamma, beta=beta, rm=np.zeros(cout), rv=np.full(cout, 4.0))
         for training in (True, False):
             mods = _modules(ops, dtype, pdtype, True, True, True, gpu, eps=0.0)

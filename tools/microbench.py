@@ -1036,7 +1036,7 @@ def linbn(out_path=None):
 
 def linbn16(out_path=None):
     """The same layers on float16 / bfloat16 rows (49 152 key-point rows, every channel pair of LINBN_LAYERS, both dtypes), forward and
-    forward + backward, three routes: (a) the 16-bit fused op (pcdet.ops.spconv.linear.linear_bn_relu16, csrc/linear_bn_h.hip);
+    forward + backward, three routes: (a) the 16-bit fused op (pcdet.ops.spconv.linear.linear_bn_relu16, the 16-bit formats of csrc/linear_bn.hip);
     (b) the route 16-bit rows take without it: fv2p_model.run_rows on the same 16-bit modules and tensors with pays16 off (the library's
     16-bit product, then the 16-bit BatchNorm op); (c) the fp32 fused op on fp32 copies.  Each figure: the median of ROUNDS windows of
     REPS calls, the routes taken alternately in one process, +- half the range of the windows.  fv2p_linear_bn_h_pays is filled from the
