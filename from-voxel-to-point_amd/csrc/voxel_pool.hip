@@ -19,8 +19,17 @@
 // order: no float atomics, no workgroup waits for another, every output is bit-identical from run to run.
 // An idx entry outside [0, n) is a row of zeros of F AND of xyz (d = 0 - new_xyz[i]) and receives no gradient, the rule of
 // sa_fused.hip: no input makes a kernel read or write outside its buffers.
+//
+// Row formats.  pool and route - the two kernels that touch F, out, grad_out and the staged g - are written once and instantiated for
+// F32, Fmt16<H16> and Fmt16<B16> (bn_fmt.hpp): the *_h entry points take float16 / bfloat16 rows (F, out, grad_out, grad_F) beside
+// the same fp32 coordinates and parameters.  A 16-bit row is widened on load; the sum, the ReLU, the maximum and the arg-max byte are
+// fp32 exactly as in the fp32 instance, out is rounded to nearest even ONCE at the store, the ReLU mask of the backward reads the
+// stored output widened, g (grad_out or 0: exact) is staged in the rows' format and grad_F goes through scatter_add_h (the fp32
+// association of fv2p_scatter_add, one rounding).  moments and the two folds never see F and are shared.
 #include "common.hpp"
 #include "bn_fold.hpp"
+#include "bn_fmt.hpp"
+#include <type_traits>
 
 namespace fv2p {
 
@@ -139,18 +148,40 @@ __global__ __launch_bounds__(256) void vp_fold_fwd_k(int64_t blocks, int c, long
 
 // ---- 3. pool: c / 4 lanes per query, each owns 4 consecutive channels; qpw queries per workgroup (the lanes that do not fill a
 // query are masked: c = 12 leaves one of 256).  The (d, row) entries of the workgroup's queries are formed once, into LDS rows
-// padded by one 16-byte slot (queries s slots apart would all read one bank group); the F rows come by 16-byte gathers, four in
-// flight per lane. ------------------------------------------------------------------------------------------------------------------
+// padded by one 16-byte slot (queries s slots apart would all read one bank group); the F rows come by 16-byte gathers (8-byte ones
+// of 16-bit rows), four in flight per lane. ------------------------------------------------------------------------------------------
+// 4 consecutive channels of a row in format R as fp32: one 16-byte (F32) or one 8-byte (Fmt16) access
+template <class R>
+__device__ __forceinline__ float4 vp_load4(const typename R::elem* p) {
+  if constexpr (sizeof(typename R::elem) == 4) {
+    return *reinterpret_cast<const float4*>(p);
+  } else {
+    const uint2 q = *reinterpret_cast<const uint2*>(p);
+    return make_float4(R::widen(static_cast<u16>(q.x & 0xffffu)), R::widen(static_cast<u16>(q.x >> 16)),
+                       R::widen(static_cast<u16>(q.y & 0xffffu)), R::widen(static_cast<u16>(q.y >> 16)));
+  }
+}
+template <class R>
+__device__ __forceinline__ void vp_store4(typename R::elem* p, const float4& v) {   // Fmt16: the one rounding, nearest even
+  if constexpr (sizeof(typename R::elem) == 4) {
+    *reinterpret_cast<float4*>(p) = v;
+  } else {
+    *reinterpret_cast<uint2*>(p) = make_uint2(static_cast<unsigned>(R::narrow(v.x)) | (static_cast<unsigned>(R::narrow(v.y)) << 16),
+                                              static_cast<unsigned>(R::narrow(v.z)) | (static_cast<unsigned>(R::narrow(v.w)) << 16));
+  }
+}
+
 __device__ __forceinline__ void vp_take(float g, const float4& a, const float4& e, int j, float* best, int* bj) {
   const float v = g + fmaf(a.x, e.x, fmaf(a.y, e.y, fmaf(a.z, e.z, a.w)));
   const float r = v < 0.f ? 0.f : v;            // relu; a NaN stays
   if (r > *best || r != r) { *best = r; *bj = j; }   // max_pool2d's scan: strict >, a NaN candidate always enters
 }
 
-__global__ __launch_bounds__(256) void vp_pool_k(int64_t m, int s, int c, int64_t n, int qpw, const float* __restrict__ f,
+template <class R>
+__global__ __launch_bounds__(256) void vp_pool_k(int64_t m, int s, int c, int64_t n, int qpw, const typename R::elem* __restrict__ f,
                                                  const float* __restrict__ xyz, const float* __restrict__ new_xyz, const int* __restrict__ idx,
                                                  const unsigned char* __restrict__ empty, const float* __restrict__ coef,
-                                                 float* __restrict__ out, unsigned char* __restrict__ arg) {
+                                                 typename R::elem* __restrict__ out, unsigned char* __restrict__ arg) {
   extern __shared__ float4 vp_ent[];   // [qpw][s + 1]
   const int tid = threadIdx.x, L = c >> 2, ld = s + 1;
   const int64_t q0 = static_cast<int64_t>(blockIdx.x) * qpw;
@@ -171,14 +202,14 @@ __global__ __launch_bounds__(256) void vp_pool_k(int64_t m, int s, int c, int64_
 #pragma unroll
   for (int k = 0; k < 4; ++k) { best[k] = -INFINITY; bj[k] = 0; }
   const float4* ent = vp_ent + q * ld;
-  const float* fl = f + 4 * l;
+  const typename R::elem* fl = f + 4 * l;
   for (int j0 = 0; j0 < s; j0 += 4) {
     float4 e[4], g[4];
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       e[u] = ent[j0 + u < s ? j0 + u : s - 1];
       const int row = __float_as_int(e[u].w);
-      g[u] = row >= 0 ? *reinterpret_cast<const float4*>(fl + static_cast<int64_t>(row) * c) : make_float4(0.f, 0.f, 0.f, 0.f);
+      g[u] = row >= 0 ? vp_load4<R>(fl + static_cast<int64_t>(row) * c) : make_float4(0.f, 0.f, 0.f, 0.f);
     }
 #pragma unroll
     for (int u = 0; u < 4; ++u)
@@ -190,18 +221,20 @@ __global__ __launch_bounds__(256) void vp_pool_k(int64_t m, int s, int c, int64_
       }
   }
   const int64_t o = (q0 + q) * c + 4 * l;
-  *reinterpret_cast<float4*>(out + o) = make_float4(best[0], best[1], best[2], best[3]);
+  vp_store4<R>(out + o, make_float4(best[0], best[1], best[2], best[3]));
   if (arg) *reinterpret_cast<uchar4*>(arg + o) = make_uchar4(static_cast<unsigned char>(bj[0]), static_cast<unsigned char>(bj[1]),
                                                              static_cast<unsigned char>(bj[2]), static_cast<unsigned char>(bj[3]));
 }
 
 // ---- 4. route: block b takes queries [b * kVpBlock, ...), c / 4 lanes per query in passes of 256 / (c / 4) queries.  Per
-// (query, channel): g = grad_out * [out > 0], the destination element idx[i][arg] * c + channel of grad_F (-1: masked, empty query,
+// (query, channel): g = grad_out * [out > 0] (out as stored, widened; g staged in the rows' format: exact), the destination element idx[i][arg] * c + channel of grad_F (-1: masked, empty query,
 // row out of range), and the lane's fp64 sums of g and g * d[i][arg] in pass order; the block's lanes are then folded in lane order
 // into part[b][c][4]. ---------------------------------------------------------------------------------------------------------------
+template <class R>
 __global__ __launch_bounds__(256) void vp_route_k(int64_t m, int s, int c, int64_t n, const float* __restrict__ xyz, const float* __restrict__ new_xyz,
-                                                  const int* __restrict__ idx, const unsigned char* __restrict__ empty, const float* __restrict__ out,
-                                                  const unsigned char* __restrict__ arg, const float* __restrict__ gy, float* __restrict__ gbuf,
+                                                  const int* __restrict__ idx, const unsigned char* __restrict__ empty,
+                                                  const typename R::elem* __restrict__ out, const unsigned char* __restrict__ arg,
+                                                  const typename R::elem* __restrict__ gy, typename R::elem* __restrict__ gbuf,
                                                   int* __restrict__ dst, double* __restrict__ part) {
   __shared__ double red[256][17];
   const int tid = threadIdx.x, L = c >> 2, qpp = 256 / L;
@@ -215,7 +248,7 @@ __global__ __launch_bounds__(256) void vp_route_k(int64_t m, int s, int c, int64
       const int64_t i = base + qq;
       if (i >= m) break;
       const int64_t o = i * c + 4 * l;
-      const float4 ov = *reinterpret_cast<const float4*>(out + o), gv = *reinterpret_cast<const float4*>(gy + o);
+      const float4 ov = vp_load4<R>(out + o), gv = vp_load4<R>(gy + o);
       const uchar4 av = *reinterpret_cast<const uchar4*>(arg + o);
       const float oo[4] = {ov.x, ov.y, ov.z, ov.w}, gg[4] = {gv.x, gv.y, gv.z, gv.w};
       const int aa[4] = {av.x, av.y, av.z, av.w};
@@ -239,7 +272,7 @@ __global__ __launch_bounds__(256) void vp_route_k(int64_t m, int s, int c, int64
         }
       }
       if (gbuf) {
-        *reinterpret_cast<float4*>(gbuf + o) = make_float4(g[0], g[1], g[2], g[3]);
+        vp_store4<R>(gbuf + o, make_float4(g[0], g[1], g[2], g[3]));
         *reinterpret_cast<int4*>(dst + o) = make_int4(d[0], d[1], d[2], d[3]);
       }
     }
@@ -312,15 +345,88 @@ template <class Cv> static VpFwdWs vp_fwd_ws(Cv& cv, int64_t m, int c) {
   w.coef = cv.template take<float>(static_cast<size_t>(c) * 4);
   return w;
 }
-struct VpBwdWs { double* part; float* g; int* dst; void* sws; size_t sws_bytes; };
-template <class Cv> static VpBwdWs vp_bwd_ws(Cv& cv, int64_t m, int c) {
-  VpBwdWs w;
+// backward workspace.  fp32: part, g, dst, the scatter-add's own.  16-bit: g (2 bytes per cell) comes LAST and the size is the
+// unpadded end of it, so that the query is 2 m c bytes below the fp32 one at least, whatever the 256-byte padding of the regions does.
+template <class R> struct VpBwdWs { double* part; typename R::elem* g; int* dst; void* sws; size_t sws_bytes; size_t bytes; };
+template <class R, class Cv> static VpBwdWs<R> vp_bwd_ws(Cv& cv, int64_t m, int c) {
+  constexpr bool k16 = sizeof(typename R::elem) == 2;
+  VpBwdWs<R> w;
   w.part = cv.template take<double>(static_cast<size_t>(vp_blocks(m)) * c * 4);
-  w.g = cv.template take<float>(static_cast<size_t>(m) * c);
+  if constexpr (!k16) w.g = cv.template take<typename R::elem>(static_cast<size_t>(m) * c);
   w.dst = cv.template take<int>(static_cast<size_t>(m) * c);
   w.sws_bytes = fv2p_scatter_add_ws_bytes(m * c, 1);
   w.sws = cv.template take<char>(w.sws_bytes);
+  if constexpr (k16) w.g = cv.template take<typename R::elem>(static_cast<size_t>(m) * c);
+  w.bytes = k16 ? cv.off : align_up(cv.off);
   return w;
+}
+
+// what a lane's access of 4 channels needs of the row pointers: 16 bytes (fp32 rows) or 8 (16-bit rows)
+template <class R> constexpr uintptr_t kVpAlign = 4 * sizeof(typename R::elem);
+template <class R> static bool vp_aligned(const void* a, const void* b, const unsigned char* arg) {
+  return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & (kVpAlign<R> - 1)) == 0 && (reinterpret_cast<uintptr_t>(arg) & 3) == 0;
+}
+
+template <class R>
+static int vp_forward(const char* who, const typename R::elem* f, const float* xyz, const float* new_xyz, const int* idx, const unsigned char* empty,
+                      int64_t n, int64_t m, int s, int c, const float* w, const float* gamma, const float* beta, float* running_mean,
+                      float* running_var, int64_t* num_batches_tracked, float momentum, float eps, int training, typename R::elem* out,
+                      unsigned char* arg, double* saved, void* ws, size_t ws_bytes, fv2p_stream_t stream) {
+  FV2P_REQUIRE(vp_ok(m, s, c), FV2P_ELIMIT, "%s: m %lld, s %d, c %d outside fv2p_voxel_pool_supported", who, static_cast<long long>(m), s, c);
+  FV2P_REQUIRE(n >= 1 && n < (1ll << 31), FV2P_EINVAL, "%s: n %lld rows", who, static_cast<long long>(n));
+  FV2P_REQUIRE(f && xyz && new_xyz && idx && empty && w && gamma && beta && out && saved && ws, FV2P_EINVAL, "%s: null pointer", who);
+  FV2P_REQUIRE(training || (running_mean && running_var), FV2P_EINVAL, "%s: eval mode needs the running statistics", who);
+  FV2P_REQUIRE(!training || m * s >= 2, FV2P_EINVAL, "%s: batch statistics of a single position", who);
+  FV2P_REQUIRE(vp_aligned<R>(f, out, arg), FV2P_EINVAL, "%s: F and out must be %d-byte aligned, arg 4-byte aligned", who, static_cast<int>(kVpAlign<R>));
+  FV2P_REQUIRE(ws_bytes >= fv2p_voxel_pool_ws_bytes(m, s, c), FV2P_EWORKSPACE, "%s: workspace too small", who);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  Carver cv(ws, ws_bytes);
+  const VpFwdWs wk = vp_fwd_ws(cv, m, c);
+  const int64_t blocks = vp_blocks(m);
+  if (training)
+    hipLaunchKernelGGL(vp_moments_k, dim3(static_cast<unsigned>(blocks)), dim3(256), 0, st, m, s, n, xyz, new_xyz, idx, empty, wk.part);
+  hipLaunchKernelGGL(vp_fold_fwd_k, dim3(1), dim3(256), 0, st, blocks, c, static_cast<long long>(m * s), training ? 1 : 0, wk.part, w, gamma, beta,
+                     running_mean, running_var, reinterpret_cast<long long*>(num_batches_tracked), momentum, eps, saved, wk.coef);
+  const int qpw = vp_qpw(s, c);
+  const size_t lds = static_cast<size_t>(qpw) * (s + 1) * sizeof(float4);
+  hipLaunchKernelGGL((vp_pool_k<R>), dim3(static_cast<unsigned>(ceil_div(m, qpw))), dim3(256), lds, st, m, s, c, n, qpw, f, xyz, new_xyz, idx, empty,
+                     wk.coef, out, arg);
+  FV2P_LAUNCH_CHECK();
+  return 0;
+}
+
+template <class R>
+static int vp_backward(const char* who, const float* xyz, const float* new_xyz, const int* idx, const unsigned char* empty, int64_t n, int64_t m,
+                       int s, int c, const float* w, const float* gamma, const typename R::elem* out, const unsigned char* arg,
+                       const double* saved, const typename R::elem* grad_out, int training, typename R::elem* grad_f, float* grad_w,
+                       float* grad_gamma, float* grad_beta, void* ws, size_t ws_bytes, fv2p_stream_t stream) {
+  FV2P_REQUIRE(vp_ok(m, s, c), FV2P_ELIMIT, "%s: m %lld, s %d, c %d outside fv2p_voxel_pool_supported", who, static_cast<long long>(m), s, c);
+  FV2P_REQUIRE(vp_bwd_ok(m, s, c, n), FV2P_ELIMIT, "%s: m * c or n * c reaches 2^31 (n %lld)", who, static_cast<long long>(n));
+  FV2P_REQUIRE(xyz && new_xyz && idx && empty && w && gamma && out && arg && saved && grad_out && ws, FV2P_EINVAL, "%s: null pointer", who);
+  FV2P_REQUIRE(vp_aligned<R>(out, grad_out, arg), FV2P_EINVAL, "%s: out and grad_out must be %d-byte aligned, arg 4-byte aligned", who,
+               static_cast<int>(kVpAlign<R>));
+  Sizer sz;
+  FV2P_REQUIRE(ws_bytes >= vp_bwd_ws<R>(sz, m, c).bytes, FV2P_EWORKSPACE, "%s: workspace too small", who);
+  if (!grad_f && !grad_w && !grad_gamma && !grad_beta) return 0;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  Carver cv(ws, ws_bytes);
+  const VpBwdWs<R> wk = vp_bwd_ws<R>(cv, m, c);
+  const int64_t blocks = vp_blocks(m);
+  hipLaunchKernelGGL((vp_route_k<R>), dim3(static_cast<unsigned>(blocks)), dim3(256), 0, st, m, s, c, n, xyz, new_xyz, idx, empty, out, arg, grad_out,
+                     grad_f ? wk.g : nullptr, wk.dst, wk.part);
+  if (grad_w || grad_gamma || grad_beta)
+    hipLaunchKernelGGL(vp_fold_bwd_k, dim3(1), dim3(256), 0, st, blocks, c, static_cast<long long>(m * s), training ? 1 : 0, wk.part, w, gamma, saved,
+                       grad_w, grad_gamma, grad_beta);
+  FV2P_LAUNCH_CHECK();
+  if (!grad_f) return 0;
+  if constexpr (sizeof(typename R::elem) == 4) {
+    FV2P_HIP(hipMemsetAsync(grad_f, 0, static_cast<size_t>(n) * c * sizeof(float), st));
+    return fv2p_scatter_add(m * c, 1, n * c, wk.dst, nullptr, nullptr, wk.g, 1, grad_f, wk.sws, wk.sws_bytes, stream);
+  } else {   // zero-fills grad_f itself; every element's fp32 total is rounded once.  The format's code follows from R.
+    constexpr int dtype = std::is_same_v<R, Fmt16<H16>> ? FV2P_DT_F16 : FV2P_DT_BF16;
+    static_assert(std::is_same_v<R, Fmt16<H16>> || std::is_same_v<R, Fmt16<B16>>, "a 16-bit row format");
+    return scatter_add_h(m * c, 1, n * c, wk.dst, nullptr, nullptr, wk.g, 1, grad_f, dtype, wk.sws, wk.sws_bytes, st);
+  }
 }
 
 }  // namespace fv2p
@@ -342,8 +448,13 @@ extern "C" size_t fv2p_voxel_pool_ws_bytes(int64_t m, int s, int c) {
 extern "C" size_t fv2p_voxel_pool_backward_ws_bytes(int64_t m, int s, int c, int64_t n) {
   if (!vp_bwd_ok(m, s, c, n)) return 0;
   Sizer sz;
-  vp_bwd_ws(sz, m, c);
-  return sz.bytes();
+  return vp_bwd_ws<F32>(sz, m, c).bytes;
+}
+
+extern "C" size_t fv2p_voxel_pool_backward_h_ws_bytes(int64_t m, int s, int c, int64_t n) {   // the same for both 16-bit formats
+  if (!vp_bwd_ok(m, s, c, n)) return 0;
+  Sizer sz;
+  return vp_bwd_ws<Fmt16<H16>>(sz, m, c).bytes;
 }
 
 extern "C" int fv2p_voxel_pool_forward(const float* f, const float* xyz, const float* new_xyz, const int* idx, const unsigned char* empty,
@@ -351,29 +462,23 @@ extern "C" int fv2p_voxel_pool_forward(const float* f, const float* xyz, const f
                                        float* running_mean, float* running_var, int64_t* num_batches_tracked, float momentum, float eps,
                                        int training, float* out, unsigned char* arg, double* saved, void* ws, size_t ws_bytes,
                                        fv2p_stream_t stream) {
-  FV2P_REQUIRE(vp_ok(m, s, c), FV2P_ELIMIT, "fv2p_voxel_pool_forward: m %lld, s %d, c %d outside fv2p_voxel_pool_supported",
-               static_cast<long long>(m), s, c);
-  FV2P_REQUIRE(n >= 1 && n < (1ll << 31), FV2P_EINVAL, "fv2p_voxel_pool_forward: n %lld rows", static_cast<long long>(n));
-  FV2P_REQUIRE(f && xyz && new_xyz && idx && empty && w && gamma && beta && out && saved && ws, FV2P_EINVAL, "fv2p_voxel_pool_forward: null pointer");
-  FV2P_REQUIRE(training || (running_mean && running_var), FV2P_EINVAL, "fv2p_voxel_pool_forward: eval mode needs the running statistics");
-  FV2P_REQUIRE(!training || m * s >= 2, FV2P_EINVAL, "fv2p_voxel_pool_forward: batch statistics of a single position");
-  FV2P_REQUIRE(((reinterpret_cast<uintptr_t>(f) | reinterpret_cast<uintptr_t>(out)) & 15) == 0 && (reinterpret_cast<uintptr_t>(arg) & 3) == 0,
-               FV2P_EINVAL, "fv2p_voxel_pool_forward: F and out must be 16-byte aligned, arg 4-byte aligned");
-  FV2P_REQUIRE(ws_bytes >= fv2p_voxel_pool_ws_bytes(m, s, c), FV2P_EWORKSPACE, "fv2p_voxel_pool_forward: workspace too small");
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  Carver cv(ws, ws_bytes);
-  const VpFwdWs wk = vp_fwd_ws(cv, m, c);
-  const int64_t blocks = vp_blocks(m);
-  if (training)
-    hipLaunchKernelGGL(vp_moments_k, dim3(static_cast<unsigned>(blocks)), dim3(256), 0, st, m, s, n, xyz, new_xyz, idx, empty, wk.part);
-  hipLaunchKernelGGL(vp_fold_fwd_k, dim3(1), dim3(256), 0, st, blocks, c, static_cast<long long>(m * s), training ? 1 : 0, wk.part, w, gamma, beta,
-                     running_mean, running_var, reinterpret_cast<long long*>(num_batches_tracked), momentum, eps, saved, wk.coef);
-  const int qpw = vp_qpw(s, c);
-  const size_t lds = static_cast<size_t>(qpw) * (s + 1) * sizeof(float4);
-  hipLaunchKernelGGL(vp_pool_k, dim3(static_cast<unsigned>(ceil_div(m, qpw))), dim3(256), lds, st, m, s, c, n, qpw, f, xyz, new_xyz, idx, empty,
-                     wk.coef, out, arg);
-  FV2P_LAUNCH_CHECK();
-  return 0;
+  return vp_forward<F32>("fv2p_voxel_pool_forward", f, xyz, new_xyz, idx, empty, n, m, s, c, w, gamma, beta, running_mean, running_var,
+                         num_batches_tracked, momentum, eps, training, out, arg, saved, ws, ws_bytes, stream);
+}
+
+extern "C" int fv2p_voxel_pool_forward_h(const void* f, const float* xyz, const float* new_xyz, const int* idx, const unsigned char* empty,
+                                         int64_t n, int64_t m, int s, int c, const float* w, const float* gamma, const float* beta,
+                                         float* running_mean, float* running_var, int64_t* num_batches_tracked, float momentum, float eps,
+                                         int training, void* out, unsigned char* arg, double* saved, void* ws, size_t ws_bytes, int dtype,
+                                         fv2p_stream_t stream) {
+  FV2P_DT16_OK("fv2p_voxel_pool_forward_h", dtype);
+  if (dtype == FV2P_DT_F16)
+    return vp_forward<Fmt16<H16>>("fv2p_voxel_pool_forward_h", static_cast<const u16*>(f), xyz, new_xyz, idx, empty, n, m, s, c, w, gamma, beta,
+                                  running_mean, running_var, num_batches_tracked, momentum, eps, training, static_cast<u16*>(out), arg, saved,
+                                  ws, ws_bytes, stream);
+  return vp_forward<Fmt16<B16>>("fv2p_voxel_pool_forward_h", static_cast<const u16*>(f), xyz, new_xyz, idx, empty, n, m, s, c, w, gamma, beta,
+                                running_mean, running_var, num_batches_tracked, momentum, eps, training, static_cast<u16*>(out), arg, saved, ws,
+                                ws_bytes, stream);
 }
 
 extern "C" int fv2p_voxel_pool_backward(const float* xyz, const float* new_xyz, const int* idx, const unsigned char* empty, int64_t n,
@@ -381,28 +486,21 @@ extern "C" int fv2p_voxel_pool_backward(const float* xyz, const float* new_xyz, 
                                         const unsigned char* arg, const double* saved, const float* grad_out, int training, float* grad_f,
                                         float* grad_w, float* grad_gamma, float* grad_beta, void* ws, size_t ws_bytes,
                                         fv2p_stream_t stream) {
-  FV2P_REQUIRE(vp_ok(m, s, c), FV2P_ELIMIT, "fv2p_voxel_pool_backward: m %lld, s %d, c %d outside fv2p_voxel_pool_supported",
-               static_cast<long long>(m), s, c);
-  FV2P_REQUIRE(vp_bwd_ok(m, s, c, n), FV2P_ELIMIT, "fv2p_voxel_pool_backward: m * c or n * c reaches 2^31 (n %lld)", static_cast<long long>(n));
-  FV2P_REQUIRE(xyz && new_xyz && idx && empty && w && gamma && out && arg && saved && grad_out && ws, FV2P_EINVAL,
-               "fv2p_voxel_pool_backward: null pointer");
-  FV2P_REQUIRE(((reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(grad_out)) & 15) == 0 && (reinterpret_cast<uintptr_t>(arg) & 3) == 0,
-               FV2P_EINVAL, "fv2p_voxel_pool_backward: out and grad_out must be 16-byte aligned, arg 4-byte aligned");
-  FV2P_REQUIRE(ws_bytes >= fv2p_voxel_pool_backward_ws_bytes(m, s, c, n), FV2P_EWORKSPACE, "fv2p_voxel_pool_backward: workspace too small");
-  if (!grad_f && !grad_w && !grad_gamma && !grad_beta) return 0;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  Carver cv(ws, ws_bytes);
-  const VpBwdWs wk = vp_bwd_ws(cv, m, c);
-  const int64_t blocks = vp_blocks(m);
-  hipLaunchKernelGGL(vp_route_k, dim3(static_cast<unsigned>(blocks)), dim3(256), 0, st, m, s, c, n, xyz, new_xyz, idx, empty, out, arg, grad_out,
-                     grad_f ? wk.g : nullptr, wk.dst, wk.part);
-  if (grad_w || grad_gamma || grad_beta)
-    hipLaunchKernelGGL(vp_fold_bwd_k, dim3(1), dim3(256), 0, st, blocks, c, static_cast<long long>(m * s), training ? 1 : 0, wk.part, w, gamma, saved,
-                       grad_w, grad_gamma, grad_beta);
-  FV2P_LAUNCH_CHECK();
-  if (grad_f) {
-    FV2P_HIP(hipMemsetAsync(grad_f, 0, static_cast<size_t>(n) * c * sizeof(float), st));
-    return fv2p_scatter_add(m * c, 1, n * c, wk.dst, nullptr, nullptr, wk.g, 1, grad_f, wk.sws, wk.sws_bytes, stream);
-  }
-  return 0;
+  return vp_backward<F32>("fv2p_voxel_pool_backward", xyz, new_xyz, idx, empty, n, m, s, c, w, gamma, out, arg, saved, grad_out, training, grad_f,
+                          grad_w, grad_gamma, grad_beta, ws, ws_bytes, stream);
+}
+
+extern "C" int fv2p_voxel_pool_backward_h(const float* xyz, const float* new_xyz, const int* idx, const unsigned char* empty, int64_t n,
+                                          int64_t m, int s, int c, const float* w, const float* gamma, const void* out,
+                                          const unsigned char* arg, const double* saved, const void* grad_out, int training, void* grad_f,
+                                          float* grad_w, float* grad_gamma, float* grad_beta, void* ws, size_t ws_bytes, int dtype,
+                                          fv2p_stream_t stream) {
+  FV2P_DT16_OK("fv2p_voxel_pool_backward_h", dtype);
+  if (dtype == FV2P_DT_F16)
+    return vp_backward<Fmt16<H16>>("fv2p_voxel_pool_backward_h", xyz, new_xyz, idx, empty, n, m, s, c, w, gamma, static_cast<const u16*>(out), arg,
+                                   saved, static_cast<const u16*>(grad_out), training, static_cast<u16*>(grad_f), grad_w, grad_gamma, grad_beta,
+                                   ws, ws_bytes, stream);
+  return vp_backward<Fmt16<B16>>("fv2p_voxel_pool_backward_h", xyz, new_xyz, idx, empty, n, m, s, c, w, gamma, static_cast<const u16*>(out), arg,
+                                 saved, static_cast<const u16*>(grad_out), training, static_cast<u16*>(grad_f), grad_w, grad_gamma, grad_beta,
+                                 ws, ws_bytes, stream);
 }

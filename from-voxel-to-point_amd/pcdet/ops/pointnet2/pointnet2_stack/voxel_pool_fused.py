@@ -6,7 +6,9 @@ mlps_out with pool_method 'max_pool', without the grouped (M, C, S) and (M, 3, S
 F (N, C) the mlps_in rows, idx (M, S) int32 GLOBAL rows of the voxel query, empty (M) bool (an empty query pools relu(bn(0))),
 conv the Conv2d(3, C, 1, bias=False) and bn the BatchNorm2d of mlps_pos.  The BatchNorm runs in the module's own mode: batch
 statistics over the M * S positions (running statistics and num_batches_tracked move as torch moves them) or the running ones.
-Gradients for F, conv.weight, bn.weight and bn.bias; one byte per (query, channel) is kept for them.  float32 on the GPU only:
+Gradients for F, conv.weight, bn.weight and bn.bias; one byte per (query, channel) is kept for them.  On the GPU only, for float32
+rows outside autocast and for the float16 / bfloat16 rows that mlps_in hands over under a torch.autocast of that dtype (the *_h
+entry points: out, grad_out and grad_F in the rows' dtype, coordinates, parameters and their gradients float32 as always):
 `supported()` says whether the op takes a call, and the module runs its torch route when it does not."""
 import torch
 import torch.nn as nn
@@ -35,9 +37,16 @@ def _modules_ok(conv, bn):
 
 def supported(features, idx, conv, bn, xyz=None, new_xyz=None, m=None, s=None):
     """Whether voxel_pool_max takes this call.  idx may be None when the query has not run yet: then m and s give its shape."""
-    if not (torch.is_tensor(features) and features.is_cuda and features.dtype == torch.float32 and features.dim() == 2):
+    if not (torch.is_tensor(features) and features.is_cuda and features.dim() == 2):
         return False
-    if torch.is_autocast_enabled() or not _modules_ok(conv, bn):
+    # float32 rows outside autocast; 16-bit rows only under an autocast of their own dtype - the one situation in which the torch route
+    # returns rows of that dtype too (outside autocast it promotes them to the float32 of the parameters)
+    if torch.is_autocast_enabled():
+        if features.dtype not in G.DT16 or torch.get_autocast_dtype("cuda") != features.dtype:
+            return False
+    elif features.dtype != torch.float32:
+        return False
+    if not _modules_ok(conv, bn):
         return False
     if idx is not None:
         if not (idx.is_cuda and idx.dtype == torch.int32 and idx.dim() == 2):
@@ -59,7 +68,8 @@ def supported(features, idx, conv, bn, xyz=None, new_xyz=None, m=None, s=None):
     if c != conv.out_channels or n < 1 or (bn.training and m * s < 2):
         return False
     lib = _nat.lib()
-    return bool(lib.fv2p_voxel_pool_supported(m, s, c)) and lib.fv2p_voxel_pool_backward_ws_bytes(m, s, c, n) > 0
+    ws_bytes = lib.fv2p_voxel_pool_backward_h_ws_bytes if features.dtype in G.DT16 else lib.fv2p_voxel_pool_backward_ws_bytes
+    return bool(lib.fv2p_voxel_pool_supported(m, s, c)) and ws_bytes(m, s, c, n) > 0
 
 
 def _fwd(saved, f, xyz, new_xyz, idx, empty, w, gamma, beta, bn, needs):
@@ -67,14 +77,16 @@ def _fwd(saved, f, xyz, new_xyz, idx, empty, w, gamma, beta, bn, needs):
     m, s = idx.shape
     f, xyz, new_xyz, idx, w = f.contiguous(), xyz.contiguous(), new_xyz.contiguous(), idx.contiguous(), w.contiguous().view(c, 3)
     empty = empty.contiguous().view(torch.uint8) if empty.dtype == torch.bool else empty.contiguous()
-    out = G.new(f, (m, c))
+    dt = G.DT16[f.dtype] if G.rows_16bit("voxel_pool_max", f) else None
+    out = G.new(f, (m, c), f.dtype)
     arg = G.new(f, (m, c), torch.uint8) if any(needs) else None     # the winning sample: all that backward needs beside `keep`
     keep = G.new(f, (_nat.lib().fv2p_voxel_pool_saved_bytes(c) // 8,), torch.float64)
     ws = G.scratch("fv2p_voxel_pool_ws_bytes", f.device, m, s, c)
     training = bool(bn.training)
     momentum = -1.0 if bn.momentum is None else float(bn.momentum)
-    G.run("fv2p_voxel_pool_forward", f, xyz, new_xyz, idx, empty, n, m, s, c, w, gamma, beta, bn.running_mean, bn.running_var,
-          bn.num_batches_tracked, momentum, float(bn.eps), int(training), out, arg, keep, ws, ws.numel())
+    G.run("fv2p_voxel_pool_forward_h" if dt else "fv2p_voxel_pool_forward", f, xyz, new_xyz, idx, empty, n, m, s, c, w, gamma, beta,
+          bn.running_mean, bn.running_var, bn.num_batches_tracked, momentum, float(bn.eps), int(training), out, arg, keep, ws, ws.numel(),
+          *((dt,) if dt else ()))
     saved.update(t=(xyz, new_xyz, idx, empty, w, gamma, out, arg, keep), dims=(n, m, s, c), training=training, needs=needs)
     return out
 
@@ -85,13 +97,14 @@ def _bwd(saved, grad):
         raise RuntimeError("voxel_pool_max: backward of a forward pass that ran without gradients enabled")
     n, m, s, c = saved["dims"]
     need_f, need_w, need_g, need_b = saved["needs"]
-    g_f = G.new(grad, (n, c)) if need_f else None
+    dt = G.pair_16bit("voxel_pool_max: out and grad_out", out, grad)     # nothing is cast: grad_out has the rows' dtype
+    g_f = G.new(grad, (n, c), out.dtype) if need_f else None
     g_w = G.new(grad, (c, 3)) if need_w else None
     g_g = G.new(grad, (c,)) if need_g else None
     g_b = G.new(grad, (c,)) if need_b else None
-    ws = G.scratch("fv2p_voxel_pool_backward_ws_bytes", grad.device, m, s, c, n)
-    G.run("fv2p_voxel_pool_backward", xyz, new_xyz, idx, empty, n, m, s, c, w, gamma, out, arg, keep, grad.contiguous(), int(saved["training"]),
-          g_f, g_w, g_g, g_b, ws, ws.numel())
+    ws = G.scratch("fv2p_voxel_pool_backward_h_ws_bytes" if dt else "fv2p_voxel_pool_backward_ws_bytes", grad.device, m, s, c, n)
+    G.run("fv2p_voxel_pool_backward_h" if dt else "fv2p_voxel_pool_backward", xyz, new_xyz, idx, empty, n, m, s, c, w, gamma, out, arg, keep,
+          grad.contiguous(), int(saved["training"]), g_f, g_w, g_g, g_b, ws, ws.numel(), *((dt,) if dt else ()))
     return g_f, None, None, None, None, (g_w.view(c, 3, 1, 1) if need_w else None), g_g, g_b
 
 

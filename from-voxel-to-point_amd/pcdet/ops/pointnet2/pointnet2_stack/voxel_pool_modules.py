@@ -10,8 +10,8 @@ from . import voxel_pool_fused, voxel_query_utils
 
 
 class NeighborVoxelSAModuleMSG(nn.Module):
-    # max_pool groupers on float32 GPU rows run as one fused op (voxel_pool_fused: no grouped (M, C, S) tensor); False keeps every
-    # call on the torch composition below
+    # max_pool groupers on float32 GPU rows, and on the float16 / bfloat16 rows of a torch.autocast region, run as one fused op
+    # (voxel_pool_fused: no grouped (M, C, S) tensor); False keeps every call on the torch composition below
     FUSED = True
 
     def __init__(self, *, query_ranges: List[List[int]], radii: List[float], nsamples: List[int], mlps: List[List[int]],
@@ -44,7 +44,8 @@ class NeighborVoxelSAModuleMSG(nn.Module):
 
     def _fused_pool(self, k, new_coords, xyz, xyz_batch_cnt, new_xyz, new_xyz_batch_cnt, f_in, voxel2point_indices):
         """Grouper k between mlps_in and mlps_out as one voxel_pool_max call -> (M, C), or None: the torch route below runs
-        (FUSED off, avg_pool, host or 16-bit tensors, autocast, a shape or a module the op does not take)."""
+        (FUSED off, avg_pool, host tensors, 16-bit rows outside an autocast of their dtype, 16-bit parameters, a shape or a module
+        the op does not take)."""
         if not self.FUSED or self.pool_method != 'max_pool':
             return None
         grouper, pos = self.groupers[k], self.mlps_pos[k]

@@ -1279,7 +1279,7 @@ int fv2p_linear_bn_backward_h(const void* x, const void* z, const void* dy, int6
                               void* ws, size_t ws_bytes, fv2p_stream_t stream);
 
 /* ---- Voxel R-CNN RoI-grid pooling: NeighborVoxelSAModuleMSG between mlps_in and mlps_out as one op ----------------------------
- * What a grouper of the module does after its voxel query with pool_method 'max_pool' (csrc/voxel_pool.hip), fp32 only, without a
+ * What a grouper of the module does after its voxel query with pool_method 'max_pool' (csrc/voxel_pool.hip), on fp32 rows (16-bit rows: the *_h forms below), without a
  * tensor proportional to m * c * s.  f [n][c] the mlps_in rows, xyz [n][3], new_xyz [m][3], idx [m][s] GLOBAL rows of the voxel
  * query (int32), empty [m] one byte per query (non-zero: the query found nothing), w [c][3] the Conv2d(3, c, 1, bias=False)
  * weight, gamma / beta / running_mean / running_var [c] and num_batches_tracked of its BatchNorm2d.  With
@@ -1319,6 +1319,30 @@ int fv2p_voxel_pool_backward(const float* xyz, const float* new_xyz, const int* 
                              const unsigned char* arg, const double* saved, const float* grad_out, int training, float* grad_f,
                              float* grad_w, float* grad_gamma, float* grad_beta, void* ws, size_t ws_bytes,
                              fv2p_stream_t stream);
+
+/* The same op on float16 / bfloat16 rows, what torch.autocast hands the module (`dtype`: FV2P_DT_F16 / FV2P_DT_BF16, the format T of
+ * f, out, grad_out and grad_f; any other value returns FV2P_EINVAL).  Everything that comes from coordinates and parameters stays
+ * fp32 / fp64 as above: xyz, new_xyz, w, gamma, beta, the running statistics, the nine moment sums, the coefficients, saved, grad_w,
+ * grad_gamma, grad_beta.  The kernels are the fp32 ones instantiated for T:
+ *     out[i][ch] = round_T(max_j relu(widen(f[idx[i][j]][ch]) + BN(w d[i][j])[ch]))
+ * with the sum, the ReLU, the maximum and arg taken in fp32 and ONE rounding to nearest even at the store.  backward: a cell is live
+ * when the stored out, widened, is > 0; g = grad_out there and 0 elsewhere is staged in T (exact); the fp64 sums run in the order of the
+ * fp32 op; grad_f [n][c] is WRITTEN by the 16-bit form of fv2p_scatter_add (its fp32 association, every element rounded once).  No
+ * float atomics and no fp32 buffer of m * c or n * c elements in either direction.  The limits, fv2p_voxel_pool_supported, _blocks,
+ * _saved_bytes and the forward workspace (_ws_bytes) are those of the fp32 op; fv2p_voxel_pool_backward_h_ws_bytes (g in T, the int32
+ * destinations, the scatter-add's own workspace) is at least 2 m c bytes below fv2p_voxel_pool_backward_ws_bytes, 0 where that is 0
+ * and never decreasing in m.  f, out and grad_out must be 8-byte aligned (a lane moves 4 channels of 2 bytes per access). */
+size_t fv2p_voxel_pool_backward_h_ws_bytes(int64_t m, int s, int c, int64_t n);
+int fv2p_voxel_pool_forward_h(const void* f, const float* xyz, const float* new_xyz, const int* idx, const unsigned char* empty,
+                              int64_t n, int64_t m, int s, int c, const float* w, const float* gamma, const float* beta,
+                              float* running_mean, float* running_var, int64_t* num_batches_tracked, float momentum, float eps,
+                              int training, void* out, unsigned char* arg, double* saved, void* ws, size_t ws_bytes, int dtype,
+                              fv2p_stream_t stream);
+int fv2p_voxel_pool_backward_h(const float* xyz, const float* new_xyz, const int* idx, const unsigned char* empty, int64_t n,
+                               int64_t m, int s, int c, const float* w, const float* gamma, const void* out,
+                               const unsigned char* arg, const double* saved, const void* grad_out, int training, void* grad_f,
+                               float* grad_w, float* grad_gamma, float* grad_beta, void* ws, size_t ws_bytes, int dtype,
+                               fv2p_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Per-kernel timings on one GPU (events on the launch stream). Not part of the product or of bench.py; used to
-iterate on kernel variants:  python tools/microbench.py [conv|conv16|amp16|bn16|bn2d|bn2d16|linbn|linbn16|voxelpool|bev16|beventry|exit16|batch16|sa16|dcn|dcn16|dcn16bwd|fps|voxel|nms|all]"""
+iterate on kernel variants:  python tools/microbench.py [conv|conv16|amp16|bn16|bn2d|bn2d16|linbn|linbn16|voxelpool|voxelpool16|bev16|beventry|exit16|batch16|sa16|dcn|dcn16|dcn16bwd|fps|voxel|nms|all]"""
 import os
 import sys
 import time
@@ -1216,6 +1216,110 @@ def voxelpool(out_path=None):
     _write(lines, out_path)
 
 
+def voxelpool16(out_path=None):
+    """The four groupers of `voxelpool` under torch.autocast, float16 and bfloat16: the whole one-grouper module with FUSED on (the 16-bit
+    instances of csrc/voxel_pool.hip) against FUSED off (the grouped torch composition under the same autocast) and against the fp32
+    fused op outside autocast, forward and forward + backward, on copies of the same weights.  Then the op alone through the C entry
+    points, 16-bit against fp32.  The method of `voxelpool`: the median of ROUNDS windows of REPS calls, the routes taken alternately
+    in one process, +- half the range of the windows."""
+    import copy
+    import fv2p_native as nat
+    from pcdet.ops.pointnet2.pointnet2_stack.voxel_pool_modules import NeighborVoxelSAModuleMSG
+    dev = torch.device("cuda:0")
+    ROUNDS, REPS, S, C, CIN = 7, 10, 16, 32, 64
+    spread = lambda x: (max(x) - min(x)) / 2
+    ahead = lambda a, b: "yes" if np.median(b) - np.median(a) > max(spread(a), spread(b)) else "no"
+    lines = ["Voxel R-CNN RoI-grid pooling under torch.autocast (car config, batch 2), one grouper per row, us per module call: median of %d windows of %d calls, "
+             "+- half the range" % (ROUNDS, REPS),
+             "fused16: FUSED on under autocast (16-bit rows into the op) | grouped16: FUSED off under the same autocast | fused32: FUSED on, float32, no autocast",
+             "ahead: the first route's forward + backward median is below the second's by more than the larger spread",
+             "%-9s %-11s | %-15s %-15s %-15s | %-15s %-15s %-15s | %-18s %s" % ("dtype", "grouper", "fwd fused16", "fwd grouped16", "fwd fused32", "f+b fused16",
+                                                                             "f+b grouped16", "f+b fused32", "fused16<grouped16", "fused16<fused32")]
+    scenes, ops = {}, []
+    for name, stride, qrange, radius in VOXELPOOL_GROUPERS:
+        if stride not in scenes:
+            scenes[stride] = {k: v.to(dev) for k, v in _voxelpool_scene(stride).items()}
+        t = scenes[stride]
+        n, m = t["xyz"].shape[0], t["new_xyz"].shape[0]
+        torch.manual_seed(0)
+        feats = torch.randn(n, CIN, device=dev, requires_grad=True)
+        base = NeighborVoxelSAModuleMSG(query_ranges=[qrange], radii=[radius], nsamples=[S], mlps=[[CIN, C, C]]).to(dev)
+        coords = t["new_coords"][:, [0, 3, 2, 1]].contiguous()
+        with torch.no_grad():
+            idx, empty = base.groupers[0].query(coords, t["xyz"], t["xyz_batch_cnt"], t["new_xyz"], t["new_xyz_batch_cnt"], t["vol"])
+        for dtype in (torch.float16, torch.bfloat16):
+            g = {torch.float32: torch.randn(m, C, device=dev)}
+            g[dtype] = g[torch.float32].to(dtype)
+            mods = {}
+            for route, fused, dt in (("fused16", True, dtype), ("grouped16", False, dtype), ("fused32", True, torch.float32)):
+                mods[route] = (copy.deepcopy(base), dt)
+                mods[route][0].FUSED = fused
+
+            def fwd(route):
+                mod, dt = mods[route]
+
+                def run():
+                    if dt == torch.float32:
+                        return mod(t["xyz"], t["xyz_batch_cnt"], t["new_xyz"], t["new_xyz_batch_cnt"], t["new_coords"], feats, t["vol"])
+                    with torch.autocast("cuda", dtype=dt):
+                        return mod(t["xyz"], t["xyz_batch_cnt"], t["new_xyz"], t["new_xyz_batch_cnt"], t["new_coords"], feats, t["vol"])
+                return run
+
+            def both(route):
+                f, (mod, dt) = fwd(route), mods[route]
+
+                def run():
+                    f().backward(g[dt])
+                    feats.grad = None
+                    for p in mod.parameters():
+                        p.grad = None
+                return run
+            assert fwd("fused16")().dtype == dtype and fwd("grouped16")().dtype == dtype
+            tf = _windows({k: fwd(k) for k in mods}, ROUNDS, REPS)
+            tb = _windows({k: both(k) for k in mods}, ROUNDS, REPS)
+            lines.append("%-9s %-11s | %s %s %s | %s %s %s | %-18s %s" % (
+                str(dtype).replace("torch.", ""), name, _cell(tf["fused16"]), _cell(tf["grouped16"]), _cell(tf["fused32"]), _cell(tb["fused16"]),
+                _cell(tb["grouped16"]), _cell(tb["fused32"]), ahead(tb["fused16"], tb["grouped16"]), ahead(tb["fused16"], tb["fused32"])))
+            print(lines[-1], flush=True)
+        # the op alone through the C entry points, on the grouper's own index lists: fp32, float16, bfloat16
+        with torch.no_grad():
+            conv, bn = base.mlps_pos[0][0], base.mlps_pos[0][1]
+            w, em = conv.weight.detach().view(C, 3).contiguous(), empty.view(torch.uint8)
+            rm, rv, nbt = bn.running_mean.clone(), bn.running_var.clone(), bn.num_batches_tracked.clone()
+            arg = torch.empty(m, C, dtype=torch.uint8, device=dev)
+            keep = torch.empty(nat.lib().fv2p_voxel_pool_saved_bytes(C) // 8, dtype=torch.float64, device=dev)
+            gw, gg, gb = torch.empty(C, 3, device=dev), torch.empty(C, device=dev), torch.empty(C, device=dev)
+            ws = nat.workspace(max(nat.lib().fv2p_voxel_pool_ws_bytes(m, S, C), nat.lib().fv2p_voxel_pool_backward_ws_bytes(m, S, C, n)), dev)
+            st = nat.stream()
+            f32, g32 = torch.randn(n, C, device=dev), torch.randn(m, C, device=dev)
+            routes = {}
+            for dt in (torch.float32, torch.float16, torch.bfloat16):
+                tag = str(dt).replace("torch.", "")
+                f_in, gy, out, gf = f32.to(dt), g32.to(dt), torch.empty(m, C, dtype=dt, device=dev), torch.empty(n, C, dtype=dt, device=dev)
+                sfx, code = ("", ()) if dt == torch.float32 else ("_h", (1 if dt == torch.float16 else 2,))
+                op_f = (lambda f_in=f_in, out=out, sfx=sfx, code=code: nat.call("fv2p_voxel_pool_forward" + sfx, f_in, t["xyz"], t["new_xyz"], idx, em, n, m, S, C, w,
+                                                                                 bn.weight, bn.bias, rm, rv, nbt, 0.1, 1e-5, 1, out, arg, keep, ws, ws.numel(), *code, st))
+                op_b = (lambda a, out=out, gy=gy, sfx=sfx, code=code: (lambda: nat.call("fv2p_voxel_pool_backward" + sfx, t["xyz"], t["new_xyz"], idx, em, n, m, S, C, w,
+                                                                                        bn.weight, out, arg, keep, gy, 1, a, gw, gg, gb, ws, ws.numel(), *code, st)))
+                routes["fwd " + tag], routes["bwd_par " + tag], routes["bwd_all " + tag] = op_f, op_b(None), op_b(gf)
+            # every backward of a format runs on the out / arg that the format's own forward wrote last: the windows go format by format
+            tp = {}
+            for dt in ("float32", "float16", "bfloat16"):
+                routes["fwd " + dt]()
+                tp.update(_windows({k: v for k, v in routes.items() if k.endswith(" " + dt)}, ROUNDS, REPS))
+        for dt in ("float32", "float16", "bfloat16"):
+            ops.append("%-11s %-9s | %s | %s | %s" % (name, dt, _cell(tp["fwd " + dt]), _cell(tp["bwd_par " + dt]), _cell(tp["bwd_all " + dt])))
+    lines += ["", "the op alone through the C entry points (training mode), us: forward (moments, fold, pool) | backward without grad_F (route, fold) | "
+              "backward with grad_F (+ the fixed-order scatter-add of M C single-channel entries); one format after the other, not alternating"] + ops
+    m = 2 * 128 * 216
+    lines += ["", "algorithmic bytes per grouper at M = %d, S = %d, C = %d (from the shapes), 16-bit against fp32:" % (m, S, C),
+              "  forward: %.1f MB gathered F rows (fp32 %.1f) + %.1f MB (idx, xyz rows: moments and pool) + %.1f MB (out, arg; fp32 %.1f)" % (
+                  m * S * C * 2 / 1e6, m * S * C * 4 / 1e6, 2 * m * S * 16 / 1e6, m * C * 3 / 1e6, m * C * 5 / 1e6),
+              "  backward: %.1f MB (out, grad_out, arg read; g and destinations written; fp32 %.1f) + the scatter-add of %d single-channel entries" % (
+                  m * C * (2 + 2 + 1 + 2 + 4) / 1e6, m * C * (4 + 4 + 1 + 4 + 4) / 1e6, m * C)]
+    _write(lines, out_path)
+
+
 def linbn_once():
     """One forward + backward of the fused op per layer of LINBN_LAYERS, for `rocprofv3 --kernel-trace --stats -- python tools/microbench.py linbn_once`."""
     from torch import nn
@@ -1738,6 +1842,9 @@ if __name__ == "__main__":
         sys.exit(0)
     if which == "voxelpool":   # python tools/microbench.py voxelpool [profiles/voxel_pool.txt]
         voxelpool(sys.argv[2] if len(sys.argv) > 2 else None)
+        sys.exit(0)
+    if which == "voxelpool16":   # python tools/microbench.py voxelpool16 [profiles/voxel_pool_half.txt]
+        voxelpool16(sys.argv[2] if len(sys.argv) > 2 else None)
         sys.exit(0)
     if which == "linbn_once":   # rocprofv3 --kernel-trace --stats -- python tools/microbench.py linbn_once
         linbn_once()
