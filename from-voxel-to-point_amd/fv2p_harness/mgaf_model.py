@@ -24,7 +24,9 @@ import torch.nn.functional as F
 from pcdet.ops.DeformableConvolutionV2PyTorch.modules.mdeformable_conv_block import MdeformConvBlock
 from pcdet.ops.DeformableConvolutionV2PyTorch.modules.modulated_deform_conv import ModulatedDeformConv
 
-from pcdet.ops.iou3d_nms import iou3d_nms_utils
+from pcdet.ops.iou3d_nms import iou3d_nms_cuda, iou3d_nms_utils
+
+import fv2p_native as _nat
 
 from .backbone import VoxelResBackBone8x
 from .fv2p_model import box_corners, run_maps, sigmoid_focal
@@ -46,6 +48,9 @@ class MGAFConfig:
     num_iouscore_training_samples = 24
     loss_weights = dict(hm=1.0, offset=1.0, height=1.0, dim=1.0, rot=1.0, segm=1.0, corner=1.0, iouscore=1.0)
     rot_bins, iou_fg_thresh, iou_bg_thresh = 12, 0.75, 0.25
+    # test time: NUM_INFERENCE_SAMPLES of the dense head and POST_PROCESSING of mgaf-3dssd_3classes.yaml
+    num_inference_samples = 50
+    score_thresh, nms_thresh, nms_pre_maxsize, nms_post_maxsize = 0.501, 0.1, 4096, 500
 
 
 class DCNBEVBackbone(nn.Module):
@@ -322,6 +327,130 @@ def center_losses(preds, tg, cfg, peaks=None):
     return total, out
 
 
+# ---------------------------------------------------------------- test time -------------------------------------------------------------
+_PEAK_MAPS = ("hm", "offset", "height", "dim", "rot", "iouscore")
+
+
+def center_peaks_tensor_ops(preds, cfg, k, maxpool=True, cells=None):
+    """predhm_based_predicted_boxes_generation_ssd (center_af_head_template.py:518-598; maxpool=False: ..._nomaxpooling, :600-667) as
+    tensor ops, on the maps' device: the K best peaks of the max-pooled heat map of every sample, decoded.  -> dict: boxes (B, K, 7),
+    cls (B, K, nc) the heat of every class at the cell, score (B, K) the raw IoU-score logit, cell (B, K) int64 = y * W + x,
+    cls_id (B, K) int32.  This is the CPU route of `center_peaks` and the baseline its op is measured against.
+    `cells` (B, K) int64: decode these cells instead of this call's own choice (cls_id is then the first maximal class there)."""
+    hm = preds["hm"].detach()
+    heat = hm * (F.max_pool2d(hm, 3, stride=1, padding=1) == hm).float() if maxpool else hm       # center_utils._nms
+    b, nc, sy, sx = heat.shape
+    if cells is None:
+        top_s, top_i = torch.topk(heat.view(b, nc, -1), k)                                          # center_utils._topk
+        top_s2, top_j = torch.topk(top_s.view(b, -1), k)
+        inds = top_i.view(b, -1).gather(1, top_j)
+        cls_id = torch.div(top_j, k, rounding_mode="floor").int()
+    else:
+        inds = cells
+        cls_id = gather_map(heat, inds).argmax(-1).int()
+    pxs, pys = (inds % sx).float().unsqueeze(-1), torch.div(inds, sx, rounding_mode="floor").float().unsqueeze(-1)
+    offq = gather_map(preds["offset"].detach(), inds)
+    bxs = (pxs + offq[:, :, 0:1]) * cfg.feature_map_stride * cfg.voxel_size[0] + cfg.point_cloud_range[0]
+    bys = (pys + offq[:, :, 1:2]) * cfg.feature_map_stride * cfg.voxel_size[1] + cfg.point_cloud_range[1]
+    rotq = decode_rot_binres(gather_map(preds["rot"].detach(), inds).reshape(b * k, -1), cfg.rot_bins).view(b, k, 1)
+    boxes = torch.cat((bxs, bys, gather_map(preds["height"].detach(), inds), gather_map(preds["dim"].detach(), inds), rotq), 2)
+    return {"boxes": boxes, "cls": gather_map(heat, inds).contiguous(), "score": gather_map(preds["iouscore"].detach(), inds).squeeze(-1),
+            "cell": inds, "cls_id": cls_id}
+
+
+def center_peaks(preds, cfg, k, maxpool=True):
+    """The K best heat-map peaks of every sample, decoded (see center_peaks_tensor_ops for the result).  On a GPU: fv2p_center_peaks,
+    two launches for the whole batch; anywhere else the tensor ops.  Order: descending heat, equal values by ascending
+    class * H * W + cell - the reference's order wherever the K + 1 best values are distinct, the op's own definition where not."""
+    hm = preds["hm"]
+    if not hm.is_cuda:
+        return center_peaks_tensor_ops(preds, cfg, k, maxpool)
+    maps = [preds[n].detach() for n in _PEAK_MAPS]
+    for n, t in zip(_PEAK_MAPS, maps):
+        if t.dtype != torch.float32:
+            raise TypeError(f"center_peaks: map '{n}' is {t.dtype}; the op takes float32 maps only")
+    maps = [t.contiguous() for t in maps]
+    b, nc, sy, sx = hm.shape
+    boxes = torch.empty((b, k, 7), dtype=torch.float32, device=hm.device)
+    cls = torch.empty((b, k, nc), dtype=torch.float32, device=hm.device)
+    score = torch.empty((b, k), dtype=torch.float32, device=hm.device)
+    cell = torch.empty((b, k), dtype=torch.int64, device=hm.device)
+    cls_id = torch.empty((b, k), dtype=torch.int32, device=hm.device)
+    with _nat.device_guard(hm.device):
+        ws = _nat.workspace(int(_nat.lib().fv2p_center_peaks_ws_bytes(b, nc, sy, sx)), hm.device)
+        _nat.call("fv2p_center_peaks", *maps, b, nc, sy, sx, int(k), int(bool(maxpool)), int(cfg.rot_bins), int(cfg.feature_map_stride),
+                  float(cfg.voxel_size[0]), float(cfg.voxel_size[1]), float(cfg.point_cloud_range[0]), float(cfg.point_cloud_range[1]),
+                  boxes, cls, score, cell, cls_id, ws, ws.numel(), _nat.stream())
+    return {"boxes": boxes, "cls": cls, "score": score, "cell": cell, "cls_id": cls_id}
+
+
+def _greedy_nms(boxes, thresh, post_max):
+    """Rotated NMS of boxes (n, 7) already in descending score order -> the first post_max survivors' positions (int64, ascending).
+    On a GPU the device pass of nms_gpu (one 4-byte copy for the count); on the host the greedy loop of iou3d_nms.cpp:121-135 on
+    boxes_bev_iou_cpu."""
+    if boxes.is_cuda:
+        keep, cnt = iou3d_nms_cuda.nms_batch_device(boxes.unsqueeze(0).contiguous(), thresh, int(post_max), False)
+        return keep[0, :int(cnt.item())]
+    iou = iou3d_nms_utils.boxes_bev_iou_cpu(boxes.contiguous(), boxes.contiguous())
+    alive, keep = torch.ones(boxes.shape[0], dtype=torch.bool), []
+    for i in range(boxes.shape[0]):
+        if alive[i]:
+            keep.append(i)
+            if len(keep) == post_max:
+                break
+            alive &= ~(iou[i] > thresh)
+    return torch.tensor(keep, dtype=torch.int64)
+
+
+def detections_tensor_ops(boxes, cls, loc_score, cfg, normalized=False):
+    """The single-class-NMS branch of post_processing_withfgscores (detector3d_template.py:392-415) with
+    class_agnostic_nms_withfgscore (model_nms_utils.py:27-50), sample by sample as the reference: mask, order (a stable descending
+    sort: topk where the scores are distinct, ascending index where they repeat), NMS, index.  The result is padded to the layout of
+    `detections`.  It is the CPU route and the baseline the op is measured against."""
+    b, n = loc_score.shape
+    post = min(cfg.nms_post_maxsize, n)
+    out = {"boxes": boxes.new_zeros(b, post, 7), "scores": boxes.new_zeros(b, post), "labels": torch.zeros(b, post, dtype=torch.int32, device=boxes.device),
+           "index": torch.full((b, post), -1, dtype=torch.int64, device=boxes.device), "count": torch.zeros(b, dtype=torch.int32, device=boxes.device)}
+    for i in range(b):
+        fg, label = torch.max(cls[i] if normalized else torch.sigmoid(cls[i]), dim=-1)
+        original = (fg >= cfg.score_thresh).nonzero().view(-1)
+        if original.numel() == 0:
+            continue
+        order = torch.sort(loc_score[i][original], descending=True, stable=True)[1][:cfg.nms_pre_maxsize]
+        keep = _greedy_nms(boxes[i][original][order], cfg.nms_thresh, post)
+        selected = original[order[keep]]
+        m = selected.numel()
+        out["boxes"][i, :m], out["scores"][i, :m] = boxes[i][selected], loc_score[i][selected]
+        out["labels"][i, :m], out["index"][i, :m], out["count"][i] = (label[selected] + 1).int(), selected, m
+    return out
+
+
+def detections(boxes, cls, loc_score, cfg, normalized=False):
+    """Detections of a batch of decoded candidates: boxes (B, N, 7), cls (B, N, nc) class scores (logits unless `normalized`),
+    loc_score (B, N).  Candidates whose best class score reaches cfg.score_thresh, in descending loc_score (equal scores by ascending
+    index), the first cfg.nms_pre_maxsize of them through rotated NMS at cfg.nms_thresh, the first cfg.nms_post_maxsize survivors.
+    -> dict: boxes (B, P, 7), scores (B, P) the raw loc_score, labels (B, P) int32 from 1, index (B, P) int64 into the N candidates
+    (-1 past the count), count (B) int32, P = min(nms_post_maxsize, N); rows past the count are zero.  On a GPU
+    fv2p_detections_fgscore, with no host synchronisation; anywhere else detections_tensor_ops."""
+    if not boxes.is_cuda:
+        return detections_tensor_ops(boxes, cls, loc_score, cfg, normalized)
+    for name, t in (("boxes", boxes), ("cls", cls), ("loc_score", loc_score)):
+        if t.dtype != torch.float32:
+            raise TypeError(f"detections: '{name}' is {t.dtype}; the op takes float32 only")
+    boxes, cls, loc_score = boxes.detach().contiguous(), cls.detach().contiguous(), loc_score.detach().contiguous()
+    b, n = loc_score.shape
+    post, pre, dev = min(int(cfg.nms_post_maxsize), n), int(cfg.nms_pre_maxsize), boxes.device
+    out = {"boxes": torch.empty((b, post, 7), dtype=torch.float32, device=dev), "scores": torch.empty((b, post), dtype=torch.float32, device=dev),
+           "labels": torch.empty((b, post), dtype=torch.int32, device=dev), "index": torch.empty((b, post), dtype=torch.int64, device=dev),
+           "count": torch.empty((b,), dtype=torch.int32, device=dev)}
+    with _nat.device_guard(dev):
+        ws = _nat.workspace(int(_nat.lib().fv2p_detections_fgscore_ws_bytes(b, n, pre, post)), dev)
+        _nat.call("fv2p_detections_fgscore", boxes, cls, loc_score, b, n, cls.shape[-1], int(bool(normalized)), float(cfg.score_thresh),
+                  float(cfg.nms_thresh), pre, post, out["boxes"], out["scores"], out["labels"], out["index"], out["count"], ws, ws.numel(),
+                  _nat.stream())
+    return out
+
+
 class MGAFDetector(nn.Module):
     def __init__(self, cfg=MGAFConfig, offset_init_std=0.05):
         super().__init__()
@@ -354,3 +483,32 @@ class MGAFDetector(nn.Module):
         if self.taps is not None:
             self.taps.update(preds=preds, targets=targets, terms=terms)
         return loss
+
+    def head_maps(self, voxel_features, voxel_coords, batch_size):
+        """The seven head maps of a batch: sparse backbone, height compression, BEV backbone, centre head."""
+        out, _ = self.backbone_3d(voxel_features, voxel_coords, batch_size)
+        dense = out.dense()
+        spatial = dense.view(batch_size, dense.shape[1] * dense.shape[2], dense.shape[3], dense.shape[4])
+        if getattr(self, "bev_channels_last", False):
+            spatial = spatial.contiguous(memory_format=torch.channels_last)
+        return self.dense_head(self.backbone_2d(spatial))
+
+    @torch.no_grad()
+    def detect(self, preds):
+        """Head maps -> the reference's pred_dicts: the eval branch of CenterAFHeadSingle.forward (center_af_head_single.py:130-138)
+        and Detector3DTemplate.post_processing_withfgscores (detector3d_template.py:318-431, single-class NMS, no recall record).
+        Two library calls and ONE device-to-host copy, of the per-sample counts."""
+        peaks = center_peaks(preds, self.cfg, self.cfg.num_inference_samples)
+        det = detections(peaks["boxes"], peaks["cls"], peaks["score"], self.cfg, normalized=False)   # cls_preds_normalized = False
+        counts = det["count"].cpu().tolist()
+        return [{"pred_boxes": det["boxes"][i, :c], "pred_scores": det["scores"][i, :c], "pred_labels": det["labels"][i, :c].long()}
+                for i, c in enumerate(counts)]
+
+    @torch.no_grad()
+    def predict(self, voxel_features, voxel_coords, batch_size):
+        """Test-time pass: a list of {'pred_boxes' (n, 7), 'pred_scores' (n,), 'pred_labels' (n,) from 1} per sample.  Normalisation
+        layers follow the module's mode: call .eval() first to use their running statistics."""
+        preds = self.head_maps(voxel_features, voxel_coords, batch_size)
+        if self.taps is not None:
+            self.taps.update(preds=preds)
+        return self.detect(preds)

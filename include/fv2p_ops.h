@@ -501,6 +501,55 @@ int fv2p_boxes_iou3d_batch(const float* boxes_a, int batch, int num_a, const flo
                            fv2p_stream_t stream);
 int fv2p_boxes_iou_bev_cpu(const float* boxes_a, int num_a, const float* boxes_b, int num_b, float* ans_iou);
 
+/* ---- centre head at test time: heat-map peak decode and detections --------------------------------
+ * fv2p_center_peaks replaces CenterAFHeadTemplate.predhm_based_predicted_boxes_generation_ssd
+ * (pcdet/models/dense_heads/center_af_head_template.py:518-598; maxpool == 0: ..._nomaxpooling, :600-667) with
+ * center_utils._nms / _topk / _transpose_and_gather_feat and box_utils.decode_rot_binres (pcdet/utils/box_utils.py:366-406) for a
+ * whole batch.  All maps fp32, NCHW, contiguous: hm [B,nc,H,W], offset [B,2,H,W], height [B,1,H,W], dim [B,3,H,W],
+ * rot [B,2*bins,H,W], iouscore [B,1,H,W]; free of NaN.
+ *   heat      = hm * keep, keep = 1.0f where hm equals the maximum of its 3x3 neighbourhood in its own class map (cells outside
+ *               the map take no part, max_pool2d with padding 1), 0.0f elsewhere: a real multiply, a suppressed negative logit
+ *               gives -0.0f.  maxpool == 0: heat = hm.
+ *   selection : per sample the k entries of heat over (class c, cell = y*W + x) that come first when sorted by descending value,
+ *               ties (-0.0f equals 0.0f) by ascending c*H*W + cell.  The reference (two torch.topk) gives this order wherever the
+ *               k+1 best values are distinct; where they are not, torch.topk promises nothing and THIS RULE IS THE OP'S
+ *               DEFINITION.  Zeros of suppressed cells outrank negative peaks, as in the reference.
+ *   decode    : x = ((x + off_x) * float(stride)) * voxel_x + range_x0 in fp32, every product and sum rounded on its own (no
+ *               fused multiply-add); y likewise; height and dim copied; heading from the first maximal bin: bin * per + res *
+ *               (per/2), per = 2 pi / bins, torch's remainder by 2 pi, values above pi lowered by 2 pi.
+ *   outputs   : boxes [B,k,7], cls [B,k,nc] = heat of all classes at the cell, score [B,k] = raw iouscore logit,
+ *               cell [B,k] i64 = y*W + x, cls_id [B,k] i32 = c.
+ * Limits: 1 <= k <= 512, k <= H*W, 1 <= nc <= 16, 1 <= bins <= 32, maxpool 0 or 1, stride >= 1, sizes >= 1 and non-null pointers
+ * (FV2P_EINVAL otherwise); nc*H*W < 2^31 - 4096 and batch <= 65535 (FV2P_ELIMIT); FV2P_EWORKSPACE below fv2p_center_peaks_ws_bytes
+ * (a pure host function; 0 for non-positive sizes).  All checks come before the first launch.
+ * TWO launches whatever the batch: the heat keys of all samples, then one workgroup per sample that finds the bin of the k-th key
+ * with an LDS histogram of the keys' top 12 bits and either sorts the at most 4096 keys from that bin upwards or, in a crowded bin,
+ * finds the k-th key with two more histograms (10 + 10 bits) and collects the larger keys and the ties in index order; then it
+ * decodes.  No float atomics, no global atomics, no workgroup waits for another: bit-identical from run to run and on any stream. */
+size_t fv2p_center_peaks_ws_bytes(int batch, int nc, int h, int w);
+int fv2p_center_peaks(const float* hm, const float* offset, const float* height, const float* dim, const float* rot, const float* iouscore,
+                      int batch, int nc, int h, int w, int k, int maxpool, int bins, int stride, float voxel_x, float voxel_y, float range_x0,
+                      float range_y0, float* boxes, float* cls, float* score, int64_t* cell, int* cls_id, void* ws, size_t ws_bytes,
+                      fv2p_stream_t stream);
+
+/* fv2p_detections_fgscore replaces the single-class-NMS branch of Detector3DTemplate.post_processing_withfgscores
+ * (pcdet/models/detectors/detector3d_template.py:318-431, the branch :392-415) with
+ * model_nms_utils.class_agnostic_nms_withfgscore (pcdet/models/model_utils/model_nms_utils.py:27-50) for a whole batch, without
+ * nonzero() / topk / one host synchronisation per sample.  boxes [B,n,7], cls [B,n,nc], loc_score [B,n], fp32.  Per sample:
+ * fg = max over c of cls (of 1 / (1 + exp(-cls)) when normalized == 0), label = first maximal class + 1; candidates with
+ * fg >= score_thresh, ordered by descending loc_score (ties, -0.0f equal to 0.0f, by ascending candidate index - where
+ * loc scores repeat torch.topk promises nothing and this rule is the op's definition), cut at pre_max; rotated NMS at nms_thresh
+ * (fv2p_nms_batch: rejected candidates are ordered last as zero-sized boxes far outside the scene, whose IoU with anything is 0), the
+ * first post_max survivors.  out_boxes [B,post_max,7], out_scores [B,post_max] = raw loc_score (src_box_scores[selected]),
+ * out_labels [B,post_max] i32, out_index [B,post_max] i64 = index into the n candidates, count [B] i32 on the device; rows past
+ * count are zero with out_index -1.  1 <= n <= 4096, 1 <= post_max <= n, pre_max >= 1, nc >= 1, batch >= 1 (FV2P_EINVAL); batch <= 65535
+ * (FV2P_ELIMIT).  One ordering-and-gather launch, fv2p_nms_batch (two memsets, then a mask and a greedy launch per chunk of row blocks; one
+ * chunk where min(n, pre_max) <= 2 * post_max), one output launch; the number does not depend on the batch. */
+size_t fv2p_detections_fgscore_ws_bytes(int batch, int n, int pre_max, int post_max);
+int fv2p_detections_fgscore(const float* boxes, const float* cls, const float* loc_score, int batch, int n, int nc, int normalized,
+                            float score_thresh, float nms_thresh, int pre_max, int post_max, float* out_boxes, float* out_scores,
+                            int* out_labels, int64_t* out_index, int* count, void* ws, size_t ws_bytes, fv2p_stream_t stream);
+
 /* ---- (f).4: second-stage target sampling --------------------------------------------------------
  * Replaces ProposalTargetLayer.sample_rois_for_rcnn / subsample_rois
  * (pcdet/models/roi_heads/target_assigner/proposal_target_layer.py:92-217; thresholds of ROI_HEAD.TARGET_CONFIG) for a whole

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Per-kernel timings on one GPU (events on the launch stream). Not part of the product or of bench.py; used to
-iterate on kernel variants:  python tools/microbench.py [conv|conv16|amp16|bn16|bn2d|bn2d16|linbn|linbn16|voxelpool|voxelpool16|bev16|beventry|exit16|batch16|sa16|dcn|dcn16|dcn16bwd|fps|voxel|nms|all]"""
+iterate on kernel variants:  python tools/microbench.py [conv|conv16|amp16|bn16|bn2d|bn2d16|linbn|linbn16|voxelpool|voxelpool16|bev16|beventry|centerpeaks|exit16|batch16|sa16|dcn|dcn16|dcn16bwd|fps|voxel|nms|all]"""
 import os
 import sys
 import time
@@ -1445,6 +1445,54 @@ def beventry(out_path=None):
     _write(lines, out_path)
 
 
+def _device_launches(fn):
+    """-> (kernels, memsets and copies one call of `fn` puts on the device, the sum of their own durations in us): torch.profiler, after
+    a warm call.  The second figure leaves out the host's share of a call and the gaps between launches."""
+    from torch.profiler import ProfilerActivity, profile
+    fn()
+    torch.cuda.synchronize()
+    with profile(activities=[ProfilerActivity.CUDA]) as prof:
+        fn()
+        torch.cuda.synchronize()
+    on_device = [e for e in prof.events() if e.device_type == torch.autograd.DeviceType.CUDA]
+    return len(on_device), sum(e.time_range.elapsed_us() for e in on_device)
+
+
+def centerpeaks(out_path=None):
+    """The centre head's test-time glue on its two routes: `op` = fv2p_center_peaks / fv2p_detections_fgscore, `tensor ops` =
+    center_peaks_tensor_ops / detections_tensor_ops (the reference's own composition; per-sample Python loop and one host synchronisation
+    per sample in the detections).  Maps [4, 3, 200, 176] of seeded normal logits, K = 24 (the training term) and K = 50 (test time); the
+    post-processing of predict at B = 4, N = 50 on the K = 50 peaks, at the yaml's thresholds and at a score threshold that passes
+    about half.  Each figure: the median of ROUNDS windows of REPS calls, the routes taken alternately in one process; +- is half the
+    range of the windows.  Launches: what one call puts on the device (kernels, memsets, copies)."""
+    from fv2p_harness import mgaf_model as mm
+    dev = torch.device("cuda:0")
+    ROUNDS, REPS = 7, 20
+    g = torch.Generator().manual_seed(8)
+    chans = {"hm": 3, "offset": 2, "height": 1, "dim": 3, "rot": 24, "iouscore": 1}
+    preds = {n: torch.randn(4, c, 200, 176, generator=g).to(dev) for n, c in chans.items()}
+    cfg = mm.MGAFConfig
+    lines = ["centre head at test time, us per call: median of %d windows of %d calls, +- half the range; launches per call / us inside them"
+             % (ROUNDS, REPS), "%-44s %-16s %-16s %-10s %-9s %-9s" % ("case", "op", "tensor ops", "op/tensor", "op", "tensor")]
+
+    def row(name, routes):
+        t = _windows(routes, ROUNDS, REPS)
+        n = {k: _device_launches(fn) for k, fn in routes.items()}
+        lines.append("%-44s %-16s %-16s %-10.2f %-9s %-9s" % (name, _cell(t["op"]), _cell(t["tensor"]), np.median(t["op"]) / np.median(t["tensor"]),
+                                                             "%d/%.0f" % n["op"], "%d/%.0f" % n["tensor"]))
+        print(lines[-1], flush=True)
+    for k in (24, 50):
+        row("center_peaks [4, 3, 200, 176] K = %d" % k, {"op": lambda: mm.center_peaks(preds, cfg, k), "tensor": lambda: mm.center_peaks_tensor_ops(preds, cfg, k)})
+    peaks = mm.center_peaks(preds, cfg, 50)
+    half = type("Half", (cfg,), {"score_thresh": float(torch.sigmoid(peaks["cls"]).amax(-1).median())})
+    for name, c in (("yaml thresholds", cfg), ("score threshold at the median", half)):
+        counts = mm.detections(peaks["boxes"], peaks["cls"], peaks["score"], c)["count"].cpu().tolist()
+        row("detections B = 4, N = 50, %s %s" % (name, counts),
+            {"op": lambda: mm.detections(peaks["boxes"], peaks["cls"], peaks["score"], c),
+             "tensor": lambda: mm.detections_tensor_ops(peaks["boxes"], peaks["cls"], peaks["score"], c)})
+    _write(lines, out_path)
+
+
 def bev16(out_path=None):
     """The bilinear gather and its gradient at 3 x 2048 key points on a [3, 256, 200, 176] map in 16-bit storage (fv2p_bev_interp_fwd_h /
     _bwd_h) against the fp32 op on an fp32 map (gradient in the fixed-order form, the only one the 16-bit op has) and against the route
@@ -1854,6 +1902,9 @@ if __name__ == "__main__":
         sys.exit(0)
     if which == "beventry":   # python tools/microbench.py beventry [profiles/bev_entry.txt]
         beventry(sys.argv[2] if len(sys.argv) > 2 else None)
+        sys.exit(0)
+    if which == "centerpeaks":   # python tools/microbench.py centerpeaks [profiles/center_peaks.txt]
+        centerpeaks(sys.argv[2] if len(sys.argv) > 2 else "profiles/center_peaks.txt")
         sys.exit(0)
     if which == "bev16":   # python tools/microbench.py bev16 [profiles/bev_half.txt]
         bev16(sys.argv[2] if len(sys.argv) > 2 else None)
