@@ -184,12 +184,22 @@ __global__ void pairwise_iou3d_batch(int na, const float* __restrict__ A, int nb
 // 64 x 64 tile are such pairs.  A lane's row box meets the tile's column boxes one by one, so skipping per lane would not help (some
 // lane always has a near partner); instead every lane first collects its near columns as a bit mask (a few flops per pair), the
 // tile's candidates are numbered by a wave prefix sum, and the ~1000-instruction overlap is evaluated for 64 candidates at a time,
-// whatever rows they belong to.  The suppression bits are exactly those of the plain loop (the pre-test only drops pairs whose
-// overlap is zero).
+// whatever rows they belong to.
+//
+// The pre-test may only drop pairs whose overlap is exactly 0 in box_overlap, and disjoint boxes are not enough for that: in_box2d
+// accepts a corner up to MARGIN = 1e-2 outside a box along each of its axes, so two boxes up to a centimetre apart still collect
+// corners and get a polygon with an area (with footprints of a few centimetres, IoUs above 1).  What box_overlap needs for any point at
+// all is a crossing of two edges, which lies within ra of one centre and rb of the other, or a corner of one box (within its own
+// half-diagonal of its centre) accepted by the other, i.e. within sqrt((dx/2 + MARGIN)^2 + (dy/2 + MARGIN)^2) <= r + MARGIN sqrt(2)
+// of the other centre.  Either way the centres are at most ra + rb + 1.415e-2 apart.  The reach below is that plus 8.5e-4 + 0.1 % of
+// ra + rb + 1e-4 for the fp32 roundings of the corners, of the radii and of the test itself (corners round to half a float32 step of
+// the coordinates: 1.2e-4 at 2 km).  With it the suppression bits are exactly those of the plain loop at any box size
+// (tests/test_iou3d_cases_cpu.py holds the premise, tests/test_iou3d_edges_gpu.py the survivors).  At car size the reach grows from
+// 4.2 m to 4.215 m: the candidate count does not move (profiles/nms_pretest_margin.txt).
 __device__ __forceinline__ bool circles_apart(const float* a, const float* b) {
   const float dx = a[0] - b[0], dy = a[1] - b[1];
   const float ra = 0.5f * sqrtf(a[3] * a[3] + a[4] * a[4]), rb = 0.5f * sqrtf(b[3] * b[3] + b[4] * b[4]);
-  const float reach = (ra + rb) * 1.001f + 1e-4f;   // margin: a pair is dropped only when it is clearly apart
+  const float reach = (ra + rb) * 1.001f + 1e-4f + 1.5e-2f;   // tests/test_iou3d_cases_cpu.py: CIRCLE_EXTRA
   return dx * dx + dy * dy > reach * reach;
 }
 
